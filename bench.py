@@ -5,7 +5,17 @@ candidates per block, n_steps=1) over the job's synthetic blocks (config C4:
 10^6 blocks x d=32), inputs resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c5|c1|...]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line: value,
+ms_per_step and the figures the timed steps yield by themselves.  --full adds
+everything that takes runs of its own (the CPU oracle baseline and parity
+check, the PCIe-inclusive and decoder passes, single-call and pipelined
+comparisons, the grouped configs' scoring-timer pass); in a plain line those
+fields are null.  --dump-outputs DIR writes the last timed step's results as
+DIR/<name>.npy (same arguments, same inputs: two builds compare output for
+output).
 
 With --gpus N > 1 and no launcher environment, bench.py starts the N rank
 processes itself (one per GPU; the parent never touches the GPU).  Block
@@ -101,6 +111,16 @@ def parse():
                     choices=sorted(CONFIGS) + sorted(GROUPED) + sorted(IMPORTANCE) + sorted(PLN))
     ap.add_argument("--blocks", type=int, default=0, help="override the config's block count (the whole job under strong scaling, "
                          "per rank under weak)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU oracle "
+                         "baseline and parity check, the PCIe-inclusive and decoder passes, the "
+                         "single-call / pipelined comparisons and the scoring-kernel timing "
+                         "passes (--no-cpu, --no-e2e, --per-image and --batch-only narrow it); "
+                         "without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (float32/float64; a fixed seeded sample of the blocks "
+                         "where the whole output would pass 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -127,7 +147,51 @@ def parse():
         args.steps = 3 if block else 20
     if args.warmup is None:
         args.warmup = 1 if block else 3
+    if not args.full:
+        args.no_cpu = args.no_e2e = True
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files of one run together
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: array} as out_dir/<name>.npy, float32 kept
+    and everything else (indices, offsets, bytes) widened to float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would pass {DUMP_LIMIT_BYTES} bytes")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def grouped_dump(res, bits, n_steps):
+    """The arrays of a grouped greedy step's results [(sample, bitcode, group
+    starts)]: the latent sets' samples, per-group indices (the bitcode's
+    fields) and group starts, each concatenated in call order."""
+    from compression_without_quantization_amd.binary_io import bitcode_to_indices
+    idx = [np.asarray(bitcode_to_indices(r[1], bits, (len(r[2]) - 1) * n_steps)).reshape(-1)
+           for r in res]
+    return {"sample": np.concatenate([np.asarray(r[0], np.float32).reshape(-1) for r in res]),
+            "indices": np.concatenate(idx) if idx else np.zeros(0),
+            "group_starts": np.concatenate([np.asarray(r[2], np.int64) for r in res])}
+
+
+def importance_dump(res):
+    """The arrays of a grouped importance step's results [(sample, Elias-delta
+    bitcode, group starts, (outlier positions, outlier quint16 values))],
+    each concatenated over the images in call order."""
+    idx = [np.asarray(C.elias_delta_decode_many(r[1], len(r[2]) - 1)[0]
+                      if isinstance(r[1], str) else r[1], np.int64).reshape(-1) for r in res]
+    cat = lambda xs: np.concatenate([np.asarray(x).reshape(-1) for x in xs])
+    return {"sample": cat([np.asarray(r[0], np.float32) for r in res]), "indices": cat(idx),
+            "group_starts": cat([np.asarray(r[2], np.int64) for r in res]),
+            "outlier_positions": cat([r[3][0] for r in res]),
+            "outlier_values": cat([r[3][1] for r in res])}
 
 
 def grouped_main(args):
@@ -216,6 +280,8 @@ def grouped_main(args):
         if os.environ.get("CWQ_BENCH_STEP_TIMES"):  # diagnostics: each step's wall time
             print("step ms:", " ".join(f"{(b - a) * 1e3:.2f}" for a, b in zip([t0] + per, per)),
                   file=sys.stderr, flush=True)
+        if not args.full:  # the scoring timers take a pass of their own
+            return el, res, 0.0
         if step is step_single:
             make_pairs(args.steps * len(lat))
         evq.clear()
@@ -228,7 +294,9 @@ def grouped_main(args):
         return el, res, kms
 
     batch = len(lat) > 1 and not args.per_image
-    if batch and args.batch_only:
+    if batch and (args.batch_only or not args.full):
+        # the headline of a config of several latent sets is the batched call;
+        # the single calls beside it are a --full comparison
         el, res, kernel_ms = timed(step_batch)
         batched = {"latent_sets_per_call": len(lat), "equal_to_single_calls": None,
                    "single_call_images_per_s": None}
@@ -236,7 +304,7 @@ def grouped_main(args):
         el_single, res, kms_single = timed(step_single)
         el, kernel_ms = el_single, kms_single
         batched = None
-    if batch and not args.batch_only:
+    if batch and args.full and not args.batch_only:
         el, res_b, kernel_ms = timed(step_batch)
         same = all(list(a[2]) == list(b[2]) and a[1] == b[1] and
                    np.array_equal(np.asarray(a[0]).view(np.uint32), np.asarray(b[0]).view(np.uint32))
@@ -246,7 +314,10 @@ def grouped_main(args):
                    "single_call_scoring_kernel_ms": round(kms_single, 4)}
         if not same:
             raise SystemExit("bench.py: batched results differ from the single calls")
-    if batch:
+        res = res_b  # the headline path's results (equal to the single calls')
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, grouped_dump(res, bits, n_steps))
+    if batch and args.full:
         # the same steps with the calls pipelined two deep (defer=True: step k + 1
         # is queued before step k's results are collected), so the host work
         # between calls overlaps the device work; reported beside value
@@ -458,7 +529,7 @@ def importance_main(args):
 
     batch = n_img > 1 and not args.per_image
     batched = None
-    if batch and args.batch_only:
+    if batch and (args.batch_only or not args.full):
         el, res, kernel_ms = timed(step_batch)
         batched = {"images_per_call": n_img, "equal_to_single_calls": None,
                    "single_call_images_per_s": None}
@@ -477,9 +548,12 @@ def importance_main(args):
             batched = {"images_per_call": n_img, "equal_to_single_calls": bool(same),
                        "single_call_images_per_s": n_img * args.steps / el_s,
                        "single_call_scoring_kernel_ms": round(kms_s, 4)}
-    # work: sum over groups of N_g * d_g candidate-dims (the plan the coder used)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, importance_dump(res))
+    # work: sum over groups of N_g * d_g candidate-dims (the plan the coder used);
+    # recomputing the plan takes device passes of its own (--full)
     cand_dims = 0
-    for (t, p), r in zip(lat, res):
+    for (t, p), r in zip(lat, res) if args.full else ():
         starts = np.asarray(r[2], dtype=np.int64)
         cand_dims += _importance_work(t, p, starts, kl_lim, dev)
     groups = sum(len(r[2]) - 1 for r in res)
@@ -501,8 +575,9 @@ def importance_main(args):
             "data": "synthetic PLN-like latents",
             "config": {"workload": desc, "groups_per_step": groups, "bits_per_step": bitlen,
                        "groups_per_s": groups * args.steps / el,
-                       "candidate_dims_per_step": cand_dims,
-                       "candidate_dims_per_s": cand_dims * args.steps / el,
+                       "candidate_dims_per_step": cand_dims if args.full else None,
+                       "candidate_dims_per_s": (cand_dims * args.steps / el
+                                                if args.full else None),
                        "mode": ("code_grouped_importance_sample_batch: every image of a step in "
                                 "one call" if batched else
                                 "one code_grouped_importance_sample call per image"),
@@ -539,7 +614,7 @@ def scoring_roofline(config, groups, alg, kernel_ms, cand_dims, kernel, timing):
             "algorithmic_bytes_per_launch": alg,
             "valu": {"unit": "candidate-dims/s",
                      "nominal_candidate_dims_per_s": (cand_dims / (kernel_ms * 1e-3)
-                                                      if kernel_ms > 0 else None),
+                                                      if kernel_ms > 0 and cand_dims else None),
                      "valu_issue_frac": valu,
                      "valu_issue_frac_scoring_launches": (agg or {}).get("valu_issue_frac"),
                      "valu_issue_source": (f"profiles/traffic_{config}.json: 2 * SQ_INSTS_VALU / "
@@ -682,18 +757,29 @@ def pln_main(args):
             first_level_max_group_size_bits=4) for p in paths]
     for w in range(args.warmup):
         compress(capture=(w == args.warmup - 1))
-        decompress()
+        if args.full:
+            decompress()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
         summ = compress(capture=(k == 0 and args.warmup == 0))
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        rec = decompress()
-    torch.cuda.synchronize()
-    eld = time.perf_counter() - t0
+    if args.dump_outputs:  # the .miracle files of the last compress, byte for byte
+        blobs = []
+        for p in paths:
+            with open(p, "rb") as f:
+                blobs.append(np.frombuffer(f.read(), np.uint8))
+        dump_outputs(args.dump_outputs, {
+            "miracle_bytes": np.concatenate(blobs),
+            "miracle_sizes": np.array([b.size for b in blobs], np.int64)})
+    rec = eld = None
+    if args.full:  # the decoder, timed beside the headline
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            rec = decompress()
+        torch.cuda.synchronize()
+        eld = time.perf_counter() - t0
     l1, l2 = cap["level1"], cap["level2"]
     D1, D2 = l1["q_loc"].size, l2["q_loc"].size
     G1, G2 = len(l1["result"][2]) - 1, len(l2["result"][2]) - 1
@@ -719,13 +805,13 @@ def pln_main(args):
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic image, seeded random PLN weights (no checkpoint offline)",
             "config": {"workload": desc, "groups_per_step": (G1 + G2) * n_img,
-                       "decompress_images_per_s": n_img * args.steps / eld,
+                       "decompress_images_per_s": n_img * args.steps / eld if eld else None,
                        "bytes": summ[0]["actual_byte_size"], "bpp": summ[0]["bpp"],
                        "kl_bits_level1": summ[0]["first_level_theoretical"] * 8,
                        "kl_bits_level2": summ[0]["second_level_theoretical"] * 8,
                        "groups_level1": summ[0]["first_level_groups"],
                        "groups_level2": summ[0]["second_level_groups"],
-                       "reconstruction_shape": list(rec[0].shape)},
+                       "reconstruction_shape": list(rec[0].shape) if rec else None},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity}
     print(json.dumps(line), flush=True)
 
@@ -963,6 +1049,24 @@ def devices_distinct(rank_devices):
     return len(set(keys)) == len(keys)
 
 
+def block_dump(out_idx, out_sample, nb, d, n_steps, suffix=""):
+    """--dump-outputs for a block config: every block's indices, and the
+    samples of all blocks, or of a fixed seeded choice of them (its block
+    numbers are written too) where all would pass the dump's size limit."""
+    idx = out_idx.cpu().numpy().reshape(nb, n_steps)
+    room = DUMP_LIMIT_BYTES * 3 // 4 - idx.size * 8
+    smp = out_sample.cpu().numpy().reshape(nb, d)
+    out = {"idx" + suffix: idx}
+    if smp.nbytes > room:
+        keep = max(1, room // (d * 4 + 8))
+        pick = np.sort(np.random.default_rng(20261015).choice(nb, size=min(nb, keep),
+                                                              replace=False))
+        out["sample_blocks" + suffix] = pick
+        smp = smp[pick]
+    out["sample" + suffix] = smp
+    return out
+
+
 def oracle_check(O, host, d, bits, n_steps, seed, block_id_base, idx_h, samp_h, blocks, nthr):
     """Indices and sample words of `blocks` (local block numbers) against the
     CPU oracle: the checker, outside every timed region."""
@@ -1087,6 +1191,9 @@ def main():
         elapsed, eval_ms_max = float(e[0].item()), float(e[1].item())
     else:
         eval_ms_max = eval_ms
+    if args.dump_outputs and nb:
+        dump_outputs(args.dump_outputs, block_dump(out_idx, out_sample, nb, d, n_steps,
+                                                   "" if world == 1 else f"_rank{rank}"))
 
     # PCIe-inclusive single pass (host arrays in, indices + samples out): reported aside
     e2e = e2e_streamed = None
@@ -1122,23 +1229,25 @@ def main():
 
     # decoder throughput on the same blocks (reported aside), with its own
     # HIP-event kernel time
-    dec_out = torch.empty_like(out_sample)
-    C.decode_blocks(out_idx, t["prior_loc"], t["prior_scale"], bits, n_steps, seed, block_dim=d,
-                    block_id_base=block_id_base, out_sample=dec_out)
-    torch.cuda.synchronize()
-    da = torch.cuda.Event(enable_timing=True)
-    db = torch.cuda.Event(enable_timing=True)
-    n_dec = 5
-    da.record()
-    for _ in range(n_dec):
+    dec_ms = decode_bps = roundtrip_ok = None
+    if args.full:
+        dec_out = torch.empty_like(out_sample)
         C.decode_blocks(out_idx, t["prior_loc"], t["prior_scale"], bits, n_steps, seed,
                         block_dim=d, block_id_base=block_id_base, out_sample=dec_out)
-    db.record()
-    torch.cuda.synchronize()
-    dec_ms = da.elapsed_time(db) / n_dec
-    decode_bps = nb / (dec_ms * 1e-3) if nb else 0.0
-    roundtrip_ok = bool(torch.equal(dec_out.view(torch.int32), out_sample.view(torch.int32)))
-    if dist:
+        torch.cuda.synchronize()
+        da = torch.cuda.Event(enable_timing=True)
+        db = torch.cuda.Event(enable_timing=True)
+        n_dec = 5
+        da.record()
+        for _ in range(n_dec):
+            C.decode_blocks(out_idx, t["prior_loc"], t["prior_scale"], bits, n_steps, seed,
+                            block_dim=d, block_id_base=block_id_base, out_sample=dec_out)
+        db.record()
+        torch.cuda.synchronize()
+        dec_ms = da.elapsed_time(db) / n_dec
+        decode_bps = nb / (dec_ms * 1e-3) if nb else 0.0
+        roundtrip_ok = bool(torch.equal(dec_out.view(torch.int32), out_sample.view(torch.int32)))
+    if dist and args.full:
         ok_t = torch.tensor([0 if roundtrip_ok else 1], dtype=torch.int64,
                             device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(ok_t)
@@ -1325,8 +1434,9 @@ def main():
             "pcie_inclusive_blocks_per_s": e2e,
             "pcie_inclusive_streamed_blocks_per_s": e2e_streamed,
             "decode_blocks_per_s": decode_bps,
-            "decode_kernel_ms": round(dec_ms, 4),
-            "decode_hbm_gbs": nb * (12 * d + 4 * n_steps) / (dec_ms * 1e-3) / 1e9 if nb else None,
+            "decode_kernel_ms": None if dec_ms is None else round(dec_ms, 4),
+            "decode_hbm_gbs": (nb * (12 * d + 4 * n_steps) / (dec_ms * 1e-3) / 1e9
+                               if nb and dec_ms else None),
             "decode_roundtrip_bit_exact": roundtrip_ok,
             "eval_kernel_ms_max_over_ranks": round(eval_ms_max, 3),
         }

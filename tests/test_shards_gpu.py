@@ -397,7 +397,7 @@ def test_bench_launches_two_ranks_itself(cwq):
     between them (strong scaling) and checks every rank's sample against the
     oracle: one JSON line with n_gpus == 2 and no mismatch."""
     line = _bench(["--gpus", "2", "--blocks", "8192", "--steps", "1", "--warmup", "0",
-                   "--no-e2e"])
+                   "--no-e2e", "--full"])
     assert line["n_gpus"] == 2 and line["config"]["world_size_checked"] == 2
     assert line["scaling"] == "strong"
     assert line["config"]["blocks_total"] == 8192 and line["config"]["blocks_per_gpu"] == 4096
@@ -502,7 +502,8 @@ def test_bench_eight_ranks_rehearsal(cwq, config, blocks, check):
     its shard): one line, world size 8, no mismatch.  C4-shaped (16 bits) and
     C5-shaped (2^24 candidates per block, the multi-tile blocks) cases."""
     line = _bench(["--gpus", "8", "--config", config, "--blocks", str(blocks), "--steps", "1",
-                   "--warmup", "0", "--no-e2e", "--check-blocks", str(check)], timeout=600)
+                   "--warmup", "0", "--no-e2e", "--full", "--check-blocks", str(check)],
+                  timeout=600)
     assert line["n_gpus"] == 8 and line["config"]["world_size_checked"] == 8
     assert line["scaling"] == "strong" and line["config"]["blocks_total"] == blocks
     _check_shards(line, 8, blocks)
@@ -516,7 +517,7 @@ def test_bench_eight_ranks_rehearsal(cwq, config, blocks, check):
 
 def test_bench_weak_scaling_two_ranks(cwq):
     line = _bench(["--gpus", "2", "--blocks", "2048", "--steps", "1", "--warmup", "0",
-                   "--no-e2e", "--scaling", "weak", "--config", "c4"])
+                   "--no-e2e", "--full", "--scaling", "weak", "--config", "c4"])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak"
     assert line["config"]["blocks_total"] == 4096 and line["config"]["blocks_per_gpu"] == 2048
     assert line["parity"]["index_mismatches"] == 0

@@ -7,7 +7,7 @@ Usage: python tools/collect_profile.py [--runs R] CONFIG TAG DOMINANT [SCORING .
 DOMINANT selects the kernel the bench line's roofline prices (every dispatch
 whose name contains it); SCORING (default: DOMINANT) the substrings of every
 candidate-scoring launch of one step (e.g. k_small_prep1 k_small_one
-k_small_finalize for the small pipeline).  The PMC passes ran `bench.py
+k_small_finalize for the small pipeline).  The PMC passes ran `bench.py --full
 --steps 1 --warmup 0`; R (default 1) is how many times that run executes
 the step: 2 for the grouped greedy configs (bench.py's timed() runs the step
 once without and once with the scoring timers), 1 for the importance and PLN
@@ -107,7 +107,7 @@ def main():
            "method": "rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ_INSTS_VALU "
                      "SQ_INSTS_SALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE | SQ_WAVE_CYCLES "
                      "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_WAVES) of `python3 "
-                     "bench.py --steps 1 --warmup 0 --no-cpu --no-e2e`, one pass each "
+                     "bench.py --full --steps 1 --warmup 0 --no-cpu --no-e2e`, one pass each "
                      "(tools/gpu_task.sh pmc); tools/collect_profile.py + tools/pmc_frac.py"}
     with open(os.path.join(dst, f"traffic_{config}.json"), "w") as fh:
         json.dump(out, fh, indent=1)

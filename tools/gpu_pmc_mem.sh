@@ -5,7 +5,7 @@ set -o pipefail
 export TMPDIR=/tmp
 C=${1:-c2low}
 T=${2:-$C}
-B="bench.py --no-cpu --no-e2e --config $C --steps 1 --warmup 0"
+B="bench.py --full --no-cpu --no-e2e --config $C --steps 1 --warmup 0"
 O=gpurun_out/pmcm_$T
 p() { timeout -s KILL 120 rocprofv3 --pmc "$@" -d $O/$1 -o run --output-format csv -- python3 $B > $O.$1.log 2>&1; }
 mkdir -p $O

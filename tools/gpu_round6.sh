@@ -13,11 +13,11 @@ mkdir -p gpurun_out
 part=$1; shift
 bargs() {  # per-config bench arguments of the evidence lines
   case $1 in
-    c4) echo "--config c4" ;;
-    c5|c2cli|c2low|i1) echo "--config $1 --steps 3 --warmup 1" ;;
-    pln) echo "--config pln --steps 3 --warmup 2" ;;  # the capture (last warmup) warm
-    c2) echo "--config c2 --steps 100 --warmup 5" ;;
-    *) echo "--config $1 --steps 20 --warmup 3" ;;
+    c4) echo "--full --config c4" ;;
+    c5|c2cli|c2low|i1) echo "--full --config $1 --steps 3 --warmup 1" ;;
+    pln) echo "--full --config pln --steps 3 --warmup 2" ;;  # the capture (last warmup) warm
+    c2) echo "--full --config c2 --steps 100 --warmup 5" ;;
+    *) echo "--full --config $1 --steps 20 --warmup 3" ;;
   esac
 }
 pargs() {  # profiling runs: the batched call alone for the multi-image configs
@@ -38,13 +38,13 @@ case $part in
   trace)
     for c in "$@"; do
       timeout -s KILL 240 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_r06_${c}_trace -o run \
-        --output-format csv -- python3 bench.py --no-cpu --no-e2e $(pargs $c) --steps 3 --warmup 1 \
+        --output-format csv -- python3 bench.py --full --no-cpu --no-e2e $(pargs $c) --steps 3 --warmup 1 \
         > gpurun_out/prof_r06_${c}_trace.log 2>&1 || exit 1
       echo trace $c ok
     done ;;
   pmc)
     for c in "$@"; do
-      B="bench.py --no-cpu --no-e2e $(pargs $c) --steps 1 --warmup 0"
+      B="bench.py --full --no-cpu --no-e2e $(pargs $c) --steps 1 --warmup 0"
       timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/prof_r06_${c}_fetch -o run --output-format csv -- python3 $B > gpurun_out/prof_r06_${c}_fetch.log 2>&1 && \
       timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/prof_r06_${c}_write -o run --output-format csv -- python3 $B > gpurun_out/prof_r06_${c}_write.log 2>&1 && \
       timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -d gpurun_out/prof_r06_${c}_valu -o run --output-format csv -- python3 $B > gpurun_out/prof_r06_${c}_valu.log 2>&1 && \

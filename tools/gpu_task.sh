@@ -35,16 +35,16 @@ run_one() {
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" \
         > gpurun_out/smoke.log 2>&1 && echo smoke ok ;;
     bench)
-      local c=${1%%@*} n=${1/@/_}; shift
+      local c=${1%%@*} n=${1/@/_}; shift; set -- --full "$@"
       timeout -k 10 600 python -u bench.py --config $c "$@" > gpurun_out/b_$n.log 2>&1 && \
         tail -1 gpurun_out/b_$n.log | cut -c1-200 ;;
     trace)
       local tag=$1; shift
-      BARGS="$* --steps 3 --warmup 1" prof prof_${tag}_trace --kernel-trace --stats && \
+      BARGS="--full $* --steps 3 --warmup 1" prof prof_${tag}_trace --kernel-trace --stats && \
         echo trace $tag ok ;;
     pmc)
       local tag=$1 set=$2; shift 2
-      BARGS="$* --steps 1 --warmup 0"
+      BARGS="--full $* --steps 1 --warmup 0"
       case $set in
         mem)  prof prof_${tag}_fetch --pmc FETCH_SIZE && prof prof_${tag}_write --pmc WRITE_SIZE ;;
         valu) prof prof_${tag}_valu --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE ;;
@@ -80,9 +80,9 @@ run_one() {
         python -u tools/prune_stats.py $nb > gpurun_out/s_$tag.log 2>&1 && head -3 gpurun_out/s_$tag.log ;;
     c2parts)
       timeout -k 10 300 python -u tools/c2_parts.py > gpurun_out/c2parts.log 2>&1 && cat gpurun_out/c2parts.log && \
-      CWQ_LIB_PATH=$PWD/tools/vrun/libcwq_phases.so timeout -k 10 300 python -u bench.py --config c2 \
+      CWQ_LIB_PATH=$PWD/tools/vrun/libcwq_phases.so timeout -k 10 300 python -u bench.py --full --config c2 \
         --no-cpu --no-e2e --steps 5 > gpurun_out/c2phases.log 2>&1 && grep cwq gpurun_out/c2phases.log | tail -8 && \
-      CWQ_LIB_PATH=$PWD/tools/vrun/libcwq_phases.so timeout -k 10 300 python -u bench.py --config c3 \
+      CWQ_LIB_PATH=$PWD/tools/vrun/libcwq_phases.so timeout -k 10 300 python -u bench.py --full --config c3 \
         --batch-only --no-cpu --no-e2e --steps 3 > gpurun_out/c3phases.log 2>&1 && grep "cwq batch" gpurun_out/c3phases.log | tail -4 ;;
     decvar)  # decode timing per variant, after its decode tests against the oracle
       for v in $1; do
@@ -101,7 +101,7 @@ run_one() {
       timeout -k 10 300 python -u "$@" > gpurun_out/py_$tag.log 2>&1 && tail -4 gpurun_out/py_$tag.log ;;
     timeline)  # kernel + copy trace of a bench run, then tools/timeline.py on it
       local tag=$1; shift
-      BARGS="$* --steps 3 --warmup 1" prof prof_${tag}_tl --kernel-trace --memory-copy-trace --stats && \
+      BARGS="--full $* --steps 3 --warmup 1" prof prof_${tag}_tl --kernel-trace --memory-copy-trace --stats && \
         python3 tools/timeline.py gpurun_out/prof_${tag}_tl ${TL_MS:-12} > gpurun_out/tl_$tag.txt && \
         tail -3 gpurun_out/tl_$tag.txt ;;
     ktimeline)  # ktimeline TAG WINDOW_MS SCRIPT [args]: kernel trace of a tools/ script + timeline.py
