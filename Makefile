@@ -15,8 +15,9 @@ all: $(ORACLE_SO) $(MATHCHECK_SO) $(ROCRAND_PIN_SO) $(CAPI_DEMO)
 $(ORACLE_SO): oracle/cwq_oracle.c
 	$(CC) -O2 -ffp-contract=off -fno-fast-math -fopenmp -fPIC -shared -o $@ $< -lm
 
-# Product math header compiled for the host (test shim).
-$(MATHCHECK_SO): tests/native/mathcheck.cpp compression_without_quantization_amd/csrc/cwq_math.h
+# Product math and screening-bound headers compiled for the host (test shim).
+$(MATHCHECK_SO): tests/native/mathcheck.cpp compression_without_quantization_amd/csrc/cwq_math.h \
+		compression_without_quantization_amd/csrc/cwq_screen.h
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -fno-fast-math -mfma -fPIC -shared -o $@ $<
 
 # rocRAND's Philox4x32-10 (SDK header) on the host: an independent pin (test shim).

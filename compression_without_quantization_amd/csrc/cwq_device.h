@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "cwq_math.h"
+#include "cwq_screen.h"
 
 namespace cwq {
 
@@ -15,6 +16,11 @@ static __constant__ double kLogTabConst[32] = CWQ_LOGF_TAB_INIT;
 __device__ __forceinline__ void fill_logtab(double* lds) {
   if (threadIdx.x < 32) lds[threadIdx.x] = kLogTabConst[threadIdx.x];
   __syncthreads();
+}
+
+// A target dim's log-density normaliser c = 0.5 log(2 pi) + log(scale) (cwq_math.h A.5)
+__device__ __forceinline__ float lognorm_of(float t_scale) {
+  return kHalfLog2Pi + logf_full(t_scale, kLogTabConst);
 }
 
 __device__ __forceinline__ uint32_t wave_id() {
@@ -174,9 +180,8 @@ __device__ __forceinline__ void box_muller_dev(uint32_t x0, uint32_t x1, const d
 // exhaustively on the GPU by tests/test_gpu.py.
 //
 // The radius is carried without its constant factor: q~ = sqrt(-log2 u1) =
-// r~ / sqrt(2 ln 2), and box_muller_screen returns z~ / sqrt(2 ln 2); callers
-// fold kSqrt2Ln2 into their per-dim constants (one multiply less per pair).
-constexpr double kSqrt2Ln2 = 1.1774100225154747;  // sqrt(2 ln 2)
+// r~ / sqrt(2 ln 2), and box_muller_screen returns z~ / sqrt(2 ln 2); the
+// per-dim constants fold kSqrt2Ln2 in (cwq_screen.h: one multiply less per pair).
 __device__ __forceinline__ float bm_qradius_screen(uint32_t x0) {
   const float u1 = fmaxf(uint32_to_float(x0), 1.0e-7f);
   return __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(u1));
@@ -195,17 +200,6 @@ __device__ __forceinline__ void box_muller_screen(uint32_t x0, uint32_t x1, floa
   f0 = s * q;
   f1 = c * q;
 }
-
-// Error constants of the screening Box-Muller, shared by both screening passes.
-// measured maxima over all 2^23 inputs (tools/screen_err.py, re-checked by
-// tests/test_gpu.py): |sqrt(2 ln 2) q~ - r| <= 5.82e-7, |sin~ - sin|, |cos~ - cos| <= 2.99e-7
-constexpr double kScreenEr = 1.0e-6;
-constexpr double kScreenEs = 6.0e-7;
-constexpr double kScreenRmax = 5.68;  // r <= sqrt(-2 ln 1e-7) = 5.6777
-// |sqrt(2 ln 2) RN(s~ q~) - RN(s r)| <= (1 + Es) Er + Rmax Es + 2^-23 (Rmax + Er)
-constexpr double kScreenEz =
-    (1.0 + kScreenEs) * kScreenEr + kScreenRmax * kScreenEs + 0x1p-23 * (kScreenRmax + kScreenEr);
-constexpr double kScreenZm = 5.7;     // bound on |z| and |z~|
 
 __device__ __forceinline__ F4 normal4_screen(const PhiloxStream& s, uint64_t grp) {
   const U4 x = philox_block_dev(s, grp);
@@ -258,9 +252,6 @@ __device__ __forceinline__ bool markstein_ok4(float a, float b, float c, float d
   const float hi = __builtin_fmaxf(__builtin_fmaxf(ma, mb), __builtin_fmaxf(mc, md));
   const float lo = __builtin_fminf(__builtin_fminf(ma, mb), __builtin_fminf(mc, md));
   return (hi <= 0x1p60f) & (lo >= 0x1p-60f);
-}
-__device__ __forceinline__ bool markstein_ok_den(float b) {
-  return b >= 0x1p-60f && b <= 0x1p60f;
 }
 
 struct BlockSpan {
@@ -361,18 +352,35 @@ __device__ __forceinline__ float row16_sum_f32(float v) {
   v = dpp_add_step<0x140>(v);  // row_mirror: half 0 <-> half 1
   return v;
 }
-// smallest float >= b (+inf for non-finite b: such a bound never drops anything)
-__device__ __forceinline__ float round_up_f32(double b) {
-  if (!(b == b) || b > 3.0e38 || b < -3.0e38) return __builtin_inff();
-  float f = (float)b;
-  if ((double)f < b) {
-    const uint32_t u = f2u(f);
-    f = (f >= 0.0f) ? u2f(f == 0.0f ? 1u : u + 1u) : u2f(u - 1u);
-  }
-  return f;
-}
-__device__ __forceinline__ float round_dn_f32(double b) { return -round_up_f32(-b); }
 
+// The span vote of k_small_screen and k_small_one.  A lane holds the screened
+// sums rs of its span's four rows ns .. ns + 3 (those below n1 exist).  tau is
+// raised from the lane's best row: the lower bound is monotone in the screened
+// value, and any row's lower bound is a valid threshold, so one wave max per
+// span replaces one per row.  Then one ballot per row: m[q] holds the lanes
+// whose row q exists and whose upper bound reaches tau.  Returns the number of
+// such rows in the wave.  Requires a full exec mask.
+__device__ __forceinline__ uint32_t span_vote(const float (&rs)[4], int64_t ns, int64_t n1,
+                                              float c1, float c2, float As, float Pq, float B,
+                                              float& tau, uint64_t (&m)[4]) {
+  float smax = -__builtin_inff();
+  bool any = false;
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq)
+    if (ns + qq < n1) {
+      smax = fmaxf(smax, rs[qq]);
+      any = true;
+    }
+  const float lower = any ? screen_row_lower(smax, c2, As, Pq) : -__builtin_inff();
+  tau = fmaxf(tau, wave_max_f32(lower));
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    m[qq] = __ballot(ns + qq < n1 && screen_row_upper(rs[qq], c1, B) >= tau);
+    cnt += (uint32_t)__builtin_popcountll(m[qq]);
+  }
+  return cnt;
+}
 template <int DC, class ElemF>
 __device__ __forceinline__ float eval_row_f(const PhiloxStream& st, uint64_t kbase, int64_t d_rt,
                                             int align_rt, const double* logtab, ElemF&& val) {
@@ -395,8 +403,7 @@ __device__ __forceinline__ float eval_row_f(const PhiloxStream& st, uint64_t kba
   }
   float t = 0.0f;
   for (int64_t j = vec; j < d; ++j) t = t + elem(j);
-  const float q0 = p[0] + p[4], q1 = p[1] + p[5], q2 = p[2] + p[6], q3 = p[3] + p[7];
-  return t + ((q0 + q2) + (q1 + q3));
+  return eigen_fold8(p, t);
 }
 
 static inline unsigned grid_for(int64_t work, int64_t per_block, unsigned cap) {

@@ -32,8 +32,8 @@ __global__ void __launch_bounds__(256) k_imp_prep(const float* __restrict__ t_sc
                                                   float* __restrict__ lnp) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    lnt[i] = kHalfLog2Pi + logf_full(t_scale[i], kLogTabConst);
-    lnp[i] = kHalfLog2Pi + logf_full(p_scale[i], kLogTabConst);
+    lnt[i] = lognorm_of(t_scale[i]);
+    lnp[i] = lognorm_of(p_scale[i]);
   }
 }
 
@@ -354,8 +354,8 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
     auto exact_row = [&](int64_t n) __attribute__((always_inline)) -> float {
       return eval_row_f<0>(st, (uint64_t)n * (uint64_t)d, d, (int)(((uint64_t)n * d) & 3u), logtab,
                            [&](int64_t e, float zz) -> float {
-                             float x = ps[e] * zz;  // misc.py:14
-                             x = pl[e] + x;         // misc.py:15
+                             const float sc = ps[e];
+                             const float x = shard_sample(pl[e], sc, zz);
                              const float lt = log_prob(x, tl[e], ts[e], ct[e]);
                              const float lq = log_prob(x, pl[e], ps[e], cp[e]);
                              return lt - lq;        // :60
@@ -539,8 +539,8 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
       for (int64_t n = n0 + 4 * (int64_t)lane + wv; n < n1; n += 256) {
         const float v = eval_row_f<0>(st, (uint64_t)n * (uint64_t)d, d, align, logtab,
                                       [&](int64_t e, float zz) -> float {
-                                        float x = ps[e] * zz;  // misc.py:14
-                                        x = pl[e] + x;         // misc.py:15
+                                        const float sc = ps[e];
+                                        const float x = shard_sample(pl[e], sc, zz);
                                         const float lt = log_prob(x, tl[e], ts[e], ct[e]);
                                         const float lq = log_prob(x, pl[e], ps[e], cp[e]);
                                         return lt - lq;        // :60
@@ -600,8 +600,8 @@ __global__ void __launch_bounds__(256) k_imp_small(
     for (int64_t n = lane; n < N; n += 64) {
       const float v = eval_row_f<0>(st, (uint64_t)n * (uint64_t)d, d, (int)(((uint64_t)n * d) & 3u),
                                     logtab, [&](int64_t e, float zz) -> float {
-                                      float x = ps[e] * zz;  // misc.py:14
-                                      x = pl[e] + x;         // misc.py:15
+                                      const float sc = ps[e];
+                                      const float x = shard_sample(pl[e], sc, zz);
                                       const float lt = log_prob(x, tl[e], ts[e], ct[e]);
                                       const float lq = log_prob(x, pl[e], ps[e], cp[e]);
                                       return lt - lq;        // :60
@@ -636,8 +636,7 @@ __global__ void __launch_bounds__(256) k_imp_rows(
     const int64_t d = block_off[g + 1] - off;
     int64_t idx;
     if (keys) {
-      const uint64_t key = keys[g];
-      idx = (key >> 32) > kArgmaxClampOrd ? (int64_t)argmax_key_index(key) : 0;
+      idx = (int64_t)key_index(keys[g]);
       if (lane == 0) index_out[g] = idx;
     } else {
       idx = index_in[g];
@@ -647,17 +646,12 @@ __global__ void __launch_bounds__(256) k_imp_rows(
       float v = __builtin_nanf("");
       if (idx >= 0) {
         const uint64_t k = (uint64_t)idx * (uint64_t)d + (uint64_t)j;
-        const F4 z = normal4_dev(st, k >> 2, logtab);
-        const uint32_t w = (uint32_t)(k & 3u);
-        const float zz = w == 0 ? z.a : (w == 1 ? z.b : (w == 2 ? z.c : z.d));
-        v = p_scale[off + j] * zz;
-        v = p_loc[off + j] + v;
+        const float zz = f4_word(normal4_dev(st, k >> 2, logtab), (uint32_t)(k & 3u));
+        const float sc = p_scale[off + j];
+        v = shard_sample(p_loc[off + j], sc, zz);
       }
       if (out_sample) out_sample[off + j] = v;
-      if (dst_out) {
-        const float m = dst_scale[off + j] * v;
-        dst_out[off + j] = m + dst_loc[off + j];
-      }
+      if (dst_out) dst_out[off + j] = destandardise_1(v, dst_loc[off + j], dst_scale[off + j]);
     }
   }
 }

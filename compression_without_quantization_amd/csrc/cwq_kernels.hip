@@ -40,11 +40,12 @@ __global__ void __launch_bounds__(256) k_prep_dims(
     keys[g] = 0ull;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    loc_s[i] = p_loc[i] / nst;                // p_loc / n_steps
-    float rs = rho * p_scale[i];              // rho * p_scale
-    scale_s[i] = rs / sdiv;                   //   / sqrt(n_steps)
-    lognorm[i] = kHalfLog2Pi + logf_full(t_scale[i], kLogTabConst);
-    out_sample[i] = 0.0f;                     // best_sample = tf.zeros (:68)
+    float ls, ss;
+    shard_consts(p_loc[i], p_scale[i], nst, sdiv, rho, ls, ss);
+    loc_s[i] = ls;
+    scale_s[i] = ss;
+    lognorm[i] = lognorm_of(t_scale[i]);
+    out_sample[i] = 0.0f;  // best_sample = tf.zeros (:68)
   }
 }
 
@@ -171,8 +172,7 @@ constexpr float kPruneC1 = 0x1p-14f;
 // best + (loc_s + scale_s z) - mu  (misc.py:14-15, coded_greedy_sampler.py:57, TFP _z numerator)
 template <bool STEP0>
 __device__ __forceinline__ float cand_diff(float z, float ls, float ss, float mu, float bb) {
-  float s = ss * z;  // misc.py:14
-  s = ls + s;        // misc.py:15
+  const float s = shard_sample(ls, ss, z);
   const float tv = STEP0 ? s : bb + s;
   return tv - mu;
 }
@@ -181,26 +181,13 @@ __device__ __forceinline__ float lp_from_z(float z, float cc) {
   return u - cc;
 }
 
-// Screening pass ("screening bound").  On tiles whose constants
-// pass the range gate below, the drop decisions are taken on cheap
-// approximations instead of exact values: z~ from the hardware
-// transcendentals (|z~ - z| <= kScreenEz for every Philox output), and per dim
-//     a_j = RN(sA_j z~ + sB_j),  sA_j ~ ss_j K_j,  sB_j ~ (best + loc_s - mu)_j K_j,
-// K_j = sqrt(phi (1 - 2^-24) / 2) / sigma_j, with the guarantee
-//     0.5 y_j^2 (1 - 2^-24)  >=  a_j^2 - C_j
-// for the exact standardised value y_j (C_j a tiny per-dim constant).  With s
-// the float sum of -a_j^2 over the visited dims, every completion of the row
-// has an exact Eigen-order value
+// Screening pass (cwq_screen.h, DESIGN.md "screening bound").  On tiles whose
+// constants pass the range gate, the drop decisions are taken on the screened
+// sum s of -a_j^2 over the visited dims: every completion of the row has an
+// exact Eigen-order value
 //     E  <=  (1 - 2^-14) s + Bs_k,    Bs_k ~ sum_j M_j + sum_{visited} C_j,
 // and a completed row has E >= (1 + 2^-13) s + As - Pq sqrt(-s), which
-// feeds tau.  Survivors are re-evaluated exactly as in the exact pass, so the
-// screening arithmetic never reaches the output.
-constexpr float kScreenC1 = 1.0f - 0x1p-14f;
-constexpr float kScreenC2 = 1.0f + 0x1p-13f;
-constexpr double kScreenEps = 0x1p-15;  // split of the additive error: (x-A)^2 >= (1-e)x^2 - (1/e-1)A^2
-constexpr double kScreenPhi = (1.0 - kScreenEps) * (1.0 - 0x1p-21);
-constexpr double kScreenKappa = 0.7070958018530696;  // sqrt(phi (1 - 2^-24) / 2), rounded down
-
+// feeds tau.  Survivors are re-evaluated exactly as in the exact pass.
 
 #ifdef CWQ_TILE_TIMES
 // timing builds only (tools/tile_times.py): per tile of k_encode_prune its
@@ -371,33 +358,14 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
 #pragma unroll
       for (int f = 0; f < NF; ++f) c[(k * NF + f) * 4 + w] = fj[f];
       den_ok = markstein_ok_den(sgj) ? 1 : 0;
-      // screening constants (see kScreen* above and DESIGN.md)
-      const double ssa = __builtin_fabs((double)fj[1]), lsa = __builtin_fabs((double)fj[0]);
-      const double mua = __builtin_fabs((double)fj[2]);
-      const double bba = STEP0 ? 0.0 : __builtin_fabs((double)fj[6]);
-      const double zs = kScreenZm * ssa;
-      const double mag = bba + lsa + zs + mua;
-      // rounding of the exact chain RN(RN(RN(bb +) RN(ls + RN(ss z))) - mu)
-      const double rho = 0x1p-24 * 1.0001 * (zs + (lsa + zs) + (STEP0 ? 0.0 : bba + lsa + zs) + mag);
-      const double offd = (STEP0 ? 0.0 : (double)fj[6]) + (double)fj[0] - (double)fj[2];
-      const double sig = (double)sgj;
-      const double kq = kScreenKappa / sig;
-      const float sa = (float)((double)fj[1] * kq * kSqrt2Ln2);  // z~ arrives / sqrt(2 ln 2)
-      const float sb = (float)(offd * kq);
+      // screening constants; the gate includes den_ok's test of sigma
+      const ScreenDim o = screen_dim<STEP0>(fj[0], fj[1], fj[2], sgj, fj[4], fj[6]);
       float* sc = reinterpret_cast<float*>(scst);
-      sc[(k * NS + 0) * 4 + w] = sa;
-      sc[(k * NS + 1) * 4 + w] = sb;
-      const double a0 = (kq * (rho + ssa * kScreenEz) +
-                         kq * 0x1p-24 * 1.0001 * (zs + __builtin_fabs(offd))) * (1.0 + 0x1p-20) +
-                        0x1p-140;
-      const float cdim = round_up_f32((1.0 / kScreenEps - 1.0) * a0 * a0 / kScreenPhi * (1.0 + 0x1p-20));
-      dA[j] = round_up_f32(a0 * 1.0001);
-      dC[j] = cdim;
-      const float cj = fj[4];
-      scr_ok = (den_ok && mag <= 0x1p100 && mag / sig <= 0x1p50 && cdim <= 0x1p60f &&
-                sa - sa == 0.0f && sb - sb == 0.0f && cj - cj == 0.0f)
-                   ? 1
-                   : 0;
+      sc[(k * NS + 0) * 4 + w] = o.sa;
+      sc[(k * NS + 1) * 4 + w] = o.sb;
+      dA[j] = o.A;
+      dC[j] = o.C;
+      scr_ok = o.ok ? 1 : 0;
     }
     const bool fastdiv = __syncthreads_and(den_ok) != 0;
     const bool scr_all = __syncthreads_and(scr_ok) != 0;
@@ -435,9 +403,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
                                 : round_up_f32(rf + 0x1p-14 * kk + marg);
         if (kb >= 1) meta[kb - 1].y = (int)f2u(bk);
         if (kb == G) lowc = round_up_f32(0x1p-14 * kk + marg);
-      } else if (screen) {
-        scr_a = round_dn_f32(msum - sl - 1.01 * a2 * (1.0 + 0x1p-11));
-        scr_pq = round_up_f32(2.01 * amax * __builtin_sqrt((double)D) * (1.0 + 0x1p-11));
+      } else if (screen) {  // As, Pq with this kernel's fixed 2^-14 slack
+        scr_a = screen_as(msum, sl, a2);
+        scr_pq = screen_pq(amax, D);
       }
       if (kb == 0) {
         uint32_t t0 = ord_f32(-__builtin_inff());
@@ -507,7 +475,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           s = __builtin_fmaf(-a1, a1, s);
           s = __builtin_fmaf(-a2, a2, s);
           s = __builtin_fmaf(-a3, a3, s);
-          upper = __builtin_fmaf(s, kScreenC1, u2f((uint32_t)mt.y));
+          upper = screen_row_upper(s, kScreenC1, u2f((uint32_t)mt.y));
         } else {
           box_muller_dev(x.x, x.y, logtab, z0, z1);
           box_muller_dev(x.z, x.w, logtab, z2, z3);
@@ -554,7 +522,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         if (complete && active && upper >= tau) {  // may be the best: keep it
           float lower;
           if constexpr (SCREEN)
-            lower = __builtin_fmaf(s, kScreenC2, sA) - sPq * __builtin_amdgcn_sqrtf(-s);  // ~1 ulp: inside Pq's 0.4% slack
+            lower = screen_row_lower(s, kScreenC2, sA, sPq);
           else
             lower = (s - __builtin_fabsf(s) * kPruneC1) - lc;
           tau = fmaxf(tau, lower);
@@ -659,39 +627,6 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
 //   * tiles of one block share their threshold through gtau[g].
 // Blocks whose constants fail the gate are scored exactly.
 // ---------------------------------------------------------------------------
-struct CsrDim {
-  float sa, sb;     // a = RN(sa z' + sb), z' = screening z / sqrt(2 ln 2)
-  float A, C;       // additive error (a units) and C_j of the bound
-  double M;         // M_j = -c_j
-  bool ok;
-};
-
-template <bool STEP0>
-__device__ __forceinline__ CsrDim csr_dim(float ls, float ss, float mu, float sg, float c,
-                                          float bb) {
-  CsrDim o;
-  const double ssa = __builtin_fabs((double)ss), lsa = __builtin_fabs((double)ls);
-  const double mua = __builtin_fabs((double)mu);
-  const double bba = STEP0 ? 0.0 : __builtin_fabs((double)bb);
-  const double zs = kScreenZm * ssa;
-  const double mag = bba + lsa + zs + mua;
-  const double rho = 0x1p-24 * 1.0001 * (zs + (lsa + zs) + (STEP0 ? 0.0 : bba + lsa + zs) + mag);
-  const double offd = (STEP0 ? 0.0 : (double)bb) + (double)ls - (double)mu;
-  const double sig = (double)sg;
-  const double kq = kScreenKappa / sig;
-  o.sa = (float)((double)ss * kq * kSqrt2Ln2);
-  o.sb = (float)(offd * kq);
-  const double a0 = (kq * (rho + ssa * kScreenEz) +
-                     kq * 0x1p-24 * 1.0001 * (zs + __builtin_fabs(offd))) * (1.0 + 0x1p-20) +
-                    0x1p-140;
-  o.A = round_up_f32(a0 * 1.0001);
-  o.C = round_up_f32((1.0 / kScreenEps - 1.0) * a0 * a0 / kScreenPhi * (1.0 + 0x1p-20));
-  o.M = -(double)c;
-  o.ok = markstein_ok_den(sg) && mag <= 0x1p100 && mag / sig <= 0x1p50 && o.C <= 0x1p60f &&
-         o.sa - o.sa == 0.0f && o.sb - o.sb == 0.0f && c - c == 0.0f;
-  return o;
-}
-
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
   red[threadIdx.x] = v;
   __syncthreads();
@@ -753,8 +688,7 @@ __global__ void __launch_bounds__(256) k_csr_prep(
   for (int64_t g = blockIdx.x; g < nb; g += gridDim.x) {
     const BlockSpan sp = block_span(block_off, ud, g);
     const int64_t off = sp.off, d = sp.d;
-    double sm = 0.0, sa = 0.0, sk = 0.0, s2 = 0.0, mx = 0.0;
-    int ok = 1;
+    ScreenSums u;  // this thread's dims (sum C is taken per visit position below)
     float2* sabg = sab + off + 8 * g + 4;  // 4 zero pads either side (partial units)
     float* cg = cdim + off;
     if (lead && tid < 8) {  // 8 trailing zeros: the last 4 are the next block's
@@ -762,29 +696,24 @@ __global__ void __launch_bounds__(256) k_csr_prep(
       sabg[d + tid] = float2{0.f, 0.f};               // past the last block)
     }
     for (int64_t j = tid; j < d; j += 256) {
-      const CsrDim o =
-          csr_dim<STEP0>(loc_s[off + j], scale_s[off + j], t_loc[off + j], t_scale[off + j],
-                         lognorm[off + j], STEP0 ? 0.0f : best[off + j]);
+      const ScreenDim o =
+          screen_dim<STEP0>(loc_s[off + j], scale_s[off + j], t_loc[off + j], t_scale[off + j],
+                            lognorm[off + j], STEP0 ? 0.0f : best[off + j]);
       sabg[j] = float2{o.sa, o.sb};
       cg[j] = o.C;
-      sm += o.M;
-      sa += __builtin_fabs(o.M);
-      sk += __builtin_fabs(o.M) + o.M;
-      s2 += (double)o.A * (double)o.A;
-      mx = (double)o.A > mx ? (double)o.A : mx;
-      ok &= o.ok ? 1 : 0;
+      u.add(o);
     }
-    sm = wave_sum_f64(sm);
-    sa = wave_sum_f64(sa);
-    sk = wave_sum_f64(sk);
-    s2 = wave_sum_f64(s2);
-    mx = wave_max_f64(mx);
+    u.sm = wave_sum_f64(u.sm);
+    u.sa = wave_sum_f64(u.sa);
+    u.sk = wave_sum_f64(u.sk);
+    u.s2 = wave_sum_f64(u.s2);
+    u.mx = wave_max_f64(u.mx);
     if (lane == 0) {
-      red[0][wv] = sm;
-      red[1][wv] = sa;
-      red[2][wv] = sk;
-      red[3][wv] = s2;
-      red[4][wv] = mx;
+      red[0][wv] = u.sm;
+      red[1][wv] = u.sa;
+      red[2][wv] = u.sk;
+      red[3][wv] = u.s2;
+      red[4][wv] = u.mx;
     }
     // the sab / cdim stores are read back below by other threads: wait for
     // them to complete (they write through to L2) and read them with
@@ -792,28 +721,19 @@ __global__ void __launch_bounds__(256) k_csr_prep(
     // workgroup on this CU filled earlier may hold this block's previous-step
     // values at its edges)
     __threadfence_block();
-    const bool all_ok = __syncthreads_and(ok) != 0;
-    const double SM = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    const double SA = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    const double SK = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
-    const double S2 = ((red[3][0] + red[3][1]) + red[3][2]) + red[3][3];
-    double MX = red[4][0];
-    for (int w = 1; w < 4; ++w) MX = red[4][w] > MX ? red[4][w] : MX;
-    // Float summation error of depth h: gamma_h = 1.01 (h + 1) 2^-24 bounds
-    // |fl(sum) - sum| / sum|x| for any summation tree in which every term
-    // passes through at most h roundings.  Two sums of d terms enter the
-    // bound: the screening sum s (sequential over the row: h = d; cooperative
-    // rows: 4 in-lane + 4 butterfly + one per 16-unit chunk, <= 16 + d/64) and
-    // the exact Eigen-order row value (8 strided accumulators, predux, tail:
-    // <= d/8 + 8).  gamma is taken at the larger depth.  The additive margin
-    // 2^-20 covers the float rounding of B_k and of the tests' fma (u |B_k|)
-    // and the double roundings of the sums here; u |s| is covered by the
-    // 2^-22 / 2^-14 terms of c1 / c2.
+    const bool all_ok = __syncthreads_and(u.ok) != 0;
+    ScreenSums S;  // the block's
+    S.sm = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    S.sa = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    S.sk = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
+    S.s2 = ((red[3][0] + red[3][1]) + red[3][2]) + red[3][3];
+    S.mx = red[4][0];
+    for (int w = 1; w < 4; ++w) S.mx = red[4][w] > S.mx ? red[4][w] : S.mx;
+    // depth of the screening sum: cooperative rows 16 + d/64, per-lane rows d
     const bool coop_blk = d >= coop_min_d;
-    const double h_s = coop_blk ? 16.0 + (double)d / 64.0 : (double)d;
-    const double h_e = (double)d / 8.0 + 8.0;
-    const double gam = 1.01 * ((h_s > h_e ? h_s : h_e) + 1.0) * 0x1p-24;
-    const double sl = (3.0 * gam + 0x1p-20) * (__builtin_fabs(SM) + SA + SK) + 0x1p-126;
+    const ScreenBlock bc =
+        screen_block_consts(S, d, coop_blk ? 16.0 + (double)d / 64.0 : (double)d);
+    const double SM = S.sm, sl = bc.sl;
     const int64_t reg = off + 12 * g, cs = csr_cls_stride(d);
     const bool recs = abp != nullptr && d > lds_dims;
     auto sab_at = [&](int64_t j) {
@@ -937,14 +857,9 @@ __global__ void __launch_bounds__(256) k_csr_prep(
         __syncthreads();
       }
     }
-    if (lead && tid == 0) {
-      const float c1 = round_dn_f32(1.0 - 3.0 * gam - 0x1p-22);
-      const float c2 = round_up_f32(1.0 + 3.0 * gam + 0x1p-14);
-      const float as = round_dn_f32(SM - sl - 1.01 * S2 * (1.0 + 0x1p-11));
-      const float pq = round_up_f32(2.01 * MX * __builtin_sqrt((double)(d > 0 ? d : 1)) *
-                                    (1.0 + 0x1p-11));
-      const bool fin = as - as == 0.0f && pq - pq == 0.0f;
-      grp[g] = (all_ok && fin && d > 0) ? float4{c1, c2, as, pq} : float4{0.f, 0.f, 0.f, 0.f};
+    if (lead && tid == 0) {  // the gate does not look at the full-row B (bpre holds the B_k)
+      grp[g] = (all_ok && bc.finite && d > 0) ? float4{bc.c1, bc.c2, bc.as, bc.pq}
+                                              : float4{0.f, 0.f, 0.f, 0.f};
       gtau[g * CWQ_CSR_GTAU_STRIDE] = ord_f32(-__builtin_inff());
     }
     __syncthreads();
@@ -1000,9 +915,7 @@ __device__ __forceinline__ float exact_row_wave(
   float p[8];
 #pragma unroll
   for (int l = 0; l < 8; ++l) p[l] = __shfl(acc, l, 64);
-  const float t = __shfl(acc, 8, 64);
-  const float q0 = p[0] + p[4], q1 = p[1] + p[5], q2 = p[2] + p[6], q3 = p[3] + p[7];
-  return t + ((q0 + q2) + (q1 + q3));
+  return eigen_fold8(p, __shfl(acc, 8, 64));
 }
 
 #ifndef CWQ_CSR_GTAU_SHARE
@@ -1265,11 +1178,10 @@ __global__ void __launch_bounds__(256, COOP ? CWQ_CSR_COOP_MIN_WAVES : CWQ_CSR_R
           }
           k = kn;
           const bool complete = k == U;
-          const float upper = __builtin_fmaf(s, gc.x, bnext);
+          const float upper = screen_row_upper(s, gc.x, bnext);
           const bool prune = !complete && (upper < tau);
           if (complete && active && upper >= tau) {  // may be the best: keep it
-            const float lower =
-                __builtin_fmaf(s, gc.y, gc.z) - gc.w * __builtin_amdgcn_sqrtf(-s);
+            const float lower = screen_row_lower(s, gc.y, gc.z, gc.w);
             tau = fmaxf(tau, lower);
             const uint32_t slot = atomicAdd(&sq_cnt, 1u);
             if (slot < CWQ_CSR_SURVIVOR_CAP) {  // else: overflow, the tile is redone
@@ -1447,11 +1359,10 @@ __global__ void __launch_bounds__(256, COOP ? CWQ_CSR_COOP_MIN_WAVES : CWQ_CSR_R
           s = s + row16_sum_f32(part);
           k = kn;
           const bool complete = k == U;
-          const float upper = __builtin_fmaf(s, gc.x, bnext);
+          const float upper = screen_row_upper(s, gc.x, bnext);
           const bool prune = !complete && (upper < tau);
           if (complete && active && upper >= tau) {  // may be the best: keep it
-            const float lower =
-                __builtin_fmaf(s, gc.y, gc.z) - gc.w * __builtin_amdgcn_sqrtf(-s);
+            const float lower = screen_row_lower(s, gc.y, gc.z, gc.w);
             tau = fmaxf(tau, lower);
             if (t == 0u) {
               const uint32_t sl = atomicAdd(&sq_cnt, 1u);
@@ -1651,38 +1562,19 @@ __global__ void __launch_bounds__(256) k_small_prep(
     uint32_t* __restrict__ gtau, uint32_t* __restrict__ scnt) {
   const uint32_t lane = threadIdx.x & 63u;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
-  struct Sums {
-    double sm = 0.0, sa = 0.0, sk = 0.0, s2 = 0.0, cs = 0.0, mx = 0.0;
-    int ok = 1;
-  };
-  auto dim = [&](Sums& u, int64_t off, int64_t g, int64_t j) {
-    const CsrDim o = csr_dim<STEP0>(loc_s[off + j], scale_s[off + j], t_loc[off + j],
-                                    t_scale[off + j], lognorm[off + j],
-                                    STEP0 ? 0.0f : best[off + j]);
+  auto dim = [&](ScreenSums& u, int64_t off, int64_t g, int64_t j) {
+    const ScreenDim o = screen_dim<STEP0>(loc_s[off + j], scale_s[off + j], t_loc[off + j],
+                                          t_scale[off + j], lognorm[off + j],
+                                          STEP0 ? 0.0f : best[off + j]);
     sab[off + 8 * g + 4 + j] = float2{o.sa, o.sb};  // k_csr_prep's padded layout
-    u.sm += o.M;
-    u.sa += __builtin_fabs(o.M);
-    u.sk += __builtin_fabs(o.M) + o.M;
-    u.s2 += (double)o.A * (double)o.A;
-    u.cs += (double)o.C;
-    u.mx = (double)o.A > u.mx ? (double)o.A : u.mx;
-    u.ok &= o.ok ? 1 : 0;
+    u.add(o);
   };
-  // as k_csr_prep: gamma at the larger depth of the two float sums, the
-  // screening sum (sequential over the row here: h = d) and the exact
-  // Eigen-order row value (h <= d/8 + 8)
-  auto finish = [&](const Sums& u, int64_t off, int64_t g, int64_t d) {
-    const double h_s = (double)d, h_e = (double)d / 8.0 + 8.0;
-    const double gam = 1.01 * ((h_s > h_e ? h_s : h_e) + 1.0) * 0x1p-24;
-    const double sl = (3.0 * gam + 0x1p-20) * (__builtin_fabs(u.sm) + u.sa + u.sk) + 0x1p-126;
-    const float bf = round_up_f32(u.sm + u.cs * (1.0 + 0x1p-20) + sl);
-    const float c1 = round_dn_f32(1.0 - 3.0 * gam - 0x1p-22);
-    const float c2 = round_up_f32(1.0 + 3.0 * gam + 0x1p-14);
-    const float as = round_dn_f32(u.sm - sl - 1.01 * u.s2 * (1.0 + 0x1p-11));
-    const float pq = round_up_f32(2.01 * u.mx * __builtin_sqrt((double)(d > 0 ? d : 1)) *
-                                  (1.0 + 0x1p-11));
-    const bool fin = as - as == 0.0f && pq - pq == 0.0f && bf - bf == 0.0f;
-    const float4 gc = (u.ok && fin && d > 0) ? float4{c1, c2, as, pq} : float4{0.f, 0.f, 0.f, 0.f};
+  auto finish = [&](const ScreenSums& u, int64_t off, int64_t g, int64_t d) {
+    const ScreenBlock bc = screen_block_consts(u, d, (double)d);  // rows summed sequentially
+    const float bf = bc.bf;
+    const bool fin = bc.finite && bf - bf == 0.0f;
+    const float4 gc = (u.ok && fin && d > 0) ? float4{bc.c1, bc.c2, bc.as, bc.pq}
+                                             : float4{0.f, 0.f, 0.f, 0.f};
     grp[g] = gc;
     // the block's header (kSmallHdr), indexed by g alone: the screen reads it
     // with one load level and prefetches the next tile's
@@ -1700,7 +1592,7 @@ __global__ void __launch_bounds__(256) k_small_prep(
     if (g < nb) {
       const BlockSpan sp = block_span(block_off, ud, g);
       if (sp.d <= kSmallLaneD) {
-        Sums u;
+        ScreenSums u;
         for (int64_t j = 0; j < sp.d; ++j) dim(u, sp.off, g, j);
         finish(u, sp.off, g, sp.d);
       } else {
@@ -1710,7 +1602,7 @@ __global__ void __launch_bounds__(256) k_small_prep(
     for (uint64_t m = __ballot(longb); m != 0ull; m &= m - 1ull) {  // the long blocks, a wave each
       const int64_t gl = gb + (int64_t)__builtin_ctzll(m);
       const BlockSpan sp = block_span(block_off, ud, gl);
-      Sums u;
+      ScreenSums u;
       for (int64_t j = lane; j < sp.d; j += 64) dim(u, sp.off, gl, j);
       const bool all_ok = __ballot(u.ok == 0) == 0ull;
       u.sm = wave_sum_f64(u.sm);
@@ -1771,28 +1663,8 @@ __global__ void __launch_bounds__(256, CWQ_SMALL_SCREEN_WAVES) k_small_screen(
     const PhiloxLo K = philox_lo_key(st);
     // tau, survivor slots of one span's four rows (rs: their screened values)
     auto span_tail = [&](int64_t ns, const float (&rs)[4]) __attribute__((always_inline)) {
-      // tau from the lane's best valid row: the lower bound is monotone in
-      // the screened value, and any row's lower bound is a valid threshold,
-      // so one wave max per span replaces one per row
-      float smax = -__builtin_inff();
-      bool any = false;
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq)
-        if (ns + qq < n1) {
-          smax = fmaxf(smax, rs[qq]);
-          any = true;
-        }
-      const float lower = any ? __builtin_fmaf(smax, gc.y, gc.z) -
-                                    gc.w * __builtin_amdgcn_sqrtf(-smax)
-                              : -__builtin_inff();
-      tau = fmaxf(tau, wave_max_f32(lower));
       uint64_t m[4];
-      uint32_t cnt = 0;
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        m[qq] = __ballot(ns + qq < n1 && __builtin_fmaf(rs[qq], gc.x, bf) >= tau);
-        cnt += (uint32_t)__builtin_popcountll(m[qq]);
-      }
+      const uint32_t cnt = span_vote(rs, ns, n1, gc.x, gc.y, gc.z, gc.w, bf, tau, m);
       if (cnt) {
         // the block's slots: this wave's scalar count, or a global counter
         // shared with the block's other tiles
@@ -1813,7 +1685,7 @@ __global__ void __launch_bounds__(256, CWQ_SMALL_SCREEN_WAVES) k_small_screen(
                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
             if (slot < CWQ_SLIST_PER_BLOCK)
               slist[CWQ_SLIST_PER_BLOCK * g + slot] =
-                  uint2{(uint32_t)(ns + qq), f2u(__builtin_fmaf(rs[qq], gc.x, bf))};
+                  uint2{(uint32_t)(ns + qq), f2u(screen_row_upper(rs[qq], gc.x, bf))};
           }
           pre += (uint32_t)__builtin_popcountll(mq);
         }
@@ -1822,12 +1694,6 @@ __global__ void __launch_bounds__(256, CWQ_SMALL_SCREEN_WAVES) k_small_screen(
                              __HIP_MEMORY_SCOPE_AGENT);
       }
     };
-    // lane span m: rows n0 + 4 (lane + 64 m) + q, q = 0..3.  n0 is a multiple
-    // of 4 (tiles are multiples of 256 candidates), so a span's 4d words are
-    // exactly Philox blocks [n d / 4, n d / 4 + d): every block is computed
-    // once (a row alone would start and end inside blocks its neighbours also
-    // compute), and the dim index of each word is the same in every lane, so
-    // the per-dim constants are wave-uniform loads.
     auto spans = [&](auto lo_tag) __attribute__((always_inline)) {
       constexpr bool LO = decltype(lo_tag)::value;  // every Philox block index < 2^32
       for (int64_t m0 = 0; n0 + 256 * m0 < n1; ++m0) {
@@ -2165,10 +2031,9 @@ __global__ void __launch_bounds__(CWQ_PREP1_THREADS) k_small_prep1(
     }
     float ls, ss, c;
     const float sg = t_scale[i];
-    if (FIRST) {  // k_prep_dims' arithmetic, bit for bit
-      ls = p_loc[i] / nst;
-      ss = (rho * p_scale[i]) / sdiv;
-      c = kHalfLog2Pi + logf_full(sg, kLogTabConst);
+    if (FIRST) {  // as k_prep_dims
+      shard_consts(p_loc[i], p_scale[i], nst, sdiv, rho, ls, ss);
+      c = lognorm_of(sg);
       loc_s[i] = ls;
       scale_s[i] = ss;
       lognorm[i] = c;
@@ -2177,7 +2042,7 @@ __global__ void __launch_bounds__(CWQ_PREP1_THREADS) k_small_prep1(
       ss = scale_s[i];
       c = lognorm[i];
     }
-    const CsrDim o = csr_dim<FIRST>(ls, ss, t_loc[i], sg, c, FIRST ? 0.0f : best[i]);
+    const ScreenDim o = screen_dim<FIRST>(ls, ss, t_loc[i], sg, c, FIRST ? 0.0f : best[i]);
     pre_ab[i] = float2{o.sa, o.sb};
     atomicAdd(&acc[0][lo], o.M);
     atomicAdd(&acc[1][lo], __builtin_fabs(o.M));
@@ -2193,20 +2058,17 @@ __global__ void __launch_bounds__(CWQ_PREP1_THREADS) k_small_prep1(
   const int64_t g = g0 + t;
   const int64_t off = boff[t];
   const int d = (int)(boff[t + 1] - off);
-  const double sm = acc[0][t], sa = acc[1][t], sk = acc[2][t], s2 = acc[3][t], cs = acc[4][t];
-  const double mx = (double)u2f(amx[t]);
-  // the screening bound's block constants (round 4's k_small_fused, term for term)
-  const double h_s = (double)d, h_e = (double)d / 8.0 + 8.0;
-  const double gam = 1.01 * ((h_s > h_e ? h_s : h_e) + 1.0) * 0x1p-24;
-  const double sl = (3.0 * gam + 0x1p-20) * (__builtin_fabs(sm) + sa + sk) + 0x1p-126;
-  const float bf = round_up_f32(sm + cs * (1.0 + 0x1p-20) + sl);
-  const float c1 = round_dn_f32(1.0 - 3.0 * gam - 0x1p-22);
-  const float c2 = round_up_f32(1.0 + 3.0 * gam + 0x1p-14);
-  const float as = round_dn_f32(sm - sl - 1.01 * s2 * (1.0 + 0x1p-11));
-  const float pq = round_up_f32(2.01 * mx * __builtin_sqrt((double)(d > 0 ? d : 1)) *
-                                (1.0 + 0x1p-11));
-  const bool screen = abad[t] == 0u && d > 0 && d <= CWQ_FUSED_DMAX && as - as == 0.0f &&
-                      pq - pq == 0.0f && bf - bf == 0.0f && mx - mx == 0.0;
+  ScreenSums u;
+  u.sm = acc[0][t];
+  u.sa = acc[1][t];
+  u.sk = acc[2][t];
+  u.s2 = acc[3][t];
+  u.cs = acc[4][t];
+  u.mx = (double)u2f(amx[t]);
+  const ScreenBlock bc = screen_block_consts(u, d, (double)d);  // rows summed sequentially
+  const float bf = bc.bf, c1 = bc.c1, c2 = bc.c2, as = bc.as, pq = bc.pq;
+  const bool screen = abad[t] == 0u && d > 0 && d <= CWQ_FUSED_DMAX && bc.finite &&
+                      bf - bf == 0.0f && u.mx - u.mx == 0.0;
   const PhiloxStream st = generate_key(step_seed(sd.of(g), step), 42);
   SmallRec r;
   r.q0 = uint4{(uint32_t)off, (uint32_t)((uint64_t)off >> 32), (uint32_t)d,
@@ -2241,8 +2103,8 @@ CWQ_RARE unsigned long long small_listed_exact(
       const uint32_t j = it - (e - e0) * du;
       const int64_t ei = off + j;
       const float zz = exact_normal(sb, (uint64_t)ln[e] * (uint64_t)du + j, logtab);
-      float sv = scale_s[ei] * zz;  // misc.py:14
-      sv = loc_s[ei] + sv;          // misc.py:15
+      const float sc = scale_s[ei];
+      const float sv = shard_sample(loc_s[ei], sc, zz);
       const float tv = STEP0 ? sv : best[ei] + sv;  // :57
       lpv[it] = log_prob(tv, t_loc[ei], t_scale[ei], lognorm[ei]);
     }
@@ -2258,8 +2120,7 @@ CWQ_RARE unsigned long long small_listed_exact(
       }
       float sum = 0.0f;
       for (int jj = vec; jj < db; ++jj) sum = sum + x[jj];
-      const float r0 = p[0] + p[4], r1 = p[1] + p[5], r2 = p[2] + p[6], r3 = p[3] + p[7];
-      const uint64_t k = argmax_key(sum + ((r0 + r2) + (r1 + r3)), ln[e]);
+      const uint64_t k = argmax_key(eigen_fold8(p, sum), ln[e]);
       bestk = k > bestk ? k : bestk;
     }
     wave_lds_sync();
@@ -2359,26 +2220,8 @@ __global__ void __launch_bounds__(64, CWQ_FUSED_WAVES) k_small_one(
             }
           }
         }
-        // tau from the lane's best valid row (the lower bound is monotone in s)
-        float smax = -__builtin_inff();
-        bool any = false;
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq)
-          if (ns + qq < n_cand) {
-            smax = fmaxf(smax, rs[qq]);
-            any = true;
-          }
-        const float lower = any ? __builtin_fmaf(smax, c2b, asb) -
-                                      pqb * __builtin_amdgcn_sqrtf(-smax)
-                                : -__builtin_inff();
-        tau = fmaxf(tau, wave_max_f32(lower));
         uint64_t m[4];
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          m[qq] = __ballot(ns + qq < n_cand && __builtin_fmaf(rs[qq], c1b, bfb) >= tau);
-          cnt += (uint32_t)__builtin_popcountll(m[qq]);
-        }
+        const uint32_t cnt = span_vote(rs, ns, n_cand, c1b, c2b, asb, pqb, bfb, tau, m);
         if (cnt == 0) continue;
         if (used + cnt > CWQ_FUSED_LIST) {  // drop the rows the raised tau excludes
           const bool have = lane < used;
@@ -2404,7 +2247,7 @@ __global__ void __launch_bounds__(64, CWQ_FUSED_WAVES) k_small_one(
           if ((mq >> lane) & 1ull) {
             const uint32_t slot_i = at + lane_rank(mq);
             ln[slot_i] = (uint32_t)(ns + qq);
-            lu[slot_i] = __builtin_fmaf(rs[qq], c1b, bfb);
+            lu[slot_i] = screen_row_upper(rs[qq], c1b, bfb);
           }
           at += (uint32_t)__builtin_popcountll(mq);
         }
@@ -2460,10 +2303,7 @@ __global__ void __launch_bounds__(64, CWQ_FUSED_WAVES) k_small_one(
       if (lane == 0) kmax = bk;
       wave_lds_sync();
     }
-    if (state != kQuadKnown) {  // ArgMaxTupleReducer: a key at the clamp level is index 0
-      const unsigned long long kb = kmax;
-      idx = (kb >> 32) > kArgmaxClampOrd ? argmax_key_index(kb) : 0u;
-    }
+    if (state != kQuadKnown) idx = key_index(kmax);
     if (lane == 0) out_idx[g * n_steps + step] = (int32_t)idx;
 #ifdef CWQ_QUAD_TIMES
     if (lane == 0u && g < kQuadTimes)
@@ -2495,14 +2335,11 @@ __global__ void __launch_bounds__(256) k_small_finalize(
     const PhiloxStream st{q1.x, q1.y, q1.z, q1.w};
     const uint32_t idx = (uint32_t)out_idx[(int64_t)g * n_steps + step];  // k_small_one's
     const float zz = exact_normal(st, (uint64_t)idx * (uint64_t)d + j, logtab);
-    float sv = scale_s[i] * zz;  // misc.py:14
-    sv = loc_s[i] + sv;          // misc.py:15
+    const float sc = scale_s[i];
+    const float sv = shard_sample(loc_s[i], sc, zz);
     const float b = (STEP0 ? 0.0f : best[i]) + sv;
     best[i] = b;
-    if (ds_out) {  // :292 destandardise (k_destandardise's arithmetic)
-      const float m = ds_scale[i] * b;
-      ds_out[i] = m + ds_loc[i];
-    }
+    if (ds_out) ds_out[i] = destandardise_1(b, ds_loc[i], ds_scale[i]);  // :292
   }
 }
 
@@ -2524,12 +2361,6 @@ __device__ __forceinline__ int64_t block_of_dim(const int64_t* __restrict__ off,
     if (off[m] <= i) lo = m; else hi = m;
   }
   return lo;
-}
-
-__device__ __forceinline__ uint32_t key_index(uint64_t key) {
-  // ArgMaxTupleReducer starts at (index 0, lowest()) and only a value strictly
-  // above lowest() replaces it: a winning key at the clamp level means index 0
-  return (key >> 32) > kArgmaxClampOrd ? argmax_key_index(key) : 0u;
 }
 
 __global__ void __launch_bounds__(256) k_encode_finalize(
@@ -2555,11 +2386,9 @@ __global__ void __launch_bounds__(256) k_encode_finalize(
     const PhiloxStream st =
         generate_key(step_seed(sd.of(g), step), 42);
     const uint64_t k = (uint64_t)idx * (uint64_t)d + (uint64_t)(i - off);
-    const F4 z = normal4_dev(st, k >> 2, logtab);
-    const uint32_t w = (uint32_t)(k & 3u);
-    const float zz = w == 0 ? z.a : (w == 1 ? z.b : (w == 2 ? z.c : z.d));
-    float sv = scale_s[i] * zz;
-    sv = loc_s[i] + sv;
+    const float zz = f4_word(normal4_dev(st, k >> 2, logtab), (uint32_t)(k & 3u));
+    const float sc = scale_s[i];
+    const float sv = shard_sample(loc_s[i], sc, zz);
     out_sample[i] = out_sample[i] + sv;
   }
 }
@@ -2593,19 +2422,17 @@ __global__ void __launch_bounds__(256) k_encode_finalize_q4(
     const int64_t g = c * bpw + L.lb;
     if (!L.active || g >= nb) continue;
     const int64_t t = g * qpb + L.q;
-    const uint64_t key = keys[g];
-    const uint32_t idx = (key >> 32) > kArgmaxClampOrd ? argmax_key_index(key) : 0u;
+    const uint32_t idx = key_index(keys[g]);
     if (L.q == 0) out_idx[g * n_steps + step] = (int32_t)idx;
     const PhiloxStream st =
         generate_key(step_seed(sd.of(g), step), 42);
     const F4 z = normal4_dev(st, (uint64_t)idx * qpb + L.q, logtab);
     const float4 l = loc_s[t], sc = scale_s[t];
     float4 b = out_sample[t];
-    float s;
-    s = sc.x * z.a; s = l.x + s; b.x = b.x + s;
-    s = sc.y * z.b; s = l.y + s; b.y = b.y + s;
-    s = sc.z * z.c; s = l.z + s; b.z = b.z + s;
-    s = sc.w * z.d; s = l.w + s; b.w = b.w + s;
+    b.x = b.x + shard_sample(l.x, sc.x, z.a);
+    b.y = b.y + shard_sample(l.y, sc.y, z.b);
+    b.z = b.z + shard_sample(l.z, sc.z, z.c);
+    b.w = b.w + shard_sample(l.w, sc.w, z.d);
     out_sample[t] = b;
   }
 }
@@ -2630,9 +2457,8 @@ __global__ void __launch_bounds__(256) k_decode(
     const int64_t off = block_off ? block_off[g] : g * ud;
     const int64_t d = block_off ? block_off[g + 1] - off : ud;
     const int32_t sg = block_seed(seed, block_id_base + g);
-    const float ls = p_loc[i] / nst;
-    const float rs = rho * p_scale[i];
-    const float ss = rs / sdiv;
+    float ls, ss;
+    shard_consts(p_loc[i], p_scale[i], nst, sdiv, rho, ls, ss);
     float v = 0.0f;  // sample = tf.zeros (:143)
     for (int s = 0; s < n_steps; ++s) {
       const int64_t n = idx[g * n_steps + s];
@@ -2645,9 +2471,7 @@ __global__ void __launch_bounds__(256) k_decode(
       const F4 z = normal4_dev(st, k >> 2, logtab);
       const uint32_t w = (uint32_t)(k & 3u);
       const float zz = w == 0 ? z.a : (w == 1 ? z.b : (w == 2 ? z.c : z.d));
-      float sv = ss * zz;
-      sv = ls + sv;
-      v = v + sv;  // :153 tile(sample) + samples, row indices[i]
+      v = v + shard_sample(ls, ss, zz);  // :153 tile(sample) + samples, row indices[i]
     }
     out_sample[i] = v;
   }
@@ -2759,9 +2583,7 @@ __global__ void __launch_bounds__(256, CWQ_DECODE_MIN_WAVES) k_decode_q4(
         const float zz[4] = {z.a, z.b, z.c, z.d};
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
-          float sv = ss[w] * zz[w];
-          sv = ls[w] + sv;
-          v[w] = v[w] + sv;  // :153 tile(sample) + samples, row indices[i]
+          v[w] = v[w] + shard_sample(ls[w], ss[w], zz[w]);  // :153 sample + row indices[i]
         }
       }
 #if CWQ_DECODE_NT
@@ -2878,9 +2700,7 @@ __global__ void __launch_bounds__(256, CWQ_GLDS_MIN_WAVES) k_decode_q4_glds(
           const float ss[4] = {rho * cs.x, rho * cs.y, rho * cs.z, rho * cs.w};
 #pragma unroll
           for (int w = 0; w < 4; ++w) {
-            float sv = ss[w] * zz[w];
-            sv = ls[w] + sv;
-            v[w] = 0.0f + sv;  // :153 tile(sample) + samples, from tf.zeros (:143)
+            v[w] = 0.0f + shard_sample(ls[w], ss[w], zz[w]);  // :153, from tf.zeros (:143)
           }
         }
         typedef float nt4 __attribute__((ext_vector_type(4)));
@@ -2913,8 +2733,8 @@ __global__ void __launch_bounds__(256) k_stateless_normal_sample(
       if (f < total) {
         const int64_t j = f % d;
         const float r = zz[w] * 1.0f + 0.0f;  // rnd * stddev + mean
-        const float s = scale[j] * r;
-        out[f] = loc[j] + s;
+        const float sc = scale[j];
+        out[f] = shard_sample(loc[j], sc, r);
       }
     }
   }
@@ -2929,9 +2749,7 @@ __global__ void __launch_bounds__(256) k_standardise(
     float* __restrict__ t_loc, float* __restrict__ t_scale) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const float dl = q_loc[i] - p_loc[i];
-    t_loc[i] = dl / p_scale[i];
-    t_scale[i] = q_scale[i] / p_scale[i];
+    standardise_1(q_loc[i], q_scale[i], p_loc[i], p_scale[i], t_loc[i], t_scale[i]);
   }
 }
 
@@ -2969,9 +2787,7 @@ __global__ void __launch_bounds__(256) k_grouped_prep(
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float ql = q_loc[i], qs = q_scale[i], pl = p_loc[i], ps = p_scale[i];
-    const float dl = ql - pl;
-    t_loc[i] = dl / ps;
-    t_scale[i] = qs / ps;
+    standardise_1(ql, qs, pl, ps, t_loc[i], t_scale[i]);
     kl[i] = kl_normal_normal_1(ql, qs, pl, ps);
     zeros[i] = 0.0f;
     ones[i] = 1.0f;
@@ -3002,9 +2818,8 @@ __global__ void __launch_bounds__(256) k_imp_grouped_prep(
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float ql = q_loc[i], qs = q_scale[i], pl = p_loc[i], ps = p_scale[i];
-    const float dl = ql - pl;
-    float tl = dl / ps;
-    float ts = qs / ps;
+    float tl, ts;
+    standardise_1(ql, qs, pl, ps, tl, ts);
     const float kl = kl_normal_normal_1(ql, qs, pl, ps);
     const float bits = kl / 0.6931472f;
     const bool k = bits <= limit;
@@ -3023,11 +2838,8 @@ __global__ void __launch_bounds__(256) k_imp_grouped_prep(
         sd = seed1[lo];
       }
       const F4 z = normal4_dev(generate_key(sd, 42), (uint64_t)j >> 2, logtab);
-      const uint32_t w = (uint32_t)j & 3u;
-      const float zz = w == 0 ? z.a : (w == 1 ? z.b : (w == 2 ? z.c : z.d));
-      const float r = zz * 1.0f + 0.0f;  // rnd * stddev + mean
-      const float sm = qs * r;           // misc.py:14
-      tsamp[i] = ql + sm;                // misc.py:15
+      const float r = f4_word(z, (uint32_t)j & 3u) * 1.0f + 0.0f;  // rnd * stddev + mean
+      tsamp[i] = shard_sample(ql, qs, r);
     }
     t_loc[i] = tl;
     t_scale[i] = ts;
@@ -3044,8 +2856,7 @@ __global__ void __launch_bounds__(256) k_destandardise(const float* sample,
                                                        int64_t n, float* out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const float m = p_scale[i] * sample[i];
-    out[i] = m + p_loc[i];
+    out[i] = destandardise_1(sample[i], p_loc[i], p_scale[i]);
   }
 }
 

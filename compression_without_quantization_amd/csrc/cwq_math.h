@@ -259,6 +259,41 @@ CWQ_HD F4 normal4(const PhiloxStream& s, uint64_t grp, const double* logtab) {
   box_muller(x.z, x.w, logtab, z.c, z.d);
   return z;
 }
+// word w (0..3) of a Philox block's four normals
+CWQ_HD float f4_word(const F4& z, uint32_t w) {
+  return w == 0 ? z.a : (w == 1 ? z.b : (w == 2 ? z.c : z.d));
+}
+
+// ---------------------------------------------------------------------------
+// The proposal shard of a step and a draw from it.
+// ---------------------------------------------------------------------------
+// coded_greedy_sampler.py:42-48: ls = p_loc / n_steps, ss = rho p_scale / sqrt(n_steps)
+CWQ_HD void shard_consts(float p_loc, float p_scale, float nst, float sdiv, float rho, float& ls,
+                         float& ss) {
+  ls = p_loc / nst;
+  const float rs = rho * p_scale;
+  ss = rs / sdiv;
+}
+// misc.py:14-15: loc + scale * z, two roundings.  Callers that pass loads read the scale
+// into a local first: the load order the kernels had before this helper (their register
+// allocation follows it).
+CWQ_HD float shard_sample(float ls, float ss, float z) {
+  const float s = ss * z;  // misc.py:14
+  return ls + s;           // misc.py:15
+}
+
+// Grouped wrappers (coded_greedy_sampler.py:193-201, :292): the target in the
+// prior's standard coordinates, and a standard-coordinate sample back
+CWQ_HD void standardise_1(float q_loc, float q_scale, float p_loc, float p_scale, float& t_loc,
+                          float& t_scale) {
+  const float dl = q_loc - p_loc;
+  t_loc = dl / p_scale;
+  t_scale = q_scale / p_scale;
+}
+CWQ_HD float destandardise_1(float sample, float p_loc, float p_scale) {
+  const float m = p_scale * sample;
+  return m + p_loc;
+}
 
 // ---------------------------------------------------------------------------
 // A.5 TFP Normal.log_prob with a precomputed normaliser c = 0.9189385f + log(s)
@@ -269,6 +304,13 @@ CWQ_HD float log_prob(float x, float loc, float scale, float c) {
   float z = (x - loc) / scale;
   float u = -0.5f * (z * z);
   return u - c;
+}
+
+// A.6 the Eigen 3.3 AVX inner-dim reduction's last step: the eight strided
+// accumulators p and the scalar tail of the d % 8 trailing dims
+CWQ_HD float eigen_fold8(const float (&p)[8], float tail) {
+  const float q0 = p[0] + p[4], q1 = p[1] + p[5], q2 = p[2] + p[6], q3 = p[3] + p[7];
+  return tail + ((q0 + q2) + (q1 + q3));
 }
 
 // Orderable argmax key: max key <=> max value, lowest index on ties.
@@ -286,6 +328,12 @@ CWQ_HD uint64_t argmax_key(float v, uint32_t idx) {
 constexpr uint32_t kArgmaxClampOrd = 0x00800000u;
 CWQ_HD uint32_t argmax_key_index(uint64_t key) {
   return 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+}
+// The winning index of a reduced key.  ArgMaxTupleReducer starts at (index 0,
+// lowest()) and only a value strictly above lowest() replaces it: a winning
+// key at the clamp level means index 0.
+CWQ_HD uint32_t key_index(uint64_t key) {
+  return (key >> 32) > kArgmaxClampOrd ? argmax_key_index(key) : 0u;
 }
 
 }  // namespace cwq

@@ -1,8 +1,12 @@
-// Host build of the product's device-math restatement (csrc/cwq_math.h), used
-// by tests/test_math_exhaustive.py to compare it with the host glibc over the
-// full Box-Muller input domains.  Test-only shim; not part of the product.
+// Host build of the product's device-math restatement (csrc/cwq_math.h) and of
+// the screening bound (csrc/cwq_screen.h).  tests/test_math_exhaustive.py
+// compares the former with the host glibc over the full Box-Muller input
+// domains; tests/test_screen_bound.py checks the latter's inequalities.
+// Test-only shim; not part of the product.
 #include <stdint.h>
+#include <vector>
 #include "../../compression_without_quantization_amd/csrc/cwq_math.h"
+#include "../../compression_without_quantization_amd/csrc/cwq_screen.h"
 
 static const double kTab[32] = CWQ_LOGF_TAB_INIT;
 
@@ -25,5 +29,74 @@ void mc_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
 }
 void mc_philox_many(const uint32_t* ctr, const uint32_t* key, int64_t n, uint32_t* out) {
   for (int64_t i = 0; i < n; ++i) mc_philox(ctr + 4 * i, key + 2 * i, out + 4 * i);
+}
+
+// out = fmaf(a, b, c), one rounding (numpy has no float fma)
+void mc_fmaf_many(int64_t n, const float* a, const float* b, const float* c, float* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = __builtin_fmaf(a[i], b[i], c[i]);
+}
+double mc_screen_ez(void) { return cwq::kScreenEz; }
+double mc_screen_sqrt2ln2(void) { return cwq::kSqrt2Ln2; }
+
+// out = (sa, sb, A, C, ok)
+void mc_screen_dim(int step0, float ls, float ss, float mu, float sg, float c, float bb,
+                   float* out) {
+  const cwq::ScreenDim o = step0 ? cwq::screen_dim<true>(ls, ss, mu, sg, c, bb)
+                                 : cwq::screen_dim<false>(ls, ss, mu, sg, c, bb);
+  out[0] = o.sa; out[1] = o.sb; out[2] = o.A; out[3] = o.C; out[4] = o.ok ? 1.0f : 0.0f;
+}
+// n dims at once: out[5 n]
+void mc_screen_dim_many(int64_t n, const uint8_t* step0, const float* ls, const float* ss,
+                        const float* mu, const float* sg, const float* c, const float* bb,
+                        float* out) {
+  for (int64_t i = 0; i < n; ++i)
+    mc_screen_dim(step0[i], ls[i], ss[i], mu[i], sg[i], c[i], bb[i], out + 5 * i);
+}
+// sums = (sum M, sum |M|, sum (|M| + M), sum A^2, sum C, max A, ok);
+// out = (gamma, sl, c1, c2, As, Pq, B, finite)
+void mc_screen_block(const double* sums, int64_t d, double h_s, double* out) {
+  cwq::ScreenSums u;
+  u.sm = sums[0]; u.sa = sums[1]; u.sk = sums[2]; u.s2 = sums[3]; u.cs = sums[4]; u.mx = sums[5];
+  u.ok = sums[6] != 0.0;
+  const cwq::ScreenBlock b = cwq::screen_block_consts(u, d, h_s);
+  out[0] = b.gam; out[1] = b.sl; out[2] = b.c1; out[3] = b.c2; out[4] = b.as; out[5] = b.pq;
+  out[6] = b.bf; out[7] = b.finite ? 1.0 : 0.0;
+}
+
+// A block of d dims (its sums accumulated as k_small_prep does, h_s = d) and
+// rows of it: zp[r d + j] the screening normals z' of row r, lp[r d + j] the
+// exact float log-densities.  For each row s = the sequential sum of -a^2, E =
+// the Eigen-order sum of lp, and out[3 r ..] = (lower, E, upper).  Returns 1,
+// or 0 when the block fails k_small_prep's gate (out is then untouched).
+int mc_screen_row_bounds(int step0, int64_t d, const float* ls, const float* ss, const float* mu,
+                         const float* sg, const float* c, const float* bb, int64_t rows,
+                         const float* zp, const float* lp, float* out) {
+  cwq::ScreenSums u;
+  std::vector<cwq::ScreenDim> o(d);
+  for (int64_t j = 0; j < d; ++j) {
+    o[j] = step0 ? cwq::screen_dim<true>(ls[j], ss[j], mu[j], sg[j], c[j], bb[j])
+                 : cwq::screen_dim<false>(ls[j], ss[j], mu[j], sg[j], c[j], bb[j]);
+    u.add(o[j]);
+  }
+  const cwq::ScreenBlock b = cwq::screen_block_consts(u, d, (double)d);
+  if (!(u.ok && b.finite && b.bf - b.bf == 0.0f && d > 0)) return 0;
+  for (int64_t r = 0; r < rows; ++r) {
+    float s = 0.0f;
+    for (int64_t j = 0; j < d; ++j) {
+      const float a = __builtin_fmaf(o[j].sa, zp[r * d + j], o[j].sb);
+      s = __builtin_fmaf(-a, a, s);
+    }
+    const float* x = lp + r * d;
+    const int64_t vec = d & ~(int64_t)7;
+    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int64_t j = 0; j < vec; j += 8)
+      for (int l = 0; l < 8; ++l) p[l] = p[l] + x[j + l];
+    float t = 0.0f;
+    for (int64_t j = vec; j < d; ++j) t = t + x[j];
+    out[3 * r] = cwq::screen_row_lower(s, b.c2, b.as, b.pq);
+    out[3 * r + 1] = cwq::eigen_fold8(p, t);
+    out[3 * r + 2] = cwq::screen_row_upper(s, b.c1, b.bf);
+  }
+  return 1;
 }
 }

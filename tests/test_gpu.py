@@ -383,7 +383,7 @@ def _adversarial_inputs(kind, nb, d):
 def test_screen_tables_within_bounds(cwq, cwqlib):
     """The screening pass's Box-Muller approximations (hardware v_log/v_sqrt/
     v_sin/v_cos) stay within the constants its bounds are built on
-    (kScreenEr, kScreenEs, kScreenRmax in csrc/cwq_kernels.hip), over all 2^23
+    (kScreenEr, kScreenEs, kScreenRmax in csrc/cwq_screen.h), over all 2^23
     inputs of each."""
     k_er, k_es, k_rmax = 1.0e-6, 6.0e-7, 5.68
     dev = torch.device("cuda")
