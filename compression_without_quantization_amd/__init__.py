@@ -12,12 +12,14 @@ from .coding import ArithmeticCoder
 from .coded_greedy_sampler import (Normal, code_greedy_sample, code_grouped_greedy_sample,
                                    code_grouped_greedy_sample_batch,
                                    decode, decode_blocks, decode_greedy_sample,
-                                   decode_grouped_greedy_sample, encode, encode_blocks,
+                                   decode_grouped_greedy_sample,
+                                   decode_grouped_greedy_sample_batch, encode, encode_blocks,
                                    encode_workspace_bytes, group_size_threshold, group_starts)
 from .coded_importance_sampler import (code_grouped_importance_sample,
                                        code_grouped_importance_sample_batch,
                                        code_importance_sample,
                                        decode_grouped_importance_sample,
+                                       decode_grouped_importance_sample_batch,
                                        decode_importance_sample, importance_decode_blocks,
                                        importance_encode_blocks)
 from .misc import stateless_normal_sample
@@ -38,4 +40,5 @@ __all__ = [
     "importance_encode_blocks", "importance_decode_blocks", "ArithmeticCoder",
     "write_bin_code", "read_bin_code", "ProbabilisticLadderNetwork", "build_empirical_dists",
     "encode_blocks_host", "code_grouped_greedy_sample_batch",
+    "decode_grouped_greedy_sample_batch", "decode_grouped_importance_sample_batch",
 ]

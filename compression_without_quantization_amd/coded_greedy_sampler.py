@@ -13,6 +13,10 @@ plus the batched block API the north star asks for:
   decode(indices_or_bitcode, prior_loc, prior_scale, seed, kl_bits)
   encode_blocks / decode_blocks   (CSR or uniform blocks, explicit n_steps)
 
+and the grouped coder for many items in one native call:
+
+  code_grouped_greedy_sample_batch / decode_grouped_greedy_sample_batch
+
 Differences from the TF1 reference (deliberate, documented in DESIGN.md):
   * functions return concrete values instead of graph tensors; ``sess`` is
     accepted and ignored;
@@ -709,6 +713,147 @@ def _int64_array(x):
         except (TypeError, OverflowError):
             pass
     return np.asarray(x, dtype=np.int64).reshape(-1)
+
+
+def _batch_seeds32(seeds, n_items):
+    """One int32 seed per item (an int: the same for all), wrapped as TF's int32
+    arithmetic wraps the single calls' seed."""
+    if np.ndim(seeds) == 0:
+        seeds64 = np.full(n_items, int(seeds), dtype=object)
+    else:
+        seeds64 = np.array([int(x) for x in seeds], dtype=object)
+    if seeds64.size != n_items:
+        raise ValueError("one seed per item")
+    return (seeds64 & 0xFFFFFFFF).astype(np.uint64).astype(np.uint32).view(np.int32)
+
+
+def _batch_proposals(proposals):
+    """The items' proposals as (p_loc, p_scale, item_off, device): float32 CUDA
+    tensors go through one torch.cat, anything else through the single call's
+    checks and conversions."""
+    cols = ([p.loc for p in proposals], [p.scale for p in proposals])
+    f32 = torch.float32
+    fast = all(type(a) is torch.Tensor and a.dtype is f32 and a.is_cuda for c in cols for a in c)
+    cat = None
+    if fast:
+        sz = [a.numel() for a in cols[0]]
+        if [a.numel() for a in cols[1]] != sz:
+            raise ValueError("loc and scale of an item's proposal must have the same size")
+        D0 = sum(sz)
+        try:
+            big = torch.cat([a for c in cols for a in c]).reshape(-1)
+            cat = [big[:D0], big[D0:]] if big.numel() == 2 * D0 else None
+        except RuntimeError:
+            cat = None
+    if cat is None:
+        for p in proposals:
+            if not _is_float32(p.loc) or not _is_float32(p.scale):
+                raise Exception("Proposal datatype must be float32!")
+        dev = _device_of(*[a for c in cols for a in c])
+        parts = [_dist_parts(p, dev, "Proposal") for p in proposals]
+        if any(a.numel() != b.numel() for a, b in parts):
+            raise ValueError("loc and scale of an item's proposal must have the same size")
+        sz = [a.numel() for a, _ in parts]
+        cat = [torch.cat([pt[k] for pt in parts]) for k in range(2)]
+    item_off = np.concatenate([[0], np.cumsum(np.array(sz, dtype=np.int64))]).astype(np.int64)
+    return cat[0].contiguous(), cat[1].contiguous(), item_off, cat[0].device
+
+
+def _decode_staging(n, stream_ordered, dev):
+    """Page-locked staging of a batch decode.  A call that waits for its result
+    uses this thread's cached buffer.  One that only enqueues work
+    (``stream_ordered``) leaves a copy from its staging in flight: it takes a
+    buffer no earlier such call may still be copying from, and release()
+    marks the point on the stream after which it is free again."""
+    if not stream_ordered:
+        return _pinned_scratch(n), lambda: None
+    pend = getattr(_scratch, "decode_pending", None)
+    if pend is None:
+        pend = _scratch.decode_pending = []
+    buf = None
+    for k, (b, ev) in enumerate(pend):
+        if b.numel() >= n and ev.query():
+            buf = pend.pop(k)[0]
+            break
+    if buf is None:
+        buf = torch.empty(max(int(n), 1), dtype=torch.uint8, pin_memory=True)
+    pend[:] = [(b, ev) for b, ev in pend if not ev.query()]  # finished smaller ones: dropped
+
+    def release():
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        pend.append((buf, ev))
+    return buf, release
+
+
+def decode_grouped_greedy_sample_batch(sess, bitcodes, group_start_indices, proposals,
+                                       n_bits_per_step, n_steps, seeds, adaptive=True, rho=1.,
+                                       *, as_tensor=False):
+    """decode_grouped_greedy_sample (coded_greedy_sampler.py:299-364) for a
+    batch of independent items in one native call
+    (cwq_decode_grouped_greedy_batch): one plan copy, one decode launch over
+    every item's groups, one copy back.
+
+    ``bitcodes`` / ``group_start_indices`` / ``proposals``: sequences with one
+    entry per item; ``group_start_indices[i]`` is what the matching encoder
+    returned for item i (a list, or the batch encoder's np.int64 array; it is
+    not modified).  Item i is decoded with seed ``seeds[i]`` (an int: the same
+    seed for every item).  Returns a list of np.float32 [D_i], each bit-equal
+    to decode_grouped_greedy_sample on that item alone.  ``as_tensor=True``
+    (keyword only): the samples stay on the device, returned as views of one
+    CUDA tensor, and nothing is copied to the host or waited for.  Not in the
+    reference (an extension for throughput).
+    """
+    lib = _lib.load()
+    bitcodes, proposals = list(bitcodes), list(proposals)
+    gsis = list(group_start_indices)
+    n_items = len(proposals)
+    if len(bitcodes) != n_items or len(gsis) != n_items:
+        raise ValueError("bitcodes, group_start_indices and proposals must have the same length")
+    if n_items == 0:
+        return []
+    seeds32 = _batch_seeds32(seeds, n_items)
+    p_loc, p_scale, item_off, dev = _batch_proposals(proposals)
+    D = int(item_off[-1])
+    n_steps, n_bits_per_step = int(n_steps), int(n_bits_per_step)
+    n_bits_per_group = n_bits_per_step * n_steps
+    st = [_int64_array(g) for g in gsis]
+    starts_off = np.concatenate([[0], np.cumsum([s.size for s in st])]).astype(np.int64)
+    starts_h = np.concatenate(st) if starts_off[-1] else np.zeros(1, np.int64)
+    bits_off = np.concatenate([[0], np.cumsum([len(b) for b in bitcodes])]).astype(np.int64)
+    if all(type(b) is str for b in bitcodes):
+        raw = "".join(bitcodes).encode("ascii")
+    else:
+        raw = b"".join(b if isinstance(b, bytes) else b.encode("ascii") for b in bitcodes)
+    for i in range(n_items):  # :345-347 and the single call's cover check
+        n_listed, Di = st[i].size, int(item_off[i + 1] - item_off[i])
+        n_avail = -(-len(bitcodes[i]) // n_bits_per_group) if n_bits_per_group else n_listed
+        G = min(n_listed, n_avail)
+        cover = (int(st[i][G]) if G < n_listed else Di) if G else 0
+        if G == 0 or cover != Di:
+            raise ValueError(f"item {i}: decoded groups cover {cover} of {Di} dims")
+    G_cap = int(starts_off[-1])
+    need = int(lib.cwq_decode_grouped_greedy_batch_workspace_size(D, G_cap, n_steps))
+    hneed = int(lib.cwq_decode_grouped_greedy_batch_host_workspace_size(D, G_cap, n_steps))
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        hws, release = _decode_staging(hneed, as_tensor, dev)
+        if as_tensor:
+            out_d = torch.empty(max(D, 1), dtype=torch.float32, device=dev)
+            out_h = None
+        else:
+            out_d = None
+            out_h = torch.empty(max(D, 1), dtype=torch.float32, pin_memory=True).numpy()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.cwq_decode_grouped_greedy_batch(
+            n_items, item_off.ctypes.data, _ptr(p_loc), _ptr(p_scale), raw, bits_off.ctypes.data,
+            starts_h.ctypes.data, starts_off.ctypes.data, n_steps, n_bits_per_step,
+            seeds32.ctypes.data, float(rho), None if as_tensor else out_h.ctypes.data,
+            out_d.data_ptr() if as_tensor else None, ws.data_ptr(), ws.numel(), hws.data_ptr(), hws.numel(), None, stream)
+        release()
+    _lib.check(rc, "cwq_decode_grouped_greedy_batch")
+    out = out_d if as_tensor else out_h
+    return [out[int(item_off[i]):int(item_off[i + 1])] for i in range(n_items)]
 
 
 def decode_grouped_greedy_sample(sess, bitcode, group_start_indices, proposal, n_bits_per_step,

@@ -30,7 +30,8 @@ import torch
 from . import _lib
 from .binary_io import (elias_delta_code, elias_delta_code_many, elias_delta_decode,
                         elias_delta_decode_many)
-from .coded_greedy_sampler import _device_of, _f32, _is_float32, _like_input, _ptr
+from .coded_greedy_sampler import (_batch_proposals, _batch_seeds32, _device_of, _f32,
+                                   _is_float32, _like_input, _pinned_scratch, _ptr)
 
 VERBOSE = True
 USE_FUSED = True   # code_grouped_importance_sample in one native call (tests compare both paths)
@@ -503,3 +504,65 @@ def decode_grouped_importance_sample(sess, bitcode, group_start_indices, proposa
     updates = np.zeros(D, dtype=np.float32)
     updates[np.asarray(outlier_indices, dtype=np.int64).reshape(-1)] = deq
     return np.where(updates == 0, sample_h, updates).astype(np.float32)
+
+
+def decode_grouped_importance_sample_batch(sess, bitcodes, group_start_indices, proposals,
+                                           n_bits_per_group, seeds, outlier_indices,
+                                           outlier_samples, use_indices=False):
+    """decode_grouped_importance_sample (:277-363) for a batch of independent
+    items in one native call (cwq_decode_grouped_importance_batch): one plan
+    copy, one row launch over every item's groups with the rescale (:347) fused,
+    one copy back; the outlier overwrite (:351-361) runs here, per item.
+
+    Every argument but ``n_bits_per_group`` and ``use_indices`` is a sequence
+    with one entry per item, as the single call takes it
+    (``group_start_indices[i]`` WITHOUT the trailing D_i); ``seeds`` may be an
+    int (the same seed for every item).  Returns a list of np.float32 [D_i],
+    each bit-equal to decode_grouped_importance_sample on that item alone.
+    Not in the reference (an extension for throughput)."""
+    lib = _lib.load()
+    bitcodes, proposals = list(bitcodes), list(proposals)
+    gsis = list(group_start_indices)
+    o_idx, o_val = list(outlier_indices), list(outlier_samples)
+    n_items = len(proposals)
+    if not (len(bitcodes) == len(gsis) == len(o_idx) == len(o_val) == n_items):
+        raise ValueError("one entry per item in every sequence")
+    if n_items == 0:
+        return []
+    seeds32 = _batch_seeds32(seeds, n_items)
+    p_loc, p_scale, item_off, dev = _batch_proposals(proposals)
+    D = int(item_off[-1])
+    st = [np.asarray(g, dtype=np.int64).reshape(-1) for g in gsis]
+    starts_off = np.concatenate([[0], np.cumsum([a.size for a in st])]).astype(np.int64)
+    G = int(starts_off[-1])
+    starts_h = np.concatenate(st) if G else np.zeros(1, np.int64)
+    index_h = np.empty(max(G, 1), dtype=np.int64)
+    for i in range(n_items):
+        a, b = int(starts_off[i]), int(starts_off[i + 1])
+        if use_indices:
+            vals = np.asarray(bitcodes[i], dtype=np.int64).reshape(-1)
+            if vals.size < b - a:
+                raise ValueError(f"item {i}: {vals.size} indices for {b - a} groups")
+        else:
+            vals, _ = elias_delta_decode_many(bitcodes[i], b - a)           # :325-336
+        index_h[a:b] = np.asarray(vals, dtype=np.int64)[:b - a] - 1
+    need = int(lib.cwq_decode_grouped_importance_batch_workspace_size(D, G))
+    hneed = int(lib.cwq_decode_grouped_importance_batch_host_workspace_size(D, G))
+    sample_h = np.empty(max(D, 1), dtype=np.float32)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        hws = _pinned_scratch(hneed)
+        _lib.check(lib.cwq_decode_grouped_importance_batch(
+            n_items, item_off.ctypes.data, _ptr(p_loc), _ptr(p_scale), index_h.ctypes.data,
+            starts_off.ctypes.data, starts_h.ctypes.data, starts_off.ctypes.data,
+            seeds32.ctypes.data, sample_h.ctypes.data, None, ws.data_ptr(), ws.numel(),
+            hws.data_ptr(), hws.numel(), None, _stream(dev)),
+            "cwq_decode_grouped_importance_batch")
+    res = []
+    for i in range(n_items):
+        a, b = int(item_off[i]), int(item_off[i + 1])
+        # :351-361 dequantise outliers and put them back where the update is non-zero
+        updates = np.zeros(b - a, dtype=np.float32)
+        updates[np.asarray(o_idx[i], dtype=np.int64).reshape(-1)] = dequantize_quint16(o_val[i])
+        res.append(np.where(updates == 0, sample_h[a:b], updates).astype(np.float32))
+    return res

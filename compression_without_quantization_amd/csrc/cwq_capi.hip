@@ -2355,6 +2355,314 @@ int64_t cwq_code_grouped_importance_batch(
                                  "cwq_code_grouped_importance_batch");
 }
 
+// ---------------------------------------------------------------------------
+// Batched grouped decoders (coded_greedy_sampler.py:299-364 and
+// coded_importance_sampler.py:277-363 once per item).  The host plans every
+// item's global group offsets, seeds and indices into one staging block, which
+// goes to the device in one copy; one launch decodes and destandardises every
+// item's groups; one copy brings the samples back.
+// ---------------------------------------------------------------------------
+namespace {
+// The plan as it lies in the host staging and in the device workspace: group
+// offsets (G + 1), the slot prefix (G + 1; greedy only), seeds (G), indices.
+struct DecPlan {
+  size_t off, slot, seeds, idx, total;
+};
+DecPlan dec_plan(int64_t G, bool slots, size_t idx_bytes_per_group) {
+  const size_t Gz = (size_t)(G > 0 ? G : 0);
+  DecPlan l;
+  l.off = 0;
+  l.slot = align_up((Gz + 1) * 8, 256);
+  l.seeds = l.slot + (slots ? align_up((Gz + 1) * 8, 256) : 0);
+  l.idx = l.seeds + align_up(Gz * 4, 256);
+  l.total = l.idx + align_up(Gz * idx_bytes_per_group, 256);
+  return l;
+}
+size_t dec_ws_bytes(int64_t D, int64_t G, bool slots, size_t idx_bytes_per_group) {
+  return dec_plan(G, slots, idx_bytes_per_group).total + align_up((size_t)D * 4, 256);
+}
+thread_local std::vector<int64_t> tl_dec_items;  // per item: G, first group, first slot, cover
+
+// The arguments the two batch decoders share.  Returns 1 for an empty batch
+// (nothing to do), 0 to go on, or a negative error code.
+int dec_check_common(const char* who, int64_t n_items, const int64_t* item_off,
+                     const int64_t* a_off, const int64_t* starts_off, const void* a_host,
+                     const int64_t* starts_host, const int32_t* seeds, const float* p_loc,
+                     const float* p_scale, const float* sample_host, const float* sample_dev) {
+  if (n_items < 0)
+    return fail(CWQ_ERR_INVALID, "%s: n_items=%lld must be >= 0", who, (long long)n_items);
+  if (!item_off || !a_off || !starts_off || !seeds)
+    return fail(CWQ_ERR_INVALID, "%s: null pointer (item_off, offsets or seeds)", who);
+  if (!sample_host && !sample_dev)
+    return fail(CWQ_ERR_INVALID, "%s: give sample_host or sample_dev", who);
+  if (n_items == 0) return 1;
+  if (item_off[0] != 0) return fail(CWQ_ERR_INVALID, "%s: item_off[0] must be 0", who);
+  for (int64_t i = 0; i < n_items; ++i)
+    if (item_off[i + 1] < item_off[i] || a_off[i + 1] < a_off[i] ||
+        starts_off[i + 1] < starts_off[i])
+      return fail(CWQ_ERR_INVALID, "%s: item %lld: offsets must be non-decreasing", who,
+                  (long long)i);
+  if (a_off[0] < 0 || starts_off[0] < 0)
+    return fail(CWQ_ERR_INVALID, "%s: negative offset", who);
+  if ((a_off[n_items] > a_off[0] && !a_host) ||
+      (starts_off[n_items] > starts_off[0] && !starts_host) ||
+      (item_off[n_items] > 0 && (!p_loc || !p_scale)))
+    return fail(CWQ_ERR_INVALID, "%s: null pointer", who);
+  return 0;
+}
+
+// Item i's groups: offs = its listed starts then D_i (:323 / :294), the first
+// G + 1 of them.  Returns the dims they cover (offs[G]; 0 for G == 0), or -1 if
+// they do not rise from 0; *slots = the groups' decode slots (decode_csr_slots).
+int64_t dec_item_cover(const int64_t* st, int64_t n_listed, int64_t Di, int64_t G,
+                       int64_t* slots) {
+  int64_t prev = 0, nq = 0;
+  for (int64_t g = 0; g <= G && G > 0; ++g) {
+    const int64_t b = g < n_listed ? st[g] : Di;
+    if ((g == 0 && b != 0) || b < prev || b > Di) return -1;
+    nq += cwq::decode_csr_slots(b - prev);
+    prev = b;
+  }
+  *slots = nq;
+  return prev;
+}
+
+// Runs f(i) for every item on the host pool (work claimed from a shared counter).
+void dec_for_items(int64_t n_items, bool parallel, const std::function<void(int64_t)>& f) {
+  std::atomic<int64_t> next{0};
+  auto worker = [&]() {
+    for (int64_t i; (i = next.fetch_add(1)) < n_items;) f(i);
+  };
+  const int64_t nw = std::min<int64_t>(host_threads() - 1, n_items - 1);
+  if (parallel && nw > 0)
+    HostPool::get().run(nw, worker);
+  else
+    worker();
+}
+
+// plan -> device, launch (queued by `launch`), sample -> host and one sync
+int64_t dec_finish(const char* who, const cwq_options& oi, const void* plan_h, void* plan_d,
+                   size_t plan_bytes, const std::function<hipError_t()>& launch, float* out,
+                   float* sample_host, int64_t D, int64_t Gtot, hipStream_t s) {
+  hipError_t e;
+  if ((e = hipMemcpyAsync(plan_d, plan_h, plan_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(e, who);
+  if (oi.eval_start_event &&
+      (e = hipEventRecord((hipEvent_t)oi.eval_start_event, s)) != hipSuccess)
+    return hip_fail(e, who);
+  if ((e = launch()) != hipSuccess) return hip_fail(e, who);
+  if (oi.eval_stop_event && (e = hipEventRecord((hipEvent_t)oi.eval_stop_event, s)) != hipSuccess)
+    return hip_fail(e, who);
+  if (sample_host) {
+    if ((e = hipMemcpyAsync(sample_host, out, (size_t)D * 4, hipMemcpyDeviceToHost, s)) !=
+            hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+      return hip_fail(e, who);
+  }
+  ok();
+  return Gtot;
+}
+}  // namespace
+
+size_t cwq_decode_grouped_greedy_batch_workspace_size(int64_t D_total, int64_t G_total,
+                                                      int n_steps) {
+  if (D_total < 0 || G_total < 0 || n_steps < 1) return 0;
+  return dec_ws_bytes(D_total, G_total, true, (size_t)n_steps * 4);
+}
+
+size_t cwq_decode_grouped_greedy_batch_host_workspace_size(int64_t D_total, int64_t G_total,
+                                                           int n_steps) {
+  if (D_total < 0 || G_total < 0 || n_steps < 1) return 0;
+  return dec_plan(G_total, true, (size_t)n_steps * 4).total;
+}
+
+int64_t cwq_decode_grouped_greedy_batch(
+    int64_t n_items, const int64_t* item_off, const float* p_loc, const float* p_scale,
+    const char* bits_host, const int64_t* bits_off, const int64_t* starts_host,
+    const int64_t* starts_off, int n_steps, int n_bits_per_step, const int32_t* seeds, float rho,
+    float* sample_host, float* sample_dev, void* workspace, size_t workspace_bytes,
+    void* host_workspace, size_t host_workspace_bytes, const cwq_options* opts, void* stream) {
+  const char* who = "cwq_decode_grouped_greedy_batch";
+  int rc = dec_check_common(who, n_items, item_off, bits_off, starts_off, bits_host, starts_host,
+                            seeds, p_loc, p_scale, sample_host, sample_dev);
+  if (rc < 0) return rc;
+  int rc2 = check_common(n_bits_per_step, n_steps, 0);
+  if (rc2) return rc2;
+  cwq_options oi;
+  if ((rc2 = read_options(opts, &oi))) return rc2;
+  if (rc == 1) {
+    ok();
+    return 0;
+  }
+  const int64_t D = item_off[n_items];
+  const int64_t Gcap = starts_off[n_items] - starts_off[0];
+  const size_t idx_b = (size_t)n_steps * 4;
+  if (workspace_bytes < dec_ws_bytes(D, Gcap, true, idx_b) || !workspace)
+    return fail(CWQ_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
+                dec_ws_bytes(D, Gcap, true, idx_b));
+  if (host_workspace_bytes < dec_plan(Gcap, true, idx_b).total || !host_workspace)
+    return fail(CWQ_ERR_WORKSPACE, "%s: host workspace too small (%zu < %zu)", who,
+                host_workspace_bytes, dec_plan(Gcap, true, idx_b).total);
+  // :345-347 group g of an item is decoded while its bit slice is non-empty
+  const int64_t bpg = (int64_t)n_bits_per_step * n_steps;
+  try {
+    tl_dec_items.assign((size_t)n_items * 4, 0);
+  } catch (...) {
+    return fail(CWQ_ERR_ALLOC, "%s: host allocation failed", who);
+  }
+  int64_t* it = tl_dec_items.data();  // [4 i]: G, first group, first slot, cover
+  int64_t Gtot = 0;
+  for (int64_t i = 0; i < n_items; ++i) {
+    const int64_t nl = starts_off[i + 1] - starts_off[i], nbits = bits_off[i + 1] - bits_off[i];
+    const int64_t avail = bpg > 0 ? (nbits + bpg - 1) / bpg : nl;
+    it[4 * i] = std::min(nl, avail);
+    it[4 * i + 1] = Gtot;
+    Gtot += it[4 * i];
+  }
+  const bool par = Gtot * n_steps >= 8192;
+  dec_for_items(n_items, par, [&](int64_t i) {
+    int64_t nq = 0;
+    it[4 * i + 3] = dec_item_cover(starts_host + starts_off[i], starts_off[i + 1] - starts_off[i],
+                                   item_off[i + 1] - item_off[i], it[4 * i], &nq);
+    it[4 * i + 2] = nq;
+  });
+  int64_t Stot = 0;
+  for (int64_t i = 0; i < n_items; ++i) {
+    const int64_t Di = item_off[i + 1] - item_off[i];
+    if (it[4 * i + 3] < 0)
+      return fail(CWQ_ERR_INVALID, "%s: item %lld: group starts must rise from 0 to at most %lld",
+                  who, (long long)i, (long long)Di);
+    if (it[4 * i] == 0 || it[4 * i + 3] != Di)
+      return fail(CWQ_ERR_INVALID, "%s: item %lld: decoded groups cover %lld of %lld dims", who,
+                  (long long)i, (long long)it[4 * i + 3], (long long)Di);
+    const int64_t nq = it[4 * i + 2];
+    it[4 * i + 2] = Stot;
+    Stot += nq;
+  }
+  const DecPlan l = dec_plan(Gtot, true, idx_b);
+  char* hp = (char*)host_workspace;
+  char* w = (char*)workspace;
+  int64_t* off_h = (int64_t*)(hp + l.off);
+  int64_t* slot_h = (int64_t*)(hp + l.slot);
+  int32_t* seed_h = (int32_t*)(hp + l.seeds);
+  int32_t* idx_h = (int32_t*)(hp + l.idx);
+  std::atomic<int> parse_rc{0};
+  dec_for_items(n_items, par, [&](int64_t i) {
+    const int64_t G = it[4 * i], gb = it[4 * i + 1], a = item_off[i];
+    const int64_t* st = starts_host + starts_off[i];
+    int64_t qn = it[4 * i + 2];
+    for (int64_t g = 0; g < G; ++g) {  // st[g + 1] past the list is D_i: the next item's a
+      const int64_t b0 = st[g], b1 = g + 1 < starts_off[i + 1] - starts_off[i]
+                                         ? st[g + 1] : item_off[i + 1] - a;
+      off_h[gb + g] = a + b0;
+      slot_h[gb + g] = qn;
+      qn += cwq::decode_csr_slots(b1 - b0);
+      seed_h[gb + g] = (int32_t)((uint32_t)seeds[i] + (uint32_t)g);  // :354 seed + g
+    }
+    // :330-342 the indices of its G groups; chars past the code read as '0'
+    if (cwq_bitcode_to_indices(bits_host ? bits_host + bits_off[i] : nullptr,
+                               bits_off[i + 1] - bits_off[i], n_bits_per_step, G * n_steps,
+                               idx_h + gb * n_steps) < 0)
+      parse_rc.store(1);
+  });
+  if (parse_rc.load()) return fail(CWQ_ERR_INVALID, "%s: bit parse failed", who);
+  off_h[Gtot] = D;
+  slot_h[Gtot] = Stot;
+  float* out = sample_dev ? sample_dev : (float*)(w + dec_plan(Gcap, true, idx_b).total);
+  hipStream_t s = (hipStream_t)stream;
+  return dec_finish(
+      who, oi, hp, w, l.total,
+      [&]() {
+        return cwq::launch_decode_csr_q4((const int32_t*)(w + l.idx), (const int64_t*)(w + l.off),
+                                         (const int64_t*)(w + l.slot), Gtot, Stot,
+                                         (const int32_t*)(w + l.seeds), n_bits_per_step, n_steps,
+                                         rho, p_loc, p_scale, out, s);
+      },
+      out, sample_host, D, Gtot, s);
+}
+
+size_t cwq_decode_grouped_importance_batch_workspace_size(int64_t D_total, int64_t G_total) {
+  if (D_total < 0 || G_total < 0) return 0;
+  return dec_ws_bytes(D_total, G_total, false, 8);
+}
+
+size_t cwq_decode_grouped_importance_batch_host_workspace_size(int64_t D_total,
+                                                               int64_t G_total) {
+  if (D_total < 0 || G_total < 0) return 0;
+  return dec_plan(G_total, false, 8).total;
+}
+
+int64_t cwq_decode_grouped_importance_batch(
+    int64_t n_items, const int64_t* item_off, const float* p_loc, const float* p_scale,
+    const int64_t* index_host, const int64_t* index_off, const int64_t* starts_host,
+    const int64_t* starts_off, const int32_t* seeds, float* sample_host, float* sample_dev,
+    void* workspace, size_t workspace_bytes, void* host_workspace, size_t host_workspace_bytes,
+    const cwq_options* opts, void* stream) {
+  const char* who = "cwq_decode_grouped_importance_batch";
+  int rc = dec_check_common(who, n_items, item_off, index_off, starts_off, index_host,
+                            starts_host, seeds, p_loc, p_scale, sample_host, sample_dev);
+  if (rc < 0) return rc;
+  cwq_options oi;
+  int rc2 = read_options(opts, &oi);
+  if (rc2) return rc2;
+  if (rc == 1) {
+    ok();
+    return 0;
+  }
+  const int64_t D = item_off[n_items];
+  const int64_t Gtot = starts_off[n_items] - starts_off[0];
+  if (workspace_bytes < dec_ws_bytes(D, Gtot, false, 8) || !workspace)
+    return fail(CWQ_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
+                dec_ws_bytes(D, Gtot, false, 8));
+  const DecPlan l = dec_plan(Gtot, false, 8);
+  if (host_workspace_bytes < l.total || !host_workspace)
+    return fail(CWQ_ERR_WORKSPACE, "%s: host workspace too small (%zu < %zu)", who,
+                host_workspace_bytes, l.total);
+  char* hp = (char*)host_workspace;
+  char* w = (char*)workspace;
+  int64_t* off_h = (int64_t*)(hp + l.off);
+  int32_t* seed_h = (int32_t*)(hp + l.seeds);
+  int64_t* idx_h = (int64_t*)(hp + l.idx);
+  int64_t gb = 0;
+  for (int64_t i = 0; i < n_items; ++i) {  // :294 the item's starts, then D_i
+    const int64_t G = starts_off[i + 1] - starts_off[i], a = item_off[i];
+    const int64_t Di = item_off[i + 1] - a;
+    const int64_t* st = starts_host + starts_off[i];
+    int64_t nq = 0;
+    const int64_t cover = dec_item_cover(st, G, Di, G, &nq);
+    if (cover < 0)
+      return fail(CWQ_ERR_INVALID, "%s: item %lld: group starts must rise from 0 to at most %lld",
+                  who, (long long)i, (long long)Di);
+    if (cover != Di)
+      return fail(CWQ_ERR_INVALID, "%s: item %lld: decoded groups cover %lld of %lld dims", who,
+                  (long long)i, (long long)cover, (long long)Di);
+    if (index_off[i + 1] - index_off[i] < G)
+      return fail(CWQ_ERR_INVALID, "%s: item %lld: %lld indices for %lld groups", who,
+                  (long long)i, (long long)(index_off[i + 1] - index_off[i]), (long long)G);
+    for (int64_t g = 0; g < G; ++g) {
+      off_h[gb + g] = a + st[g];
+      seed_h[gb + g] = (int32_t)((uint32_t)seeds[i] + (uint32_t)g);  // :339 seed + g
+      idx_h[gb + g] = index_host[index_off[i] + g];
+    }
+    gb += G;
+  }
+  off_h[Gtot] = D;
+  float* out = sample_dev ? sample_dev : (float*)(w + l.total);
+  hipStream_t s = (hipStream_t)stream;
+  if (Gtot == 0) {  // no dims either (every item is covered)
+    ok();
+    return 0;
+  }
+  return dec_finish(
+      who, oi, hp, w, l.total,
+      [&]() {
+        return cwq::launch_importance_decode_grouped(
+            (const int64_t*)(w + l.idx), (const int64_t*)(w + l.off), Gtot,
+            (const int32_t*)(w + l.seeds), p_loc, p_scale, out, s);
+      },
+      out, sample_host, D, Gtot, s);
+}
+
 int64_t cwq_group_starts(const float* kl, int64_t D, int64_t size_threshold, double n_nats,
                          int64_t* starts, int64_t cap) {
   return group_starts_impl(kl, D, size_threshold, n_nats, starts, cap, false);

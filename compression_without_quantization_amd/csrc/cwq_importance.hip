@@ -619,7 +619,8 @@ __global__ void __launch_bounds__(256) k_imp_small(
 // from index_in (decoder, coded_importance_sampler.py:82-109).  out_sample
 // (if given) gets the row; dst_out (if given) the row destandardised,
 // dst_scale * row + dst_loc, exactly as k_destandardise computes it (the
-// grouped calls' :265 rescale without a launch of its own).
+// grouped calls' :265 rescale without a launch of its own).  p_loc == p_scale
+// == nullptr: the standard proposal N(0, 1) (the same 0.0f + 1.0f * z).
 __global__ void __launch_bounds__(256) k_imp_rows(
     const unsigned long long* __restrict__ keys, const int64_t* __restrict__ index_in,
     const float* __restrict__ p_loc, const float* __restrict__ p_scale,
@@ -647,8 +648,8 @@ __global__ void __launch_bounds__(256) k_imp_rows(
       if (idx >= 0) {
         const uint64_t k = (uint64_t)idx * (uint64_t)d + (uint64_t)j;
         const float zz = f4_word(normal4_dev(st, k >> 2, logtab), (uint32_t)(k & 3u));
-        const float sc = p_scale[off + j];
-        v = shard_sample(p_loc[off + j], sc, zz);
+        const float sc = p_scale ? p_scale[off + j] : 1.0f;
+        v = shard_sample(p_loc ? p_loc[off + j] : 0.0f, sc, zz);
       }
       if (out_sample) out_sample[off + j] = v;
       if (dst_out) dst_out[off + j] = destandardise_1(v, dst_loc[off + j], dst_scale[off + j]);
@@ -758,6 +759,18 @@ hipError_t launch_importance_decode(const int64_t* index, const float* p_loc,
                      (const unsigned long long*)nullptr, index, p_loc, p_scale, block_off, nb,
                      SeedSpec{seed, block_id_base, nullptr}, (int64_t*)nullptr, out_sample,
                      (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_importance_decode_grouped(const int64_t* index, const int64_t* block_off,
+                                            int64_t nb, const int32_t* block_seeds,
+                                            const float* dst_loc, const float* dst_scale,
+                                            float* dst_out, hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_imp_rows, dim3(grid_for(nb, 4, 65536)), dim3(256), 0, stream,
+                     (const unsigned long long*)nullptr, index, (const float*)nullptr,
+                     (const float*)nullptr, block_off, nb, SeedSpec{0, 0, block_seeds},
+                     (int64_t*)nullptr, (float*)nullptr, dst_loc, dst_scale, dst_out);
   return hipGetLastError();
 }
 

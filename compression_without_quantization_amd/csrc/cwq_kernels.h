@@ -102,6 +102,17 @@ hipError_t launch_decode(const int32_t* idx, const float* p_loc, const float* p_
                          int n_bits,
                          int n_steps, int32_t seed, float rho, int64_t block_id_base,
                          float* out_sample, hipStream_t stream);
+// Grouped decode on the standard proposal, destandardisation fused
+// (k_decode_csr_q4): slot_off is the prefix of decode_csr_slots(d_g) over the nb
+// groups (nb + 1 entries, n_slots its last), block_seeds the per-group seeds [nb].
+__host__ __device__ inline int64_t decode_csr_slots(int64_t d) {
+  return d > 0 ? ((d + 3) >> 2) + 1 : 0;  // the row's Philox blocks at any alignment
+}
+hipError_t launch_decode_csr_q4(const int32_t* idx, const int64_t* block_off,
+                                const int64_t* slot_off, int64_t nb, int64_t n_slots,
+                                const int32_t* block_seeds, int n_bits, int n_steps, float rho,
+                                const float* dst_loc, const float* dst_scale, float* out,
+                                hipStream_t stream);
 hipError_t launch_stateless_normal_sample(const float* loc, const float* scale, int64_t d,
                                           int64_t num_samples, int32_t seed, float* out,
                                           hipStream_t stream);
@@ -178,6 +189,12 @@ hipError_t launch_importance_decode(const int64_t* index, const float* p_loc,
                                     const float* p_scale, const int64_t* block_off, int64_t nb,
                                     int32_t seed, int64_t block_id_base, float* out_sample,
                                     hipStream_t stream);
+// Grouped decode of a batch: rows of the standard proposal N(0, 1) with
+// per-group seeds, destandardised by dst_loc / dst_scale into dst_out.
+hipError_t launch_importance_decode_grouped(const int64_t* index, const int64_t* block_off,
+                                            int64_t nb, const int32_t* block_seeds,
+                                            const float* dst_loc, const float* dst_scale,
+                                            float* dst_out, hipStream_t stream);
 
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);

@@ -2713,6 +2713,138 @@ __global__ void __launch_bounds__(256, CWQ_GLDS_MIN_WAVES) k_decode_q4_glds(
   }
 }
 
+// Grouped (CSR) decode on the standard proposal with the destandardisation
+// fused: k_decode with p_loc = 0, p_scale = 1 followed by k_destandardise, the
+// same roundings in the same order.  The unit of work is a slot, one Philox
+// block of a group's selected row: at step s the row n starts at flat element
+// k0 = n d of the step's stream, and slot q evaluates block (k0 >> 2) + q once
+// (one Philox + two exact Box-Muller pairs).  With r = k0 & 3 the four dims
+// 4q .. 4q+3 (quad q) are words r..3 of slot q's block and words 0..r-1 of
+// slot q+1's, so a group of d > 0 dims has ceil(d/4) + 1 slots (slot_off: that
+// prefix over the groups, nb + 1 entries; an empty group has none): slot q <
+// ceil(d/4) owns quad q and takes the next block from the next lane by lane
+// shuffle, the group's last slot owns no dims.  r changes from step to step,
+// so the accumulators stay with the dims.  (First mapping tried: ceil(d/4)
+// lanes per group, a lane evaluating the next block itself where no next lane
+// had it; nearly every wave then ran the Box-Muller twice per step -- lane 63
+// of a long group, the last quad of a short one: DESIGN.md.)
+// A wave covers slots [63 w, 63 w + 64): its lane 63 repeats the next wave's
+// lane 0 and owns nothing here, so every owning lane has its next lane in the
+// wave.  A group longer than 252 dims simply spans waves and workgroups.
+// Stream keys (TF GenerateKey: a Philox-10 call each): the wave's lanes cover
+// a contiguous run of L groups; L <= 64: lane i derives the key of (step s0 +
+// i / L, the run's group i % L) for a window of 64 / L steps at once, and
+// every lane takes its (group, step) key by shuffle: a 4095-dim group at 30
+// steps pays one key call per wave, not 30 per lane.  L > 64 (a run of empty
+// groups inside the wave's slots): each lane derives its own keys.
+// Waves past the slot count ns (= slot_off[nb], passed by value) return at
+// once; the last wave's lanes past it stay as shuffle partners and key
+// producers only: they form no address from their own index (the one read
+// they may make is a seed of the wave's own run of groups).
+// U: steps evaluated together (2 for multi-step codes: a long group's waves are
+// few -- one per SIMD at the c2cli shape -- and two independent Philox /
+// Box-Muller chains hide each other's latency; the sums stay in step order).
+template <int U>
+__global__ void __launch_bounds__(256) k_decode_csr_q4(
+    const int32_t* __restrict__ idx, const int64_t* __restrict__ block_off,
+    const int64_t* __restrict__ slot_off, int64_t nb, int64_t ns, SeedSpec sd, int n_steps,
+    int64_t n_cand, float nst, float sdiv, float rho, const float* __restrict__ dst_loc,
+    const float* __restrict__ dst_scale, float* __restrict__ out) {
+  __shared__ double logtab[32];
+  fill_logtab(logtab);
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t t0 = ((int64_t)blockIdx.x * 4 + wave_id()) * 63;
+  if (t0 >= ns) return;
+  const int64_t t = t0 + lane;
+  const bool active = t < ns;
+  const uint32_t last = (uint32_t)(ns - t0 < 64 ? ns - t0 : 64) - 1u;  // last active lane
+  int64_t g = 0, off = 0, d = 0, q = 0;
+  if (active) {
+    g = block_of_dim(slot_off, nb, t);
+    off = block_off[g];
+    d = block_off[g + 1] - off;
+    q = t - slot_off[g];
+  }
+  const int64_t j0 = 4 * q;
+  // this lane's dims: quad q's (1..4), none for a group's last slot or lane 63
+  const int cnt = active && lane < 63u && j0 < d ? (int)(d - j0 < 4 ? d - j0 : 4) : 0;
+  // the wave's run of groups [g_first, g_last]
+  const int64_t g_first = __shfl(g, 0, 64);
+  const int64_t g_last = __shfl(g, (int)last, 64);
+  const int64_t run = g_last - g_first + 1;
+  const uint32_t L = __builtin_amdgcn_readfirstlane((uint32_t)(run < 65 ? run : 65));
+  const bool shared_keys = L <= 64u;
+  const uint32_t spw = shared_keys ? 64u / L : 1u;       // steps per key window
+  const uint32_t gi = active ? (uint32_t)(g - g_first) : 0u;
+  const uint32_t ds_lane = shared_keys ? lane / L : 0u;  // this lane's (step, group) of a window
+  const uint32_t gj_lane = lane - ds_lane * L;
+  const int32_t seed_own = active ? sd.of(g) : 0;
+  const int32_t seed_win =
+      shared_keys && ds_lane < spw ? sd.of(g_first + gj_lane) : 0;  // g_first + gj_lane <= g_last
+  float ls, ss;  // wave-uniform: the standard proposal's shard
+  shard_consts(0.0f, 1.0f, nst, sdiv, rho, ls, ss);
+  float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // sample = tf.zeros (:143)
+  bool bad = false;
+  PhiloxStream kw{0u, 0u, 0u, 0u};
+  uint32_t ws = 0;  // first step of the key window
+  for (int s0 = 0; s0 < n_steps; s0 += U) {
+    const int nu = n_steps - s0 < U ? n_steps - s0 : U;  // wave-uniform
+    PhiloxStream ku[U];
+    uint64_t k0[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {  // keys and rows first: the branches stay out of the arithmetic
+      const int s = s0 + u < n_steps ? s0 + u : n_steps - 1;
+      if (shared_keys) {
+        if ((uint32_t)s == ws + spw || s == 0) {  // wave-uniform
+          ws = (uint32_t)s;
+          kw = generate_key(step_seed(seed_win, (int32_t)(ws + ds_lane)), 42);
+        }
+        const int src = (int)(((uint32_t)s - ws) * L + gi);
+        ku[u] = PhiloxStream{
+            (uint32_t)__shfl((int)kw.k0, src, 64), (uint32_t)__shfl((int)kw.k1, src, 64),
+            (uint32_t)__shfl((int)kw.c2, src, 64), (uint32_t)__shfl((int)kw.c3, src, 64)};
+      } else {
+        ku[u] = generate_key(step_seed(seed_own, s), 42);
+      }
+      int64_t n = active ? (int64_t)idx[g * n_steps + s] : 0;
+      if (n < 0 || n >= n_cand) {  // NaN for the whole group, as in k_decode
+        bad = true;
+        n = 0;
+      }
+      k0[u] = (uint64_t)n * (uint64_t)d;
+    }
+    float zz[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t r = (uint32_t)(k0[u] & 3u);
+      const F4 z = normal4_dev(ku[u], (k0[u] >> 2) + (uint64_t)q, logtab);
+      // the next slot's block (an owning lane's next lane is its group's next slot)
+      const float na = __shfl_down(z.a, 1, 64), nb1 = __shfl_down(z.b, 1, 64),
+                  nc = __shfl_down(z.c, 1, 64);
+      zz[u][0] = r == 0 ? z.a : (r == 1 ? z.b : (r == 2 ? z.c : z.d));
+      zz[u][1] = r == 0 ? z.b : (r == 1 ? z.c : (r == 2 ? z.d : na));
+      zz[u][2] = r == 0 ? z.c : (r == 1 ? z.d : (r == 2 ? na : nb1));
+      zz[u][3] = r == 0 ? z.d : (r == 1 ? na : (r == 2 ? nb1 : nc));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (u < nu) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          v[w] = v[w] + shard_sample(ls, ss, zz[u][w]);  // :153 sample + row indices[i]
+      }
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (w < cnt) {
+      const int64_t i = off + j0 + w;
+      const float x = bad ? __builtin_nanf("") : v[w];
+      out[i] = destandardise_1(x, dst_loc[i], dst_scale[i]);  // :362
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // misc.py:3-17 materialised: out[n*d+j] = loc[j] + scale[j] * (z*1 + 0).
 // ---------------------------------------------------------------------------
@@ -3450,6 +3582,23 @@ hipError_t launch_decode(const int32_t* idx, const float* p_loc, const float* p_
   hipLaunchKernelGGL(k_decode, dim3(grid_for(total_dims, 256, 16384)), dim3(256), 0, stream, idx,
                      p_loc, p_scale, block_off, ud, nb, n_steps, (int64_t)1 << n_bits, nst, sdiv,
                      rho, seed, block_id_base, out_sample);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_csr_q4(const int32_t* idx, const int64_t* block_off,
+                                const int64_t* slot_off, int64_t nb, int64_t n_slots,
+                                const int32_t* block_seeds, int n_bits, int n_steps, float rho,
+                                const float* dst_loc, const float* dst_scale, float* out,
+                                hipStream_t stream) {
+  if (nb <= 0 || n_slots <= 0) return hipSuccess;
+  const int64_t grid = ((n_slots + 62) / 63 + 3) / 4;  // a wave per 63 slots (k_decode_csr_q4)
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  const float nst = (float)n_steps;
+  const float sdiv = (float)__builtin_sqrt((double)n_steps);
+  hipLaunchKernelGGL(n_steps > 1 ? k_decode_csr_q4<2> : k_decode_csr_q4<1>, dim3((unsigned)grid),
+                     dim3(256), 0, stream, idx, block_off,
+                     slot_off, nb, n_slots, SeedSpec{0, 0, block_seeds}, n_steps,
+                     (int64_t)1 << n_bits, nst, sdiv, rho, dst_loc, dst_scale, out);
   return hipGetLastError();
 }
 

@@ -25,6 +25,11 @@
  *   cwq_code_grouped_greedy      <- code/coded_greedy_sampler.py:170-296
  *                                   (the whole grouped coder in one call)
  *   cwq_code_grouped_greedy_batch <- the same, once per item of a batch
+ *   cwq_decode_grouped_greedy_batch <- code/coded_greedy_sampler.py:299-364
+ *                                   decode_grouped_greedy_sample, once per item
+ *   cwq_decode_grouped_importance_batch <- code/coded_importance_sampler.py:
+ *                                   277-363 decode_grouped_importance_sample
+ *                                   (without the outlier overwrite), per item
  *
  * Conventions
  *   - All float/index pointers are DEVICE pointers (hipMalloc / torch cuda
@@ -74,8 +79,9 @@ extern "C" {
  *        (cwq_options.item_ready);
  *   0.5  CWQ_ERR_ALLOC (host allocation failures are returned, never thrown);
  *        starts_host of the grouped _begin calls is read asynchronously;
- *   0.6  cwq_code_grouped_importance_batch. */
-#define CWQ_ABI_VERSION ((0 << 16) | 6)
+ *   0.6  cwq_code_grouped_importance_batch;
+ *   0.7  cwq_decode_grouped_greedy_batch, cwq_decode_grouped_importance_batch. */
+#define CWQ_ABI_VERSION ((0 << 16) | 7)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -375,6 +381,64 @@ int64_t cwq_code_grouped_importance_batch(
     int64_t* starts_host, int64_t starts_cap, int64_t* n_starts, int64_t* outlier_idx_host,
     float* outlier_val_host, int64_t* n_outliers, double* kl_sum_out, void* workspace,
     size_t workspace_bytes, const cwq_options* opts, void* stream);
+
+/* ---- Batched grouped decoders ------------------------------------------- */
+/* A batch of independent decode_grouped_greedy_sample calls
+ * (coded_greedy_sampler.py:299-364 once per item) in one call.  Item i is dims
+ * [item_off[i], item_off[i+1]) of the concatenated DEVICE p_loc / p_scale
+ * (item_off: HOST int64 [n_items + 1], item_off[0] == 0).  HOST inputs: its
+ * code, the '0'/'1' chars bits_host[bits_off[i], bits_off[i+1]), and its
+ * group_start_indices (local to the item, as its encoder returned them, with
+ * or without the trailing D_i), starts_host[starts_off[i], starts_off[i+1]);
+ * seeds: HOST int32 [n_items].  The item is decoded exactly as the reference
+ * decodes it alone: D_i is appended to its starts (:323), its groups are
+ * numbered from 0 and seeded seeds[i] + g (int32 wrap), group g is decoded
+ * while its bit slice is non-empty (:345-347), and chars past the end of the
+ * code read as '0' (cwq_bitcode_to_indices' rule).  The groups so decoded must
+ * cover its D_i dims: otherwise CWQ_ERR_INVALID, with the item named, before
+ * anything is launched.
+ * The call parses the codes and plans the global group offsets, slot prefix
+ * and seeds into host_workspace (on the library's host threads, item by item),
+ * copies that plan to the device once, decodes every group of every item in
+ * one launch (standard proposal, then sample * p_scale + p_loc, :362) and, if
+ * sample_host is given, copies the D_total samples to it and synchronises the
+ * stream once.  sample_dev (DEVICE [D_total]) receives the samples on the
+ * device; either may be NULL, not both.  With sample_host == NULL the call
+ * only enqueues work: host_workspace is the source of an asynchronous copy and
+ * must stay valid and unchanged until the stream has reached this point, as
+ * starts_host of cwq_code_grouped_greedy_begin must until _end.
+ * G_total of the size functions: the total number of starts entries
+ * (starts_off[n_items] - starts_off[0]).  host_workspace is best page-locked.
+ * opts: only eval_start_event / eval_stop_event are read (recorded around the
+ * launch).  Returns the total number of groups decoded, or a negative code. */
+size_t cwq_decode_grouped_greedy_batch_workspace_size(int64_t D_total, int64_t G_total,
+                                                      int n_steps);
+size_t cwq_decode_grouped_greedy_batch_host_workspace_size(int64_t D_total, int64_t G_total,
+                                                           int n_steps);
+int64_t cwq_decode_grouped_greedy_batch(
+    int64_t n_items, const int64_t* item_off, const float* p_loc, const float* p_scale,
+    const char* bits_host, const int64_t* bits_off, const int64_t* starts_host,
+    const int64_t* starts_off, int n_steps, int n_bits_per_step, const int32_t* seeds, float rho,
+    float* sample_host, float* sample_dev, void* workspace, size_t workspace_bytes,
+    void* host_workspace, size_t host_workspace_bytes, const cwq_options* opts, void* stream);
+
+/* The same for decode_grouped_importance_sample (coded_importance_sampler.py:
+ * 277-363) up to the rescale (:347); the outlier overwrite (:351-361) stays
+ * with the caller.  HOST inputs: item i's 0-based indices (the decoded
+ * Elias-delta values - 1), index_host[index_off[i] ...], one per group, and its
+ * group_start_indices WITHOUT the trailing D_i (the reference appends it,
+ * :294), starts_host[starts_off[i], starts_off[i+1]).  Group g of item i is row
+ * index[g] of the stream seeded seeds[i] + g.  One plan copy, one launch, one
+ * copy out; workspace, staging, sample_host / sample_dev, opts and the return
+ * value as above (G_total: the total number of starts entries). */
+size_t cwq_decode_grouped_importance_batch_workspace_size(int64_t D_total, int64_t G_total);
+size_t cwq_decode_grouped_importance_batch_host_workspace_size(int64_t D_total, int64_t G_total);
+int64_t cwq_decode_grouped_importance_batch(
+    int64_t n_items, const int64_t* item_off, const float* p_loc, const float* p_scale,
+    const int64_t* index_host, const int64_t* index_off, const int64_t* starts_host,
+    const int64_t* starts_off, const int32_t* seeds, float* sample_host, float* sample_dev,
+    void* workspace, size_t workspace_bytes, void* host_workspace, size_t host_workspace_bytes,
+    const cwq_options* opts, void* stream);
 
 /* ---- Arithmetic coder (code/coding.pyx:27-310), HOST functions ---------- */
 /* ArithmeticCoder(P, precision).encode(message): writes the code as '0'/'1'
