@@ -26,6 +26,8 @@ from .misc import stateless_normal_sample
 from .pln import ProbabilisticLadderNetwork, build_empirical_dists
 from .parallel import gather_indices, shard_range
 from .streaming import encode_blocks_host
+from .varbits import (block_bits, decode_blocks_var, encode_blocks_var, pack_indices,
+                      unpack_indices)
 
 __all__ = [
     "Normal", "code_greedy_sample", "decode_greedy_sample", "code_grouped_greedy_sample",
@@ -41,4 +43,5 @@ __all__ = [
     "write_bin_code", "read_bin_code", "ProbabilisticLadderNetwork", "build_empirical_dists",
     "encode_blocks_host", "code_grouped_greedy_sample_batch",
     "decode_grouped_greedy_sample_batch", "decode_grouped_importance_sample_batch",
+    "block_bits", "encode_blocks_var", "decode_blocks_var", "pack_indices", "unpack_indices",
 ]

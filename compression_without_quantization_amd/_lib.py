@@ -66,6 +66,17 @@ SIGNATURES = {
                                   c_i32, c_f32, c_i64, c_vp, c_vp]),
     "cwq_greedy_decode_uniform": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_i32,
                                           c_f32, c_i64, c_vp, c_vp]),
+    "cwq_block_bits": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f64, c_int, c_int, c_vp,
+                               c_vp, c_vp]),
+    "cwq_greedy_encode_uniform_var_workspace_size": (c_size, [c_i64, c_i64]),
+    "cwq_greedy_encode_uniform_var": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_int,
+                                              c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_size,
+                                              c_opts, c_vp]),
+    "cwq_pack_indices_var_workspace_size": (c_size, [c_i64]),
+    "cwq_pack_indices_var": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_size,
+                                     c_vp]),
+    "cwq_unpack_indices_var": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_size,
+                                       c_vp]),
     "cwq_standardise": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "cwq_kl_normal_normal": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "cwq_destandardise": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -137,7 +148,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 7
+ABI_VERSION = (0 << 16) | 8
 
 _lib = None
 

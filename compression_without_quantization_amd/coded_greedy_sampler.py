@@ -235,8 +235,16 @@ def _decode_blocks_on(lib, it, pl, ps, D, n_steps, n_bits_per_step, seed32, rho,
 # ---------------------------------------------------------------------------
 # north-star convenience surface
 # ---------------------------------------------------------------------------
+def _per_block_bits(kl_bits):
+    """True for an array of bit counts (one per row), False for one integer."""
+    if isinstance(kl_bits, torch.Tensor):
+        return kl_bits.dim() > 0
+    return np.ndim(kl_bits) > 0
+
+
 def encode(prior_loc, prior_scale, post_loc, post_scale, seed, kl_bits, block_id_base=0):
-    """Code every block (row) of [nb, d] (or one [d] block) at ``kl_bits`` bits.
+    """Code every block (row) of [nb, d] (or one [d] block) at ``kl_bits`` bits
+    (one integer, or an array with a count per row).
 
     = code_greedy_sample(t=post, p=prior, n_bits_per_step=kl_bits, n_steps=1,
     seed=seed + block_id_base + g) for each row g.  Returns (indices int32 [nb],
@@ -245,18 +253,29 @@ def encode(prior_loc, prior_scale, post_loc, post_scale, seed, kl_bits, block_id
     shape = tuple(np.shape(prior_loc)) if not isinstance(prior_loc, torch.Tensor) \
         else tuple(prior_loc.shape)
     d = shape[-1] if len(shape) else 1
-    idx, sample = encode_blocks(post_loc, post_scale, prior_loc, prior_scale, kl_bits, 1, seed,
-                                block_dim=d, block_id_base=block_id_base)
+    if _per_block_bits(kl_bits):  # a count per row (varbits.py)
+        from .varbits import encode_blocks_var
+        idx, sample = encode_blocks_var(post_loc, post_scale, prior_loc, prior_scale, kl_bits, 1,
+                                        seed, block_dim=d, block_id_base=block_id_base)
+    else:
+        idx, sample = encode_blocks(post_loc, post_scale, prior_loc, prior_scale, kl_bits, 1,
+                                    seed, block_dim=d, block_id_base=block_id_base)
     return _like_input(idx.reshape(shape[:-1]), prior_loc), \
         _like_input(sample.reshape(shape), prior_loc)
 
 
 def decode(indices_or_bitcode, prior_loc, prior_scale, seed, kl_bits, block_id_base=0):
-    """Inverse of encode: indices (int [nb]) or the LSB-first bitcode str."""
+    """Inverse of encode: indices (int [nb]) or the LSB-first bitcode str; with
+    an array of ``kl_bits``, indices or the packed stream of pack_indices."""
     shape = tuple(np.shape(prior_loc)) if not isinstance(prior_loc, torch.Tensor) \
         else tuple(prior_loc.shape)
     d = shape[-1] if len(shape) else 1
     nb = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
+    if _per_block_bits(kl_bits):  # indices, or the packed stream of pack_indices
+        from .varbits import decode_blocks_var
+        sample = decode_blocks_var(indices_or_bitcode, kl_bits, prior_loc, prior_scale, 1, seed,
+                                   block_dim=d, block_id_base=block_id_base)
+        return _like_input(sample.reshape(shape), prior_loc)
     if isinstance(indices_or_bitcode, (str, bytes)):
         indices_or_bitcode = bitcode_to_indices(indices_or_bitcode, int(kl_bits), nb)
     sample = decode_blocks(indices_or_bitcode, prior_loc, prior_scale, kl_bits, 1, seed,

@@ -548,6 +548,229 @@ int cwq_destandardise(const float* sample, const float* p_loc, const float* p_sc
 }
 
 // ---------------------------------------------------------------------------
+// Uniform blocks with a bit budget each (cwq_varbits.hip): the blocks are
+// sorted by budget, each budget's blocks go through encode_impl as one launch
+// sequence with per-block seeds, and the results are scattered back.
+// ---------------------------------------------------------------------------
+namespace {
+struct VarWs {
+  size_t t_loc, t_scale, p_loc, p_scale, sample, seeds, perm, hist, counts, enc, stage, total;
+  size_t enc_bytes;
+};
+// The encoders write the sorted index rows into the caller's out_idx; they are
+// staged for the scatter in the sorted inputs' region (16 nb d bytes, dead by
+// then) when 4 nb n_steps bytes fit there, i.e. n_steps <= 4 d, else in a tail
+// of that size: cwq_greedy_encode_uniform_var_workspace_size is n_steps = 1.
+VarWs var_layout(int64_t nb, int64_t d, int64_t n_steps) {
+  VarWs l;
+  const size_t row = (size_t)nb * (size_t)d * 4;
+  size_t o = 0;
+  l.t_loc = o;
+  o += row;
+  l.t_scale = o;
+  o += row;
+  l.p_loc = o;
+  o += row;
+  l.p_scale = o;
+  o = align_up(o + row, 256);
+  l.sample = o;
+  o = align_up(o + row, 256);
+  l.seeds = o;
+  o = align_up(o + (size_t)nb * 4, 256);
+  l.perm = o;
+  o = align_up(o + (size_t)nb * 4, 256);
+  l.hist = o;
+  o = align_up(o + cwq::vb_sort_scratch_bytes(nb), 256);
+  l.counts = o;
+  o = align_up(o + 32 * 4, 256);
+  l.enc = o;
+  l.enc_bytes = ws_layout_uniform(nb, d).total;
+  o = align_up(o + l.enc_bytes, 256);
+  l.stage = 0;
+  if (n_steps > 4 * d) {
+    l.stage = o;
+    o = align_up(o + (size_t)nb * (size_t)n_steps * 4, 256);
+  }
+  l.total = o;
+  return l;
+}
+
+struct PackWs {
+  size_t off, partial, flag, total;
+};
+PackWs pack_layout(int64_t nb) {
+  PackWs l;
+  size_t o = 0;
+  l.off = o;
+  o = align_up(o + (size_t)(nb + 1) * 8, 256);
+  l.partial = o;
+  o = align_up(o + cwq::vb_offsets_scratch_bytes(nb), 256);
+  l.flag = o;
+  o = align_up(o + 4, 256);
+  l.total = o;
+  return l;
+}
+
+// nb of the variable-budget entries: perm and the bin counts are 32-bit
+int check_var_nb(int64_t nb) {
+  if (nb < 0 || nb > INT32_MAX)
+    return fail(CWQ_ERR_INVALID, "nb=%lld outside [0, 2^31 - 1]", (long long)nb);
+  return CWQ_OK;
+}
+}  // namespace
+
+int cwq_block_bits(const float* q_loc, const float* q_scale, const float* p_loc,
+                   const float* p_scale, int64_t nb, int64_t d, double extra_bits, int min_bits,
+                   int max_bits, int32_t* bits_out, float* kl_bits_out, void* stream) {
+  if (nb < 0 || d < 0 || (d > 0 && nb > INT64_MAX / d)) return fail(CWQ_ERR_INVALID, "bad nb / d");
+  if (min_bits < 0 || max_bits > CWQ_MAX_BITS_PER_STEP || min_bits > max_bits)
+    return fail(CWQ_ERR_INVALID, "need 0 <= min_bits=%d <= max_bits=%d <= %d", min_bits, max_bits,
+                CWQ_MAX_BITS_PER_STEP);
+  if (!(extra_bits == extra_bits)) return fail(CWQ_ERR_INVALID, "extra_bits is NaN");
+  if (nb == 0) return ok();
+  if (!bits_out || (d > 0 && (!q_loc || !q_scale || !p_loc || !p_scale)))
+    return fail(CWQ_ERR_INVALID, "null pointer");
+  hipError_t e = cwq::launch_block_bits(q_loc, q_scale, p_loc, p_scale, nb, d, extra_bits,
+                                        min_bits, max_bits, bits_out, kl_bits_out,
+                                        (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_block_bits");
+  return ok();
+}
+
+size_t cwq_greedy_encode_uniform_var_workspace_size(int64_t nb, int64_t d) {
+  if (nb < 0 || nb > INT32_MAX || d < 0 || (d > 0 && nb > INT64_MAX / d / 64)) return 0;
+  return var_layout(nb, d, 1).total;
+}
+
+int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                                  const float* p_scale, int64_t nb, int64_t d,
+                                  const int32_t* n_bits, int n_steps, int32_t seed, float rho,
+                                  int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                                  void* workspace, size_t workspace_bytes,
+                                  const cwq_options* opts, void* stream) {
+  int rc;
+  if (d < 0) return fail(CWQ_ERR_INVALID, "d must be >= 0");
+  if ((rc = check_var_nb(nb))) return rc;
+  if (d > 0 && nb > INT64_MAX / d / 64) return fail(CWQ_ERR_INVALID, "bad nb");
+  if (n_steps < 1) return fail(CWQ_ERR_INVALID, "n_steps=%d must be >= 1", n_steps);
+  cwq_options o;
+  if ((rc = read_options(opts, &o))) return rc;
+  if (nb == 0) return ok();
+  if (!n_bits || !out_idx) return fail(CWQ_ERR_INVALID, "n_bits / out_idx is null");
+  if (d > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
+    return fail(CWQ_ERR_INVALID, "null input/output pointer");
+  const VarWs l = var_layout(nb, d, n_steps);
+  if (workspace_bytes < l.total || !workspace)
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
+                l.total);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)workspace;
+  float* tl_s = (float*)(w + l.t_loc);
+  float* ts_s = (float*)(w + l.t_scale);
+  float* pl_s = (float*)(w + l.p_loc);
+  float* ps_s = (float*)(w + l.p_scale);
+  float* sample_s = (float*)(w + l.sample);
+  int32_t* seeds_s = (int32_t*)(w + l.seeds);
+  int32_t* perm = (int32_t*)(w + l.perm);
+  uint32_t* counts_dev = (uint32_t*)(w + l.counts);
+  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, (uint32_t*)(w + l.hist), counts_dev, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (sort)");
+  // the one synchronisation: the bucket sizes decide the launches
+  uint32_t counts[32];
+  e = hipMemcpyAsync(counts, counts_dev, sizeof(counts), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (counts)");
+  if (counts[31] != 0)
+    return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", counts[31],
+                (long long)nb, CWQ_MAX_BITS_PER_STEP);
+  e = cwq::launch_vb_gather(t_loc, t_scale, p_loc, p_scale, perm, nb, d, seed, block_id_base,
+                            tl_s, ts_s, pl_s, ps_s, seeds_s, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (gather)");
+  // the eval events go around all the buckets' launches, so each bucket's own
+  // call takes the options without them
+  cwq_options ob = o;
+  ob.eval_start_event = ob.eval_stop_event = nullptr;
+  ob.eval_ms_out = nullptr;
+  ob.item_ready = nullptr;
+  if (o.eval_start_event &&
+      (e = hipEventRecord((hipEvent_t)o.eval_start_event, st)) != hipSuccess)
+    return hip_fail(e, "cwq_greedy_encode_uniform_var (event)");
+  int64_t end = nb;  // the buckets lie in ascending order of bits: walk them from the top
+  for (int b = CWQ_MAX_BITS_PER_STEP; b >= 0; --b) {
+    const int64_t c = counts[b];
+    if (c == 0) continue;
+    const int64_t r0 = end - c;
+    end = r0;
+    rc = encode_impl(tl_s + r0 * d, ts_s + r0 * d, pl_s + r0 * d, ps_s + r0 * d, nullptr, d, c,
+                     c * d, d, b, n_steps, seed, rho, block_id_base, out_idx + r0 * n_steps,
+                     sample_s + r0 * d, w + l.enc, l.enc_bytes, &ob, stream, seeds_s + r0);
+    if (rc) return rc;
+  }
+  if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
+    return hip_fail(e, "cwq_greedy_encode_uniform_var (event)");
+  int32_t* stage = (int32_t*)(w + l.stage);
+  e = hipMemcpyAsync(stage, out_idx, (size_t)nb * n_steps * 4, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess)
+    e = cwq::launch_vb_scatter(sample_s, stage, perm, nb, d, n_steps, out_sample, out_idx, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (scatter)");
+  return ok();
+}
+
+size_t cwq_pack_indices_var_workspace_size(int64_t nb) {
+  if (nb < 0 || nb > INT32_MAX) return 0;
+  return pack_layout(nb).total;
+}
+
+int cwq_pack_indices_var(const int32_t* idx, const int32_t* n_bits, int64_t nb, int n_steps,
+                         uint8_t* out_bytes, int64_t out_cap, int64_t* total_bits_dev,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  int rc;
+  if ((rc = check_var_nb(nb))) return rc;
+  if (n_steps < 1) return fail(CWQ_ERR_INVALID, "n_steps=%d must be >= 1", n_steps);
+  if (out_cap < 0) return fail(CWQ_ERR_INVALID, "out_cap must be >= 0");
+  if (nb == 0) return ok();  // an empty stream: nothing is written, the total included
+  if (!idx || !n_bits || !total_bits_dev || (out_cap > 0 && !out_bytes))
+    return fail(CWQ_ERR_INVALID, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e;
+  const PackWs l = pack_layout(nb);
+  if (workspace_bytes < l.total || !workspace)
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
+                l.total);
+  char* w = (char*)workspace;
+  int64_t* off = (int64_t*)(w + l.off);
+  e = cwq::launch_vb_offsets(n_bits, nb, n_steps, off, (int64_t*)(w + l.partial),
+                             (uint32_t*)(w + l.flag), total_bits_dev, st);
+  if (e == hipSuccess) e = cwq::launch_vb_pack(idx, n_bits, off, nb, n_steps, out_bytes, out_cap, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_pack_indices_var");
+  return ok();
+}
+
+int cwq_unpack_indices_var(const uint8_t* bytes, int64_t n_bytes, const int32_t* n_bits,
+                           int64_t nb, int n_steps, int32_t* idx_out, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  int rc;
+  if ((rc = check_var_nb(nb))) return rc;
+  if (n_steps < 1) return fail(CWQ_ERR_INVALID, "n_steps=%d must be >= 1", n_steps);
+  if (n_bytes < 0) return fail(CWQ_ERR_INVALID, "n_bytes must be >= 0");
+  if (nb == 0) return ok();
+  if (!idx_out || !n_bits || (n_bytes > 0 && !bytes)) return fail(CWQ_ERR_INVALID, "null pointer");
+  const PackWs l = pack_layout(nb);
+  if (workspace_bytes < l.total || !workspace)
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
+                l.total);
+  char* w = (char*)workspace;
+  int64_t* off = (int64_t*)(w + l.off);
+  hipError_t e = cwq::launch_vb_offsets(n_bits, nb, n_steps, off, (int64_t*)(w + l.partial),
+                                        (uint32_t*)(w + l.flag), nullptr, (hipStream_t)stream);
+  if (e == hipSuccess)
+    e = cwq::launch_vb_unpack(bytes, n_bytes, n_bits, off, nb, n_steps, idx_out,
+                              (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_unpack_indices_var");
+  return ok();
+}
+
+// ---------------------------------------------------------------------------
 // The whole grouped greedy coder of one latent tensor in one call
 // (coded_greedy_sampler.py:170-296): device standardise + KL, host grouping,
 // device encode + destandardise, host bitcode.  Two host<->device round trips

@@ -23,6 +23,20 @@ __device__ __forceinline__ float lognorm_of(float t_scale) {
   return kHalfLog2Pi + logf_full(t_scale, kLogTabConst);
 }
 
+// Per-dim KL(a || b) of two Gaussians, TFP <= 0.7 form in float32
+// (coded_greedy_sampler.py:201): k_kl_normal_normal, the grouped coders' prep
+// kernels and k_block_bits (cwq_varbits.hip) all take it from here.
+__device__ __forceinline__ float kl_normal_normal_1(float a_loc, float a_scale, float b_loc,
+                                                    float b_scale) {
+  const float sa2 = a_scale * a_scale;
+  const float sb2 = b_scale * b_scale;
+  const float ratio = sa2 / sb2;
+  const float dl = a_loc - b_loc;
+  const float t1 = (dl * dl) / (2.0f * sb2);
+  const float t2 = 0.5f * ((ratio - 1.0f) - logf_full(ratio, kLogTabConst));
+  return t1 + t2;
+}
+
 __device__ __forceinline__ uint32_t wave_id() {
   return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 }

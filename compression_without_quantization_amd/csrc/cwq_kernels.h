@@ -196,6 +196,47 @@ hipError_t launch_importance_decode_grouped(const int64_t* index, const int64_t*
                                             const float* dst_loc, const float* dst_scale,
                                             float* dst_out, hipStream_t stream);
 
+// ---- uniform blocks with per-block bit budgets (cwq_varbits.hip) ----------
+// bits_out[g] = clamp(ceil(KL_g / ln 2 + extra_bits), min_bits, max_bits), KL_g
+// the float64 sum of block g's float32 per-dim KLs; kl_bits_out (or nullptr):
+// KL_g / ln 2 as float32.
+hipError_t launch_block_bits(const float* q_loc, const float* q_scale, const float* p_loc,
+                             const float* p_scale, int64_t nb, int64_t d, double extra_bits,
+                             int32_t min_bits, int32_t max_bits, int32_t* bits_out,
+                             float* kl_bits_out, hipStream_t stream);
+// Stable counting sort of nb <= 2^31 - 1 blocks by bit count: perm[rank] = g,
+// counts[0..30] the blocks of each count, counts[31] those outside [0, 30]
+// (ranked last).  wg_hist: vb_sort_scratch_bytes(nb) of scratch.
+size_t vb_sort_scratch_bytes(int64_t nb);
+hipError_t launch_vb_sort(const int32_t* bits, int64_t nb, int32_t* perm, uint32_t* wg_hist,
+                          uint32_t* counts, hipStream_t stream);
+// Rows perm[r] of the four inputs to rows r of the sorted copies, and
+// seeds_s[r] = block_seed(seed, block_id_base + perm[r]).
+hipError_t launch_vb_gather(const float* t_loc, const float* t_scale, const float* p_loc,
+                            const float* p_scale, const int32_t* perm, int64_t nb, int64_t d,
+                            int32_t seed, int64_t block_id_base, float* t_loc_s, float* t_scale_s,
+                            float* p_loc_s, float* p_scale_s, int32_t* seeds_s,
+                            hipStream_t stream);
+// Rows r of sample_s (d floats) and idx_s (n_steps int32) to rows perm[r].
+hipError_t launch_vb_scatter(const float* sample_s, const int32_t* idx_s, const int32_t* perm,
+                             int64_t nb, int64_t d, int n_steps, float* out_sample,
+                             int32_t* out_idx, hipStream_t stream);
+// off[0..nb]: exclusive scan of n_steps * bits[g] in block order (a count
+// outside [0, 30] counts as 0 and sets *flag); total_out (or nullptr) receives
+// off[nb], or -1 when the flag is set.  partial: vb_offsets_scratch_bytes(nb).
+size_t vb_offsets_scratch_bytes(int64_t nb);
+hipError_t launch_vb_offsets(const int32_t* bits, int64_t nb, int n_steps, int64_t* off,
+                             int64_t* partial, uint32_t* flag, int64_t* total_out,
+                             hipStream_t stream);
+// The packed stream of idx [nb, n_steps] (binary_io._pack_bits of the joined
+// to_bit_string fields), at most out_cap bytes of it, and its inverse (bytes
+// past n_bytes read as 0).
+hipError_t launch_vb_pack(const int32_t* idx, const int32_t* bits, const int64_t* off, int64_t nb,
+                          int n_steps, uint8_t* out, int64_t out_cap, hipStream_t stream);
+hipError_t launch_vb_unpack(const uint8_t* bytes, int64_t n_bytes, const int32_t* bits,
+                            const int64_t* off, int64_t nb, int n_steps, int32_t* idx,
+                            hipStream_t stream);
+
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);
 hipError_t launch_selftest_screen(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,

@@ -2885,17 +2885,6 @@ __global__ void __launch_bounds__(256) k_standardise(
   }
 }
 
-__device__ __forceinline__ float kl_normal_normal_1(float a_loc, float a_scale, float b_loc,
-                                                    float b_scale) {
-  const float sa2 = a_scale * a_scale;
-  const float sb2 = b_scale * b_scale;
-  const float ratio = sa2 / sb2;
-  const float dl = a_loc - b_loc;
-  const float t1 = (dl * dl) / (2.0f * sb2);
-  const float t2 = 0.5f * ((ratio - 1.0f) - logf_full(ratio, kLogTabConst));
-  return t1 + t2;
-}
-
 __global__ void __launch_bounds__(256) k_kl_normal_normal(
     const float* __restrict__ a_loc, const float* __restrict__ a_scale,
     const float* __restrict__ b_loc, const float* __restrict__ b_scale, int64_t n,

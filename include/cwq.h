@@ -80,8 +80,11 @@ extern "C" {
  *   0.5  CWQ_ERR_ALLOC (host allocation failures are returned, never thrown);
  *        starts_host of the grouped _begin calls is read asynchronously;
  *   0.6  cwq_code_grouped_importance_batch;
- *   0.7  cwq_decode_grouped_greedy_batch, cwq_decode_grouped_importance_batch. */
-#define CWQ_ABI_VERSION ((0 << 16) | 7)
+ *   0.7  cwq_decode_grouped_greedy_batch, cwq_decode_grouped_importance_batch;
+ *   0.8  per-block bit budgets for uniform blocks: cwq_block_bits,
+ *        cwq_greedy_encode_uniform_var, cwq_pack_indices_var,
+ *        cwq_unpack_indices_var and their workspace sizes. */
+#define CWQ_ABI_VERSION ((0 << 16) | 8)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -181,6 +184,72 @@ int cwq_greedy_decode_uniform(const int32_t* idx, const float* p_loc, const floa
                               int64_t nb, int64_t d, int n_bits_per_step, int n_steps,
                               int32_t seed, float rho, int64_t block_id_base, float* out_sample,
                               void* stream);
+
+/* ---- Uniform blocks with a bit budget each ------------------------------- */
+/* The budget of each of nb uniform blocks of dimension d from its KL:
+ *   S_g     = the float64 sum over the block's dims of the float32 per-dim KL
+ *             (the arithmetic of cwq_kl_normal_normal), in dim order;
+ *   bits[g] = clamp(ceil(S_g / log(2.0) + extra_bits), min_bits, max_bits) in
+ *             float64; a non-finite S_g gives max_bits.
+ * 0 <= min_bits <= max_bits <= CWQ_MAX_BITS_PER_STEP.  bits_out: DEVICE int32
+ * [nb]; kl_bits_out: DEVICE float32 [nb] receiving S_g / ln 2, or NULL.  The
+ * reference closes a group at n_bits ln 2 - 1 nats (coded_greedy_sampler.py:
+ * 226), which is extra_bits = 1 / ln 2.  Asynchronous. */
+int cwq_block_bits(const float* q_loc, const float* q_scale, const float* p_loc,
+                   const float* p_scale, int64_t nb, int64_t d, double extra_bits, int min_bits,
+                   int max_bits, int32_t* bits_out, float* kl_bits_out, void* stream);
+
+/* cwq_greedy_encode_uniform with a bit count per block: n_bits is a DEVICE
+ * int32 [nb], and block g is coded exactly as cwq_greedy_encode_uniform codes
+ * it with n_bits_per_step = n_bits[g] (same seed + block_id_base + g, same
+ * opts; the eval events are recorded around all the scoring launches of the
+ * call).  The blocks are sorted by bit count on the device (a stable counting
+ * sort, so launches repeat from run to run), the 32 bucket sizes are copied
+ * to the host, the rows are gathered into sorted order, every non-empty bucket
+ * is coded by one launch sequence of the uniform encoder, highest bit count
+ * first, all on the caller's stream, and the results are scattered back to
+ * block order.  Like the fused grouped calls this one SYNCHRONISES the stream,
+ * once (for the bucket sizes), and is NOT graph-capturable; everything after
+ * that is only enqueued.  A bit count outside [0, CWQ_MAX_BITS_PER_STEP]
+ * returns CWQ_ERR_INVALID, naming how many there are, before anything is
+ * coded or written to the outputs.  nb <= 2^31 - 1; nb == 0 returns CWQ_OK
+ * without touching the device.
+ * Workspace: the sorted copies of the four inputs (16 nb d bytes) and of the
+ * sample, the permutation, the seeds and one uniform encoder workspace, which
+ * the buckets use one after another.  The size function covers n_steps <= 4 d;
+ * a call with more steps needs 4 nb n_steps bytes (rounded up to 256) on top.
+ * There is no decoder of its own: the indices, unpacked where they travel as a
+ * stream, go to cwq_greedy_decode_uniform with n_bits_per_step =
+ * CWQ_MAX_BITS_PER_STEP, which the decoders use only as the indices' range. */
+size_t cwq_greedy_encode_uniform_var_workspace_size(int64_t nb, int64_t d);
+int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                                  const float* p_scale, int64_t nb, int64_t d,
+                                  const int32_t* n_bits, int n_steps, int32_t seed, float rho,
+                                  int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                                  void* workspace, size_t workspace_bytes,
+                                  const cwq_options* opts, void* stream);
+
+/* The indices of such a call as a packed stream, on the device.  Field (g, s),
+ * g < nb, s < n_steps, is idx[g n_steps + s] in n_bits[g] bits, its bit 0
+ * first; the fields follow each other in block order, then step order, and the
+ * stream's bit i lies in byte i / 8 at bit 7 - i % 8, the last byte padded
+ * with zeros: the bytes binary_io.py:76-78 writes for the joined to_bit_string
+ * (:41-53) fields.  Blocks of 0 bits take no room.  idx, n_bits: DEVICE int32.
+ * pack writes the first min(out_cap, ceil(total / 8)) bytes of the stream to
+ * DEVICE out_bytes, never more, and the total bit count to DEVICE
+ * total_bits_dev (-1 when some n_bits[g] lies outside [0, 30]; such a block
+ * takes no room): a caller compares 8 out_cap with it.  unpack reads field
+ * (g, s) back into idx_out[g n_steps + s]; bits past n_bytes read as 0
+ * (cwq_bitcode_to_indices' rule for short codes).  Both are asynchronous and
+ * stream-ordered and allocate nothing; workspace: the blocks' bit offsets.
+ * nb == 0 returns CWQ_OK and writes nothing, total_bits_dev included. */
+size_t cwq_pack_indices_var_workspace_size(int64_t nb);
+int cwq_pack_indices_var(const int32_t* idx, const int32_t* n_bits, int64_t nb, int n_steps,
+                         uint8_t* out_bytes, int64_t out_cap, int64_t* total_bits_dev,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int cwq_unpack_indices_var(const uint8_t* bytes, int64_t n_bytes, const int32_t* n_bits,
+                           int64_t nb, int n_steps, int32_t* idx_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* coded_greedy_sampler.py:198-199: t_loc = (q_loc - p_loc) / p_scale,
  * t_scale = q_scale / p_scale (float32). */
