@@ -26,7 +26,8 @@ from .misc import stateless_normal_sample
 from .pln import ProbabilisticLadderNetwork, build_empirical_dists
 from .parallel import gather_indices, shard_range
 from .streaming import encode_blocks_host
-from .varbits import (block_bits, decode_blocks_var, encode_blocks_var, pack_indices,
+from .varbits import (block_bits, code_grouped_greedy_sample_var, decode_blocks_var,
+                      decode_grouped_greedy_sample_var, encode_blocks_var, pack_indices,
                       unpack_indices)
 
 __all__ = [
@@ -44,4 +45,5 @@ __all__ = [
     "encode_blocks_host", "code_grouped_greedy_sample_batch",
     "decode_grouped_greedy_sample_batch", "decode_grouped_importance_sample_batch",
     "block_bits", "encode_blocks_var", "decode_blocks_var", "pack_indices", "unpack_indices",
+    "code_grouped_greedy_sample_var", "decode_grouped_greedy_sample_var",
 ]

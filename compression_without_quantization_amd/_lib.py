@@ -72,6 +72,12 @@ SIGNATURES = {
     "cwq_greedy_encode_uniform_var": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_int,
                                               c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_size,
                                               c_opts, c_vp]),
+    "cwq_block_bits_csr": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f64, c_int,
+                                   c_int, c_int, c_vp, c_vp, c_vp]),
+    "cwq_greedy_encode_var_workspace_size": (c_size, [c_i64, c_i64, c_i64, c_int]),
+    "cwq_greedy_encode_var": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp,
+                                      c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_size,
+                                      c_opts, c_vp]),
     "cwq_pack_indices_var_workspace_size": (c_size, [c_i64]),
     "cwq_pack_indices_var": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_size,
                                      c_vp]),
@@ -148,7 +154,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 8
+ABI_VERSION = (0 << 16) | 9
 
 _lib = None
 

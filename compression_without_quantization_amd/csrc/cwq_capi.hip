@@ -716,6 +716,180 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
   return ok();
 }
 
+// ---------------------------------------------------------------------------
+// Ragged (CSR) blocks with a bit budget each.  As above, but
+// the sorted layout is ragged too: bucket b's blocks lie in one piece of the
+// sorted arrays, from dim pre[b], with offsets of their own (relative to that
+// dim, cwq::launch_vbc_layout), so each bucket is an ordinary CSR call of
+// encode_impl on shifted pointers -- the way the batched grouped coder hands
+// its chunks over.  (Absolute offsets into unshifted arrays would not do:
+// k_prep_dims covers dims [0, total_dims) and clears the sample there.)
+// ---------------------------------------------------------------------------
+namespace {
+struct VarCsrWs {
+  size_t t_loc, t_scale, p_loc, p_scale, sample, seeds, perm, hist, counts, wgfacts, facts, soff,
+      roff, src, partial, stage, enc, total;
+  size_t enc_bytes;
+};
+VarCsrWs var_csr_layout(int64_t nb, int64_t total_dims, int64_t max_block_dim, int64_t n_steps) {
+  VarCsrWs l;
+  const size_t row = (size_t)total_dims * 4;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes, 256);
+    return at;
+  };
+  l.t_loc = take(row);
+  l.t_scale = take(row);
+  l.p_loc = take(row);
+  l.p_scale = take(row);
+  l.sample = take(row);
+  l.seeds = take((size_t)nb * 4);
+  l.perm = take((size_t)nb * 4);
+  l.hist = take(cwq::vb_sort_scratch_bytes(nb));
+  l.counts = take(32 * 4);
+  l.wgfacts = take(cwq::vbc_facts_scratch_bytes(nb));
+  l.facts = take(sizeof(cwq::VbcFacts));
+  l.soff = take((size_t)(nb + 1) * 8);
+  l.roff = take((size_t)(nb + 33) * 8);
+  l.src = take((size_t)nb * 8);
+  l.partial = take(cwq::vb_offsets_scratch_bytes(nb));
+  l.stage = take((size_t)nb * (size_t)n_steps * 4);
+  l.enc_bytes = ws_layout_csr(nb, total_dims, max_block_dim).total;
+  l.enc = take(l.enc_bytes);
+  l.total = o;
+  return l;
+}
+bool var_csr_sizes_ok(int64_t nb, int64_t total_dims, int64_t max_block_dim, int64_t n_steps) {
+  return nb >= 0 && nb <= INT32_MAX && total_dims >= 0 && total_dims <= INT64_MAX / 1024 &&
+         max_block_dim >= 0 && n_steps >= 1 && (nb == 0 || n_steps <= INT64_MAX / 1024 / nb);
+}
+}  // namespace
+
+int cwq_block_bits_csr(const float* q_loc, const float* q_scale, const float* p_loc,
+                       const float* p_scale, const int64_t* block_off, int64_t nb,
+                       int64_t total_dims, double extra_bits, int n_steps, int min_bits,
+                       int max_bits, int32_t* bits_out, float* kl_bits_out, void* stream) {
+  if (nb < 0 || total_dims < 0) return fail(CWQ_ERR_INVALID, "bad nb / total_dims");
+  if (n_steps < 1) return fail(CWQ_ERR_INVALID, "n_steps=%d must be >= 1", n_steps);
+  if (min_bits < 0 || max_bits > CWQ_MAX_BITS_PER_STEP || min_bits > max_bits)
+    return fail(CWQ_ERR_INVALID, "need 0 <= min_bits=%d <= max_bits=%d <= %d", min_bits, max_bits,
+                CWQ_MAX_BITS_PER_STEP);
+  if (!(extra_bits == extra_bits)) return fail(CWQ_ERR_INVALID, "extra_bits is NaN");
+  if (nb == 0) return ok();
+  if (!bits_out || !block_off || (total_dims > 0 && (!q_loc || !q_scale || !p_loc || !p_scale)))
+    return fail(CWQ_ERR_INVALID, "null pointer");
+  hipError_t e = cwq::launch_block_bits_csr(q_loc, q_scale, p_loc, p_scale, block_off, nb,
+                                            extra_bits, n_steps, min_bits, max_bits, bits_out,
+                                            kl_bits_out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_block_bits_csr");
+  return ok();
+}
+
+size_t cwq_greedy_encode_var_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                            int n_steps) {
+  if (!var_csr_sizes_ok(nb, total_dims, max_block_dim, n_steps)) return 0;
+  return var_csr_layout(nb, total_dims, max_block_dim, n_steps).total;
+}
+
+int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                          const float* p_scale, const int64_t* block_off, int64_t nb,
+                          int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                          int n_steps, int32_t seed, float rho, int64_t block_id_base,
+                          int32_t* out_idx, float* out_sample, void* workspace,
+                          size_t workspace_bytes, const cwq_options* opts, void* stream) {
+  int rc;
+  if ((rc = check_var_nb(nb))) return rc;
+  if (n_steps < 1) return fail(CWQ_ERR_INVALID, "n_steps=%d must be >= 1", n_steps);
+  if (!var_csr_sizes_ok(nb, total_dims, max_block_dim, n_steps))
+    return fail(CWQ_ERR_INVALID, "bad total_dims / max_block_dim / n_steps");
+  cwq_options o;
+  if ((rc = read_options(opts, &o))) return rc;
+  if (nb == 0) return ok();
+  if (!block_off || !n_bits || !out_idx)
+    return fail(CWQ_ERR_INVALID, "block_off / n_bits / out_idx is null");
+  if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
+    return fail(CWQ_ERR_INVALID, "null input/output pointer");
+  const VarCsrWs l = var_csr_layout(nb, total_dims, max_block_dim, n_steps);
+  if (workspace_bytes < l.total || !workspace)
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
+                l.total);
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)workspace;
+  float* tl_s = (float*)(w + l.t_loc);
+  float* ts_s = (float*)(w + l.t_scale);
+  float* pl_s = (float*)(w + l.p_loc);
+  float* ps_s = (float*)(w + l.p_scale);
+  float* sample_s = (float*)(w + l.sample);
+  int32_t* seeds_s = (int32_t*)(w + l.seeds);
+  int32_t* perm = (int32_t*)(w + l.perm);
+  uint32_t* counts_dev = (uint32_t*)(w + l.counts);
+  cwq::VbcFacts* facts_dev = (cwq::VbcFacts*)(w + l.facts);
+  int64_t* soff = (int64_t*)(w + l.soff);
+  int64_t* roff = (int64_t*)(w + l.roff);
+  int64_t* src = (int64_t*)(w + l.src);
+  int32_t* stage = (int32_t*)(w + l.stage);
+  // sort, the buckets' facts, the sorted layout and the sorted copies (all in
+  // the workspace) are enqueued before the host waits for the facts
+  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, (uint32_t*)(w + l.hist), counts_dev, st);
+  if (e == hipSuccess)
+    e = cwq::launch_vbc_layout(n_bits, block_off, perm, nb, counts_dev,
+                               (unsigned long long*)(w + l.wgfacts), facts_dev, seed,
+                               block_id_base, soff, roff, src, seeds_s, (int64_t*)(w + l.partial),
+                               st);
+  if (e == hipSuccess)
+    e = cwq::launch_vbc_gather(t_loc, t_scale, p_loc, p_scale, soff, src, nb, total_dims, tl_s,
+                               ts_s, pl_s, ps_s, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_var (sort / gather)");
+  // the one synchronisation: the buckets' sizes decide the launches
+  cwq::VbcFacts f;
+  e = hipMemcpyAsync(&f, facts_dev, sizeof(f), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_var (facts)");
+  if (f.counts[31] != 0)
+    return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", f.counts[31],
+                (long long)nb, CWQ_MAX_BITS_PER_STEP);
+  if (f.bad_len != 0)
+    return fail(CWQ_ERR_INVALID, "block_off decreases at %lld blocks", (long long)f.bad_len);
+  int64_t sum_dims = 0, longest = 0;
+  for (int b = 0; b <= CWQ_MAX_BITS_PER_STEP; ++b) {
+    sum_dims += f.dims[b];
+    longest = std::max(longest, f.maxd[b]);
+  }
+  if (sum_dims > total_dims)
+    return fail(CWQ_ERR_INVALID, "the blocks hold %lld dims, total_dims=%lld", (long long)sum_dims,
+                (long long)total_dims);
+  if (longest > max_block_dim)
+    return fail(CWQ_ERR_INVALID, "a block holds %lld dims, max_block_dim=%lld",
+                (long long)longest, (long long)max_block_dim);
+  // the eval events go around all the buckets' launches, so each bucket's own
+  // call takes the options without them
+  cwq_options ob = o;
+  ob.eval_start_event = ob.eval_stop_event = nullptr;
+  ob.eval_ms_out = nullptr;
+  ob.item_ready = nullptr;
+  if (o.eval_start_event &&
+      (e = hipEventRecord((hipEvent_t)o.eval_start_event, st)) != hipSuccess)
+    return hip_fail(e, "cwq_greedy_encode_var (event)");
+  for (int b = CWQ_MAX_BITS_PER_STEP; b >= 0; --b) {
+    const int64_t c = f.counts[b];
+    if (c == 0) continue;
+    const int64_t r0 = f.start[b], d0 = f.pre[b];
+    // the bucket's own longest block: short blocks stay off the long-block path
+    rc = encode_impl(tl_s + d0, ts_s + d0, pl_s + d0, ps_s + d0, roff + r0 + b, 0, c, f.dims[b],
+                     f.maxd[b], b, n_steps, seed, rho, block_id_base, stage + r0 * n_steps,
+                     sample_s + d0, w + l.enc, l.enc_bytes, &ob, stream, seeds_s + r0);
+    if (rc) return rc;
+  }
+  if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
+    return hip_fail(e, "cwq_greedy_encode_var (event)");
+  e = cwq::launch_vbc_scatter(sample_s, stage, soff, src, perm, nb, total_dims, n_steps,
+                              out_sample, out_idx, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_var (scatter)");
+  return ok();
+}
+
 size_t cwq_pack_indices_var_workspace_size(int64_t nb) {
   if (nb < 0 || nb > INT32_MAX) return 0;
   return pack_layout(nb).total;

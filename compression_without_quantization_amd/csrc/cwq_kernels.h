@@ -237,6 +237,47 @@ hipError_t launch_vb_unpack(const uint8_t* bytes, int64_t n_bytes, const int32_t
                             const int64_t* off, int64_t nb, int n_steps, int32_t* idx,
                             hipStream_t stream);
 
+// ---- ragged (CSR) blocks with per-block bit budgets (cwq_varbits.hip) -----
+// bits_out[g] = clamp(ceil((KL_g / ln 2 + extra_bits) / n_steps), min_bits,
+// max_bits) of block g = dims [block_off[g], block_off[g + 1]).
+hipError_t launch_block_bits_csr(const float* q_loc, const float* q_scale, const float* p_loc,
+                                 const float* p_scale, const int64_t* block_off, int64_t nb,
+                                 double extra_bits, int n_steps, int32_t min_bits,
+                                 int32_t max_bits, int32_t* bits_out, float* kl_bits_out,
+                                 hipStream_t stream);
+// What the host reads back (one copy) to launch the buckets of a sorted CSR
+// call: bucket b holds the sorted rows [start[b], start[b] + counts[b]), their
+// dims[b] dims lie at [pre[b], pre[b] + dims[b]) of the sorted arrays, and none
+// of its blocks is longer than maxd[b].  bad_len: blocks of negative length
+// (they count as empty everywhere).
+struct VbcFacts {
+  int64_t dims[32], maxd[32], pre[32];
+  uint32_t counts[32], start[32];
+  int64_t bad_len;
+};
+// The sorted layout, from the sort's perm and counts: the facts; soff[0..nb]
+// the exclusive scan of the block lengths in sorted order; roff [nb + 33]:
+// bucket b's own offsets, relative to its first dim, with a terminator of its
+// own, at roff + start[b] + b (counts[b] + 1 entries); src[r] =
+// block_off[perm[r]]; seeds[r] = block_seed(seed, block_id_base + perm[r]).
+// wg: vbc_facts_scratch_bytes(nb); partial: vb_offsets_scratch_bytes(nb).
+size_t vbc_facts_scratch_bytes(int64_t nb);
+hipError_t launch_vbc_layout(const int32_t* bits, const int64_t* block_off, const int32_t* perm,
+                             int64_t nb, const uint32_t* counts, unsigned long long* wg,
+                             VbcFacts* facts, int32_t seed, int64_t block_id_base, int64_t* soff,
+                             int64_t* roff, int64_t* src, int32_t* seeds, int64_t* partial,
+                             hipStream_t stream);
+// Sorted dim i of row r (soff[r] <= i < soff[r + 1]) is dim src[r] + i - soff[r]
+// of the caller's arrays.  Nothing at or past sorted dim cap is touched.
+hipError_t launch_vbc_gather(const float* t_loc, const float* t_scale, const float* p_loc,
+                             const float* p_scale, const int64_t* soff, const int64_t* src,
+                             int64_t nb, int64_t cap, float* t_loc_s, float* t_scale_s,
+                             float* p_loc_s, float* p_scale_s, hipStream_t stream);
+hipError_t launch_vbc_scatter(const float* sample_s, const int32_t* idx_s, const int64_t* soff,
+                              const int64_t* src, const int32_t* perm, int64_t nb, int64_t cap,
+                              int n_steps, float* out_sample, int32_t* out_idx,
+                              hipStream_t stream);
+
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);
 hipError_t launch_selftest_screen(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,

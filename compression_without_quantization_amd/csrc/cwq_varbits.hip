@@ -8,6 +8,12 @@
 // bit offsets, k_vb_pack, k_vb_unpack).  Nothing here scores a candidate: the
 // blocks of one budget are coded by the existing launch_encode.
 //
+// Ragged (CSR) blocks reuse the sort and the stream and add
+// their own budgets (k_block_bits_csr), the sorted ragged layout with the facts
+// the host needs to launch each bucket (k_vbc_tile / k_vbc_reduce /
+// k_vbc_soff_final) and a segmented gather and scatter (k_vbc_gather,
+// k_vbc_scatter).
+//
 // Every result is reproducible: the only atomics are integer LDS adds of a
 // histogram, all global writes are plain vector stores.
 #include <hip/hip_runtime.h>
@@ -428,6 +434,217 @@ __global__ void __launch_bounds__(kVbThreads) k_vb_unpack(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Ragged (CSR) blocks, DESIGN.md 4d.  Block g is dims [block_off[g],
+// block_off[g + 1]); a negative length counts as 0 everywhere (and is reported
+// through VbcFacts::bad_len).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int64_t vbc_len(const int64_t* __restrict__ off, int64_t g) {
+  const int64_t d = off[g + 1] - off[g];
+  return d > 0 ? d : 0;
+}
+
+// The budget of each ragged block.  A wave per block: the lanes compute 64
+// dims' float32 KLs at once, the float64 sum then takes them in dim order
+// (every lane keeps the same sum), which is k_block_bits's arithmetic without
+// one lane walking a 4,095-dim group alone.
+__global__ void __launch_bounds__(kVbThreads) k_block_bits_csr(
+    const float* __restrict__ q_loc, const float* __restrict__ q_scale,
+    const float* __restrict__ p_loc, const float* __restrict__ p_scale,
+    const int64_t* __restrict__ block_off, int64_t nb, double extra_bits, double n_steps,
+    int32_t min_bits, int32_t max_bits, int32_t* __restrict__ bits_out,
+    float* __restrict__ kl_bits_out) {
+  constexpr int kWaves = kVbThreads / 64;
+  const int lane = threadIdx.x & 63;
+  for (int64_t g = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); g < nb;
+       g += (int64_t)gridDim.x * kWaves) {  // wave-uniform
+    const int64_t o = block_off[g];
+    const int64_t d = vbc_len(block_off, g);
+    double S = 0.0;
+    for (int64_t j0 = 0; j0 < d; j0 += 64) {
+      const int64_t j = j0 + lane;
+      float v = 0.0f;
+      if (j < d) v = kl_normal_normal_1(q_loc[o + j], q_scale[o + j], p_loc[o + j], p_scale[o + j]);
+      const int n = d - j0 < 64 ? (int)(d - j0) : 64;
+#pragma unroll
+      for (int k = 0; k < 64; ++k)
+        if (k < n) S = S + (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+    }
+    const double kl_bits = S / 0.6931471805599453;  // log(2.0)
+    int32_t b = max_bits;                           // a non-finite sum: the most we may spend
+    if (S - S == 0.0) {
+      const double v = ceil((kl_bits + extra_bits) / n_steps);
+      b = v < (double)min_bits ? min_bits : (v > (double)max_bits ? max_bits : (int32_t)v);
+    }
+    if (lane == 0) {
+      bits_out[g] = b;
+      if (kl_bits_out) kl_bits_out[g] = (float)kl_bits;
+    }
+  }
+}
+
+// Per bucket: the dims it holds and its longest block; per tile of the sorted
+// order: its dims.  Workgroup w covers the sorted rows [w kVbTile, (w + 1)
+// kVbTile) and writes wg[w][0..31] (dims by bucket), wg[w][32..63] (longest),
+// wg[w][64] (blocks of negative length) and wg[w][65] (the tile's dims):
+// integer LDS atomics only.
+constexpr int kVbcFactsRow = 2 * kVbBins + 2;
+
+__global__ void __launch_bounds__(kVbThreads) k_vbc_tile(const int32_t* __restrict__ bits,
+                                                         const int64_t* __restrict__ block_off,
+                                                         const int32_t* __restrict__ perm,
+                                                         int64_t nb,
+                                                         unsigned long long* __restrict__ wg) {
+  __shared__ unsigned long long h[kVbcFactsRow];
+  if (threadIdx.x < kVbcFactsRow) h[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * kVbTile;
+  for (int i = threadIdx.x; i < kVbTile; i += kVbThreads) {
+    const int64_t r = r0 + i;
+    if (r < nb) {
+      const int64_t g = perm[r];
+      const int bin = vb_bin(bits[g]);
+      if (block_off[g + 1] < block_off[g]) atomicAdd(&h[2 * kVbBins], 1ull);
+      const unsigned long long d = (unsigned long long)vbc_len(block_off, g);
+      atomicAdd(&h[bin], d);
+      atomicMax(&h[kVbBins + bin], d);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int b = 0; b < kVbBins; ++b) t += h[b];
+    h[2 * kVbBins + 1] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < kVbcFactsRow)
+    wg[(int64_t)blockIdx.x * kVbcFactsRow + threadIdx.x] = h[threadIdx.x];
+}
+
+// One workgroup: the tiles' rows to the call's facts, with the buckets' first
+// rows and first dims (exclusive scans over the 32 buckets), and the tiles'
+// dims to their exclusive scan partial[] (k_vb_off_scan's loop), the total to
+// off_end (soff[nb]).
+__global__ void __launch_bounds__(kVbThreads) k_vbc_reduce(
+    const unsigned long long* __restrict__ wg, int64_t nwg, const uint32_t* __restrict__ counts,
+    VbcFacts* __restrict__ facts, int64_t* __restrict__ partial, int64_t* __restrict__ off_end) {
+  __shared__ unsigned long long acc[kVbcFactsRow];
+  __shared__ int64_t lds[kVbThreads];
+  const int c = threadIdx.x;
+  if (c <= 2 * kVbBins) {
+    const bool is_max = c >= kVbBins && c < 2 * kVbBins;
+    unsigned long long a = 0;
+    for (int64_t w = 0; w < nwg; ++w) {
+      const unsigned long long v = wg[w * kVbcFactsRow + c];
+      a = is_max ? (v > a ? v : a) : a + v;
+    }
+    acc[c] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t pre = 0;
+    uint32_t start = 0;
+    for (int b = 0; b < kVbBins; ++b) {
+      facts->dims[b] = (int64_t)acc[b];
+      facts->maxd[b] = (int64_t)acc[kVbBins + b];
+      facts->pre[b] = pre;
+      facts->counts[b] = counts[b];
+      facts->start[b] = start;
+      pre += (int64_t)acc[b];
+      start += counts[b];
+    }
+    facts->bad_len = (int64_t)acc[2 * kVbBins];
+  }
+  int64_t carry = 0;
+  for (int64_t c0 = 0; c0 < nwg; c0 += kVbThreads) {
+    const int64_t w = c0 + threadIdx.x;
+    const int64_t v = w < nwg ? (int64_t)wg[w * kVbcFactsRow + 2 * kVbBins + 1] : 0;
+    const int64_t incl = wg_incl_scan(v, lds);
+    if (w < nwg) partial[w] = carry + incl - v;
+    lds[threadIdx.x] = incl;
+    __syncthreads();
+    carry += lds[kVbThreads - 1];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *off_end = carry;
+}
+
+// Sorted offsets: each tile's own scan of the lengths in sorted order on top
+// of its base (k_vb_off_final's pattern), and everything else a row needs.
+__global__ void __launch_bounds__(kVbThreads) k_vbc_soff_final(
+    const int32_t* __restrict__ bits, const int64_t* __restrict__ block_off,
+    const int32_t* __restrict__ perm, int64_t nb, const int64_t* __restrict__ partial,
+    const VbcFacts* __restrict__ facts, int32_t seed, int64_t block_id_base,
+    int64_t* __restrict__ soff, int64_t* __restrict__ roff, int64_t* __restrict__ src,
+    int32_t* __restrict__ seeds) {
+  __shared__ int64_t lds[kVbThreads];
+  const int64_t r0 = (int64_t)blockIdx.x * kVbTile + (int64_t)threadIdx.x * kVbPerThread;
+  int64_t len[kVbPerThread];
+  int64_t sum = 0;
+#pragma unroll
+  for (int k = 0; k < kVbPerThread; ++k) {
+    len[k] = r0 + k < nb ? vbc_len(block_off, perm[r0 + k]) : 0;
+    sum += len[k];
+  }
+  int64_t run = partial[blockIdx.x] + wg_incl_scan(sum, lds) - sum;
+#pragma unroll
+  for (int k = 0; k < kVbPerThread; ++k) {
+    const int64_t r = r0 + k;
+    if (r < nb) {
+      const int64_t g = perm[r];
+      const int bin = vb_bin(bits[g]);
+      const int64_t pre = facts->pre[bin];
+      soff[r] = run;
+      roff[r + bin] = run - pre;
+      if (r + 1 == (int64_t)facts->start[bin] + facts->counts[bin])  // the bucket's last row
+        roff[r + bin + 1] = run + len[k] - pre;
+      src[r] = block_off[g];
+      seeds[r] = block_seed(seed, block_id_base + g);
+    }
+    run += len[k];
+  }
+}
+
+// Segmented gather and scatter: a thread per sorted dim finds its row by binary
+// search in soff (rows of 0 dims share their successor's offset and are never
+// found).
+__global__ void __launch_bounds__(kVbThreads) k_vbc_gather(
+    const float* __restrict__ a0, const float* __restrict__ a1, const float* __restrict__ a2,
+    const float* __restrict__ a3, const int64_t* __restrict__ soff,
+    const int64_t* __restrict__ src, int64_t nb, int64_t cap, float* __restrict__ o0,
+    float* __restrict__ o1, float* __restrict__ o2, float* __restrict__ o3) {
+  const int64_t total = soff[nb] < cap ? soff[nb] : cap;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = vb_last_le(soff, nb + 1, i);  // < nb: soff[nb] > i
+    const int64_t s = src[r] + (i - soff[r]);
+    o0[i] = a0[s];
+    o1[i] = a1[s];
+    o2[i] = a2[s];
+    o3[i] = a3[s];
+  }
+}
+
+__global__ void __launch_bounds__(kVbThreads) k_vbc_scatter(
+    const float* __restrict__ sample_s, const int32_t* __restrict__ idx_s,
+    const int64_t* __restrict__ soff, const int64_t* __restrict__ src,
+    const int32_t* __restrict__ perm, int64_t nb, int64_t cap, int64_t n_steps,
+    float* __restrict__ out_sample, int32_t* __restrict__ out_idx) {
+  const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t total = soff[nb] < cap ? soff[nb] : cap;
+  for (int64_t i = t0; i < total; i += stride) {
+    const int64_t r = vb_last_le(soff, nb + 1, i);
+    out_sample[src[r] + (i - soff[r])] = sample_s[i];
+  }
+  const int64_t ni = nb * n_steps;
+  for (int64_t i = t0; i < ni; i += stride) {
+    int64_t r, s;
+    vb_row_of(i, n_steps, r, s);
+    out_idx[(int64_t)perm[r] * n_steps + s] = idx_s[i];
+  }
+}
+
 bool aligned16_all(const void* a, const void* b, const void* c, const void* d) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) == 0;
 }
@@ -542,6 +759,61 @@ hipError_t launch_vb_unpack(const uint8_t* bytes, int64_t n_bytes, const int32_t
   hipLaunchKernelGGL(k_vb_unpack, dim3(grid_for(nb * n_steps, kVbThreads, 1u << 20)),
                      dim3(kVbThreads), 0, stream, bytes, n_bytes, bits, off, nb, (int64_t)n_steps,
                      idx);
+  return hipGetLastError();
+}
+
+hipError_t launch_block_bits_csr(const float* q_loc, const float* q_scale, const float* p_loc,
+                                 const float* p_scale, const int64_t* block_off, int64_t nb,
+                                 double extra_bits, int n_steps, int32_t min_bits,
+                                 int32_t max_bits, int32_t* bits_out, float* kl_bits_out,
+                                 hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_block_bits_csr, dim3(grid_for(nb, kVbThreads / 64, 65536)),
+                     dim3(kVbThreads), 0, stream, q_loc, q_scale, p_loc, p_scale, block_off, nb,
+                     extra_bits, (double)n_steps, min_bits, max_bits, bits_out, kl_bits_out);
+  return hipGetLastError();
+}
+
+size_t vbc_facts_scratch_bytes(int64_t nb) { return (size_t)vb_tiles(nb) * kVbcFactsRow * 8; }
+
+hipError_t launch_vbc_layout(const int32_t* bits, const int64_t* block_off, const int32_t* perm,
+                             int64_t nb, const uint32_t* counts, unsigned long long* wg,
+                             VbcFacts* facts, int32_t seed, int64_t block_id_base, int64_t* soff,
+                             int64_t* roff, int64_t* src, int32_t* seeds, int64_t* partial,
+                             hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  if (nb > 0x7fffffff) return hipErrorInvalidValue;
+  const int64_t nwg = vb_tiles(nb);
+  hipLaunchKernelGGL(k_vbc_tile, dim3((unsigned)nwg), dim3(kVbThreads), 0, stream, bits,
+                     block_off, perm, nb, wg);
+  hipLaunchKernelGGL(k_vbc_reduce, dim3(1), dim3(kVbThreads), 0, stream,
+                     (const unsigned long long*)wg, nwg, counts, facts, partial, soff + nb);
+  hipLaunchKernelGGL(k_vbc_soff_final, dim3((unsigned)nwg), dim3(kVbThreads), 0, stream, bits,
+                     block_off, perm, nb, (const int64_t*)partial, (const VbcFacts*)facts, seed,
+                     block_id_base, soff, roff, src, seeds);
+  return hipGetLastError();
+}
+
+hipError_t launch_vbc_gather(const float* t_loc, const float* t_scale, const float* p_loc,
+                             const float* p_scale, const int64_t* soff, const int64_t* src,
+                             int64_t nb, int64_t cap, float* t_loc_s, float* t_scale_s,
+                             float* p_loc_s, float* p_scale_s, hipStream_t stream) {
+  if (nb <= 0 || cap <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_vbc_gather, dim3(grid_for(cap, kVbThreads, 1u << 20)), dim3(kVbThreads), 0,
+                     stream, t_loc, t_scale, p_loc, p_scale, soff, src, nb, cap, t_loc_s,
+                     t_scale_s, p_loc_s, p_scale_s);
+  return hipGetLastError();
+}
+
+hipError_t launch_vbc_scatter(const float* sample_s, const int32_t* idx_s, const int64_t* soff,
+                              const int64_t* src, const int32_t* perm, int64_t nb, int64_t cap,
+                              int n_steps, float* out_sample, int32_t* out_idx,
+                              hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  const int64_t work = cap > nb * n_steps ? cap : nb * n_steps;
+  hipLaunchKernelGGL(k_vbc_scatter, dim3(grid_for(work, kVbThreads, 1u << 20)), dim3(kVbThreads),
+                     0, stream, sample_s, idx_s, soff, src, perm, nb, cap, (int64_t)n_steps,
+                     out_sample, out_idx);
   return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-"""Uniform blocks with a bit budget of their own, and their packed bitstream.
+"""Blocks (uniform or CSR) with a bit budget of their own, and their packed bitstream.
 
 ``encode_blocks`` spends one ``n_bits_per_step`` on every block of a call.
 Rows of real latents differ in KL, and a greedy coder needs about KL_g bits
@@ -11,8 +11,12 @@ for row g, so here every block carries its own count:
   pack_indices        the indices as the bytes binary_io writes for their
   unpack_indices      joined to_bit_string fields, made and read on the device
   decode_blocks_var   the inverse of encode_blocks_var, from indices or bytes
+  code_grouped_greedy_sample_var / decode_grouped_greedy_sample_var
+                      the grouped coder with a budget per group
 
-The bit counts are side information the caller ships (5 bits per block raw).
+Every entry takes uniform blocks (``block_dim``) or ragged ones (``block_off``,
+nb + 1 offsets: cwq_block_bits_csr, cwq_greedy_encode_var), exactly one of the
+two.  The bit counts are side information the caller ships (5 bits per block raw).
 All arithmetic runs in libcwq.so; nothing here computes samples on the CPU.
 """
 import math
@@ -21,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .coded_greedy_sampler import _device_of, _f32, _ptr
+from .coded_greedy_sampler import _device_of, _dist_parts, _f32, _group_starts_array, _ptr
 
 MAX_BITS = 30  # CWQ_MAX_BITS_PER_STEP
 
@@ -59,14 +63,34 @@ def _nb_of(D, block_dim):
     return block_dim, (D // block_dim if block_dim else 0)
 
 
-def block_bits(post_loc, post_scale, prior_loc, prior_scale, block_dim,
+def _offsets(block_off, D, dev):
+    """``block_off`` checked as encode_blocks checks it: (device int64 tensor,
+    nb, longest block)."""
+    offs_h = np.asarray(block_off.cpu() if isinstance(block_off, torch.Tensor)
+                        else block_off, dtype=np.int64).reshape(-1)
+    nb = offs_h.size - 1
+    if nb < 0 or offs_h[0] != 0 or offs_h[-1] != D or (np.diff(offs_h) < 0).any():
+        raise ValueError("block_off must be non-decreasing from 0 to D")
+    longest = int(np.diff(offs_h).max()) if nb > 0 else 0
+    return torch.from_numpy(offs_h).to(dev), nb, longest
+
+
+def _one_of(block_dim, block_off):
+    if (block_dim is None) == (block_off is None):
+        raise ValueError("give exactly one of block_dim / block_off")
+
+
+def block_bits(post_loc, post_scale, prior_loc, prior_scale, block_dim=None,
                extra_bits=1.0 / math.log(2.0), min_bits=0, max_bits=MAX_BITS,
-               return_kl_bits=False):
+               return_kl_bits=False, block_off=None, n_steps=1):
     """The bit budget of each uniform block of ``block_dim`` dims:
     ``clamp(ceil(KL_g / ln 2 + extra_bits), min_bits, max_bits)`` with KL_g the
     float64 sum of the block's float32 per-dim KL(post || prior); a non-finite
     KL_g gives ``max_bits``.  The default margin is the reference's: it closes
     a group at ``n_bits ln 2 - 1`` nats (coded_greedy_sampler.py:226).
+    With ``block_off`` (nb + 1 offsets) the blocks are ragged and the budget is
+    per step of a code of ``n_steps`` steps:
+    ``clamp(ceil((KL_g / ln 2 + extra_bits) / n_steps), min_bits, max_bits)``.
     Returns an int32 cuda tensor [nb] (with ``return_kl_bits`` also KL_g / ln 2
     as float32 [nb], for logging)."""
     lib = _lib.load()
@@ -78,13 +102,25 @@ def block_bits(post_loc, post_scale, prior_loc, prior_scale, block_dim,
     D = ql.numel()
     if not (qs.numel() == pl.numel() == ps.numel() == D):
         raise ValueError("post_loc, post_scale, prior_loc, prior_scale must have the same size")
-    block_dim, nb = _nb_of(D, block_dim)
+    _one_of(block_dim, block_off)
+    if block_off is not None:
+        offs, nb, _ = _offsets(block_off, D, dev)
+    else:
+        if int(n_steps) != 1:
+            raise ValueError("n_steps applies to block_off (ragged blocks) only")
+        block_dim, nb = _nb_of(D, block_dim)
     bits = torch.empty(nb, dtype=torch.int32, device=dev)
     klb = torch.empty(nb, dtype=torch.float32, device=dev) if return_kl_bits else None
     with torch.cuda.device(dev):
-        rc = lib.cwq_block_bits(_ptr(ql), _ptr(qs), _ptr(pl), _ptr(ps), nb, block_dim,
-                                float(extra_bits), int(min_bits), int(max_bits), _ptr(bits),
-                                _ptr(klb), torch.cuda.current_stream(dev).cuda_stream)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if block_off is not None:
+            rc = lib.cwq_block_bits_csr(_ptr(ql), _ptr(qs), _ptr(pl), _ptr(ps), offs.data_ptr(),
+                                        nb, D, float(extra_bits), int(n_steps), int(min_bits),
+                                        int(max_bits), _ptr(bits), _ptr(klb), stream)
+        else:
+            rc = lib.cwq_block_bits(_ptr(ql), _ptr(qs), _ptr(pl), _ptr(ps), nb, block_dim,
+                                    float(extra_bits), int(min_bits), int(max_bits), _ptr(bits),
+                                    _ptr(klb), stream)
     _lib.check(rc, "cwq_block_bits")
     return (bits, klb) if return_kl_bits else bits
 
@@ -100,8 +136,10 @@ def encode_var_workspace_bytes(nb, block_dim, n_steps=1):
 
 def encode_blocks_var(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, rho=1.,
                       block_dim=None, block_id_base=0, out_idx=None, out_sample=None,
-                      workspace=None, prune_mode=None, eval_events=None):
-    """encode_blocks over uniform blocks of ``block_dim`` with a bit count per
+                      workspace=None, prune_mode=None, eval_events=None, block_off=None,
+                      max_block_dim=None):
+    """encode_blocks over uniform blocks of ``block_dim``, or ragged blocks
+    ``block_off`` (nb + 1 offsets), with a bit count per
     block: block g is coded exactly as ``encode_blocks(..., n_bits[g], ...)``
     codes it (seed ``seed + block_id_base + g``).  ``n_bits``: int tensor,
     array or list of nb counts in [0, 30].  Returns (idx int32 [nb, n_steps],
@@ -109,8 +147,7 @@ def encode_blocks_var(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, rho
     bucket sizes decide its launches), so it cannot be captured into a graph.
     """
     lib = _lib.load()
-    if block_dim is None:
-        raise ValueError("encode_blocks_var needs block_dim (uniform blocks)")
+    _one_of(block_dim, block_off)
     dev = _device_of(t_loc, t_scale, p_loc, p_scale)
     tl = _f32(t_loc, dev, "t_loc")
     ts = _f32(t_scale, dev, "t_scale")
@@ -119,17 +156,34 @@ def encode_blocks_var(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, rho
     D = tl.numel()
     if not (ts.numel() == pl.numel() == ps.numel() == D):
         raise ValueError("t_loc, t_scale, p_loc, p_scale must have the same size")
-    block_dim, nb = _nb_of(D, block_dim)
+    if block_off is not None:
+        offs, nb, longest = _offsets(block_off, D, dev)
+        if max_block_dim is None:
+            max_block_dim = longest
+    else:
+        block_dim, nb = _nb_of(D, block_dim)
     bits = _bits_tensor(n_bits, nb, dev)
     n_steps = int(n_steps)
     if out_idx is None:
         out_idx = torch.empty((nb, n_steps), dtype=torch.int32, device=dev)
     if out_sample is None:
         out_sample = torch.empty(D, dtype=torch.float32, device=dev)
-    need = encode_var_workspace_bytes(nb, block_dim, n_steps)
+    if block_off is not None:
+        need = int(lib.cwq_greedy_encode_var_workspace_size(nb, D, int(max_block_dim), n_steps))
+    else:
+        need = encode_var_workspace_bytes(nb, block_dim, n_steps)
     if workspace is None:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
     opts = _lib.options(prune_mode, eval_events)
+    if block_off is not None:
+        with torch.cuda.device(dev):
+            rc = lib.cwq_greedy_encode_var(
+                _ptr(tl), _ptr(ts), _ptr(pl), _ptr(ps), offs.data_ptr(), nb, D,
+                int(max_block_dim), _ptr(bits), n_steps, _seed32(seed), float(rho),
+                int(block_id_base), _ptr(out_idx), _ptr(out_sample), workspace.data_ptr(),
+                workspace.numel(), opts, torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "cwq_greedy_encode_var")
+        return out_idx, out_sample
     with torch.cuda.device(dev):
         rc = lib.cwq_greedy_encode_uniform_var(
             _ptr(tl), _ptr(ts), _ptr(pl), _ptr(ps), nb, block_dim, _ptr(bits), n_steps,
@@ -212,22 +266,24 @@ def unpack_indices(code, n_bits, n_steps):
 
 
 def decode_blocks_var(code_or_idx, n_bits, p_loc, p_scale, n_steps, seed, rho=1.,
-                      block_dim=None, block_id_base=0, out_sample=None):
+                      block_dim=None, block_id_base=0, out_sample=None, block_off=None):
     """Inverse of encode_blocks_var.  ``code_or_idx``: the packed stream (uint8
     tensor / ndarray, bytes) or the indices themselves (any other integer
     array, nb * n_steps of them).  The decoders use the bit count only as the
-    indices' range, so the unpacked indices go to the plain uniform decoder at
-    the largest count."""
+    indices' range, so the unpacked indices go to the plain uniform (or, with
+    ``block_off``, CSR) decoder at the largest count."""
     lib = _lib.load()
-    if block_dim is None:
-        raise ValueError("decode_blocks_var needs block_dim (uniform blocks)")
+    _one_of(block_dim, block_off)
     dev = _device_of(code_or_idx, p_loc, p_scale)
     pl = _f32(p_loc, dev, "p_loc")
     ps = _f32(p_scale, dev, "p_scale")
     D = pl.numel()
     if ps.numel() != D:
         raise ValueError("p_loc and p_scale must have the same size")
-    block_dim, nb = _nb_of(D, block_dim)
+    if block_off is not None:
+        offs, nb, longest = _offsets(block_off, D, dev)
+    else:
+        block_dim, nb = _nb_of(D, block_dim)
     n_steps = int(n_steps)
     bits = _bits_tensor(n_bits, nb, dev)
     is_code = isinstance(code_or_idx, (bytes, bytearray, memoryview)) or \
@@ -248,9 +304,97 @@ def decode_blocks_var(code_or_idx, n_bits, p_loc, p_scale, n_steps, seed, rho=1.
     if out_sample is None:
         out_sample = torch.empty(D, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.cwq_greedy_decode_uniform(
-            _ptr(it), _ptr(pl), _ptr(ps), nb, block_dim, MAX_BITS, n_steps, _seed32(seed),
-            float(rho), int(block_id_base), _ptr(out_sample),
-            torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "cwq_greedy_decode_uniform")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if block_off is not None:
+            rc = lib.cwq_greedy_decode(
+                _ptr(it), _ptr(pl), _ptr(ps), offs.data_ptr(), nb, D, longest, MAX_BITS, n_steps,
+                _seed32(seed), float(rho), int(block_id_base), _ptr(out_sample), stream)
+        else:
+            rc = lib.cwq_greedy_decode_uniform(
+                _ptr(it), _ptr(pl), _ptr(ps), nb, block_dim, MAX_BITS, n_steps, _seed32(seed),
+                float(rho), int(block_id_base), _ptr(out_sample), stream)
+    _lib.check(rc, "cwq_greedy_decode_uniform" if block_off is None else "cwq_greedy_decode")
     return out_sample
+
+
+# ---------------------------------------------------------------------------
+# the grouped coder with a budget per group (composed from the calls above)
+# ---------------------------------------------------------------------------
+def code_grouped_greedy_sample_var(target, proposal, n_steps, n_bits_per_step, seed,
+                                   max_group_size_bits=12, rho=1.,
+                                   extra_bits=1.0 / math.log(2.0), min_bits=0, prune_mode=None):
+    """code_grouped_greedy_sample with a bit count per group.
+
+    The standardisation, the per-dim KL and the partition are those of
+    code_grouped_greedy_sample (``n_bits_per_step * n_steps`` decides where a
+    group closes); group g is then coded with seed ``seed + g`` at
+    ``block_bits(block_off=starts, n_steps=n_steps, min_bits=min_bits,
+    max_bits=n_bits_per_step)[g]`` bits per step instead of ``n_bits_per_step``,
+    so no group spends more than the reference call, and
+    ``min_bits = n_bits_per_step`` gives its sample and indices exactly.
+    Returns (sample np.float32 [D], code bytes (pack_indices), total_bits,
+    group_start_indices list with D appended, group_bits np.int32 [G]); the
+    decoder needs the last two next to the code.  ``prune_mode``: the encoder's
+    cwq_options.prune_mode; results never depend on it, but groups of thousands
+    of dims at fewer than 12 bits are far faster with ``prune_mode=0``
+    (DESIGN.md 4d).
+    """
+    lib = _lib.load()
+    dev = _device_of(target.loc, target.scale, proposal.loc, proposal.scale)
+    q_loc, q_scale = _dist_parts(target, dev, "Target")
+    p_loc, p_scale = _dist_parts(proposal, dev, "Proposal")
+    D = p_loc.numel()
+    n_steps, n_bits_per_step = int(n_steps), int(n_bits_per_step)
+    t_loc = torch.empty(D, dtype=torch.float32, device=dev)
+    t_scale = torch.empty(D, dtype=torch.float32, device=dev)
+    kl = torch.empty(D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.cwq_standardise(_ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), D,
+                                       _ptr(t_loc), _ptr(t_scale), stream), "cwq_standardise")
+        _lib.check(lib.cwq_kl_normal_normal(_ptr(q_loc), _ptr(q_scale), _ptr(p_loc),
+                                            _ptr(p_scale), D, _ptr(kl), stream),
+                   "cwq_kl_normal_normal")
+    starts = _group_starts_array(kl.cpu().numpy(), n_bits_per_step * n_steps,
+                                 max_group_size_bits)
+    # the budgets sum the float32 per-dim KLs the partition saw (same arithmetic)
+    bits = block_bits(q_loc, q_scale, p_loc, p_scale, block_off=starts, extra_bits=extra_bits,
+                      n_steps=n_steps, min_bits=min_bits, max_bits=n_bits_per_step)
+    zeros = torch.zeros(D, dtype=torch.float32, device=dev)
+    ones = torch.ones(D, dtype=torch.float32, device=dev)
+    idx, sample = encode_blocks_var(t_loc, t_scale, zeros, ones, bits, n_steps, seed, rho=rho,
+                                    block_off=starts, prune_mode=prune_mode)
+    out = torch.empty(D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cwq_destandardise(_ptr(sample), _ptr(p_loc), _ptr(p_scale), D, _ptr(out),
+                                         torch.cuda.current_stream(dev).cuda_stream),
+                   "cwq_destandardise")
+    code, total_bits = pack_indices(idx, bits)
+    return (out.cpu().numpy(), code.cpu().numpy().tobytes(), total_bits, starts.tolist(),
+            bits.cpu().numpy())
+
+
+def decode_grouped_greedy_sample_var(code, group_start_indices, group_bits, proposal, n_steps,
+                                     seed, rho=1.):
+    """Inverse of code_grouped_greedy_sample_var.  Returns np.float32 [D]."""
+    lib = _lib.load()
+    dev = _device_of(proposal.loc, proposal.scale)
+    p_loc, p_scale = _dist_parts(proposal, dev, "Proposal")
+    D = p_loc.numel()
+    G = int(np.asarray(group_bits.cpu() if isinstance(group_bits, torch.Tensor)
+                       else group_bits).size)
+    offs = np.asarray(group_start_indices, dtype=np.int64).reshape(-1)
+    if offs.size == G:  # a list without its end
+        offs = np.append(offs, D)
+    if offs.size != G + 1:
+        raise ValueError(f"{offs.size} group starts for {G} group budgets")
+    zeros = torch.zeros(D, dtype=torch.float32, device=dev)
+    ones = torch.ones(D, dtype=torch.float32, device=dev)
+    sample = decode_blocks_var(code, group_bits, zeros, ones, n_steps, seed, rho=rho,
+                               block_off=offs)
+    out = torch.empty(D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cwq_destandardise(_ptr(sample), _ptr(p_loc), _ptr(p_scale), D, _ptr(out),
+                                         torch.cuda.current_stream(dev).cuda_stream),
+                   "cwq_destandardise")
+    return out.cpu().numpy()

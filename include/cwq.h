@@ -83,8 +83,10 @@ extern "C" {
  *   0.7  cwq_decode_grouped_greedy_batch, cwq_decode_grouped_importance_batch;
  *   0.8  per-block bit budgets for uniform blocks: cwq_block_bits,
  *        cwq_greedy_encode_uniform_var, cwq_pack_indices_var,
- *        cwq_unpack_indices_var and their workspace sizes. */
-#define CWQ_ABI_VERSION ((0 << 16) | 8)
+ *        cwq_unpack_indices_var and their workspace sizes;
+ *   0.9  per-block bit budgets for CSR blocks: cwq_block_bits_csr,
+ *        cwq_greedy_encode_var and its workspace size. */
+#define CWQ_ABI_VERSION ((0 << 16) | 9)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -228,6 +230,56 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
                                   int64_t block_id_base, int32_t* out_idx, float* out_sample,
                                   void* workspace, size_t workspace_bytes,
                                   const cwq_options* opts, void* stream);
+
+/* ---- Ragged (CSR) blocks with a bit budget each --------------------------- */
+/* cwq_block_bits for nb CSR blocks (block g = dims [block_off[g],
+ * block_off[g + 1]), block_off a DEVICE int64 [nb + 1]) of a code of n_steps
+ * steps:
+ *   bits[g] = clamp(ceil((S_g / log(2.0) + extra_bits) / n_steps), min_bits,
+ *             max_bits) in float64,
+ * S_g as above (0 for an empty block; a non-finite S_g gives max_bits), and
+ * kl_bits_out[g] = (float)(S_g / ln 2).  With n_steps = 1 and equal block
+ * lengths this is cwq_block_bits, bit for bit.  total_dims: the length of the
+ * four arrays.  Asynchronous. */
+int cwq_block_bits_csr(const float* q_loc, const float* q_scale, const float* p_loc,
+                       const float* p_scale, const int64_t* block_off, int64_t nb,
+                       int64_t total_dims, double extra_bits, int n_steps, int min_bits,
+                       int max_bits, int32_t* bits_out, float* kl_bits_out, void* stream);
+
+/* cwq_greedy_encode with a bit count per block: n_bits is a DEVICE int32 [nb],
+ * and block g is coded exactly as cwq_greedy_encode codes it with
+ * n_bits_per_step = n_bits[g] (same seed + block_id_base + g, same opts; the
+ * eval events are recorded once, around all the scoring launches of the call).
+ * The blocks are sorted by bit count on the device and gathered, bucket after
+ * bucket, into a ragged sorted layout; the 32 bucket sizes travel to the host
+ * together with each bucket's dims and its longest block, and every non-empty
+ * bucket is coded by one launch sequence of the CSR encoder, highest bit count
+ * first, on the caller's stream, sized by the bucket's own longest block (a
+ * bucket of short blocks takes the short-block kernels whatever max_block_dim
+ * says).  The results are scattered back to block order.  Like
+ * cwq_greedy_encode_uniform_var this call SYNCHRONISES the stream, once, and
+ * is NOT graph-capturable; everything after that is only enqueued.
+ * CWQ_ERR_INVALID, before anything is coded or written to the outputs: a bit
+ * count outside [0, CWQ_MAX_BITS_PER_STEP] (the message names how many), a
+ * decreasing block_off, blocks holding more than total_dims dims or one longer
+ * than max_block_dim.  CWQ_ERR_WORKSPACE: fewer bytes than
+ * cwq_greedy_encode_var_workspace_size(nb, total_dims, max_block_dim, n_steps)
+ * (0 for negative or overflowing arguments): five sorted arrays of total_dims
+ * floats, 40 B per block of layout, the staged indices and one
+ * cwq_greedy_encode workspace for the whole call, which the buckets use one
+ * after another.  nb <= 2^31 - 1; nb == 0 returns CWQ_OK without touching the
+ * device.  There is no decoder of its own: the indices, unpacked where they
+ * travel as a stream, go to cwq_greedy_decode with n_bits_per_step =
+ * CWQ_MAX_BITS_PER_STEP; the CSR decoder reads the count only as the bound
+ * 2^n_bits an index must stay below. */
+size_t cwq_greedy_encode_var_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                            int n_steps);
+int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                          const float* p_scale, const int64_t* block_off, int64_t nb,
+                          int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                          int n_steps, int32_t seed, float rho, int64_t block_id_base,
+                          int32_t* out_idx, float* out_sample, void* workspace,
+                          size_t workspace_bytes, const cwq_options* opts, void* stream);
 
 /* The indices of such a call as a packed stream, on the device.  Field (g, s),
  * g < nb, s < n_steps, is idx[g n_steps + s] in n_bits[g] bits, its bit 0
