@@ -137,6 +137,9 @@ SIGNATURES = {
     "cwq_selftest_logf": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "cwq_selftest_wave_max": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "cwq_selftest_div": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "cwq_selftest_encode_rows_wave": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                              c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp,
+                                              c_size, c_vp]),
     "cwq_pln_posterior": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "cwq_permute_gather": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "cwq_permute_scatter": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
@@ -154,7 +157,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 9
+ABI_VERSION = (0 << 16) | 10
 
 _lib = None
 

@@ -355,7 +355,8 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
                 int64_t block_id_base, int32_t* out_idx, float* out_sample, void* workspace,
                 size_t workspace_bytes, const cwq_options* opts, void* stream,
                 const int32_t* block_seeds = nullptr, float* ds_out = nullptr,
-                const float* ds_loc = nullptr, const float* ds_scale = nullptr) {
+                const float* ds_loc = nullptr, const float* ds_scale = nullptr,
+                bool rows_wave = false) {
   int rc = check_common(n_bits, n_steps, nb);
   if (rc) return rc;
   cwq_options o;
@@ -415,6 +416,7 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
   a.ds_out = ds_out;
   a.ds_loc = ds_loc;
   a.ds_scale = ds_scale;
+  a.rows_wave = rows_wave;
   hipError_t e = cwq::launch_encode(a, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode");
   return ok();
@@ -876,10 +878,20 @@ int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float*
     const int64_t c = f.counts[b];
     if (c == 0) continue;
     const int64_t r0 = f.start[b], d0 = f.pre[b];
+    // Long rows at few candidates: below 4,096 candidates the
+    // other paths walk a row with one lane, so a bucket whose mean block reaches
+    // the length from which rows count as long gives every row to a wave.
+    // prune_mode 0 keeps k_encode_eval, as it promises.
+#ifndef CWQ_VAR_ROWS_WAVE
+#define CWQ_VAR_ROWS_WAVE 1  // 0: every bucket on the paths it took before (A/B builds)
+#endif
+    const bool rows_wave = CWQ_VAR_ROWS_WAVE && b < 12 &&
+                           f.dims[b] >= (int64_t)CWQ_CSR_COOP_MIN_D * c && o.prune_mode != 0;
     // the bucket's own longest block: short blocks stay off the long-block path
     rc = encode_impl(tl_s + d0, ts_s + d0, pl_s + d0, ps_s + d0, roff + r0 + b, 0, c, f.dims[b],
                      f.maxd[b], b, n_steps, seed, rho, block_id_base, stage + r0 * n_steps,
-                     sample_s + d0, w + l.enc, l.enc_bytes, &ob, stream, seeds_s + r0);
+                     sample_s + d0, w + l.enc, l.enc_bytes, &ob, stream, seeds_s + r0, nullptr,
+                     nullptr, nullptr, rows_wave);
     if (rc) return rc;
   }
   if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
@@ -3202,6 +3214,20 @@ int cwq_debug_prune_stats(unsigned long long* out72, int flags) {
   if (r < 0) return fail(CWQ_ERR_HIP, "cwq_debug_prune_stats: symbol copy failed");
   cwq::set_error(CWQ_OK, "");
   return r;
+}
+
+int cwq_selftest_encode_rows_wave(const float* t_loc, const float* t_scale, const float* p_loc,
+                                  const float* p_scale, const int64_t* block_off, int64_t nb,
+                                  int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
+                                  int n_steps, int32_t seed, float rho, int64_t block_id_base,
+                                  int32_t* out_idx, float* out_sample, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  if (nb > 0 && !block_off) return fail(CWQ_ERR_INVALID, "block_off is null");
+  if (max_block_dim < 0) return fail(CWQ_ERR_INVALID, "max_block_dim must be >= 0");
+  return encode_impl(t_loc, t_scale, p_loc, p_scale, block_off, 0, nb, total_dims, max_block_dim,
+                     n_bits_per_step, n_steps, seed, rho, block_id_base, out_idx, out_sample,
+                     workspace, workspace_bytes, nullptr, stream, nullptr, nullptr, nullptr,
+                     nullptr, /*rows_wave=*/true);
 }
 
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream) {

@@ -29,6 +29,12 @@ __host__ __device__ inline int64_t csr_rec_entries(int64_t total_dims) {
   return total_dims + 12 * (total_dims / (CWQ_CSR_LDS_DIMS + 1) + 1);
 }
 
+#ifndef CWQ_CSR_COOP_MIN_D
+#define CWQ_CSR_COOP_MIN_D 256  // rows of at least this many dims count as long: the general
+                                // pruned kernel walks them cooperatively, and a budget bucket
+                                // of this mean length takes k_encode_rows_wave
+#endif
+
 constexpr int kTileQueueSlots = 64;
 
 struct EncodeArgs {
@@ -87,6 +93,9 @@ struct EncodeArgs {
   float* ds_out = nullptr;
   const float* ds_loc = nullptr;
   const float* ds_scale = nullptr;
+  // score every candidate row exactly with a whole wave (k_encode_rows_wave)
+  // instead of any other scoring path; results are those of prune == 0
+  bool rows_wave = false;
 };
 
 #define CWQ_SLIST_PER_BLOCK 8

@@ -918,6 +918,73 @@ __device__ __forceinline__ float exact_row_wave(
   return eigen_fold8(p, __shfl(acc, 8, 64));
 }
 
+// ---------------------------------------------------------------------------
+// Encoder, one step, a wave per candidate row: long blocks at few candidates
+// (per-group bit budgets), where a lane per row leaves most of
+// the chip idle.  Row r = g * n_cand + n of the flattened (block, candidate)
+// list goes to wave r mod W of the grid's W waves; every row is scored exactly
+// by exact_row_wave (k_encode_eval's values bit for bit, no screening), the
+// four keys of a workgroup's iteration are folded through LDS and each block
+// they touch gets one atomicMax.  An empty block gets no key: keys[g] stays 0
+// and k_encode_finalize writes index 0, as after k_encode_eval.
+// ---------------------------------------------------------------------------
+template <bool STEP0>
+__global__ void __launch_bounds__(256) k_encode_rows_wave(
+    const float* __restrict__ t_loc, const float* __restrict__ t_scale,
+    const float* __restrict__ loc_s, const float* __restrict__ scale_s,
+    const float* __restrict__ lognorm, const float* __restrict__ best,
+    const int64_t* __restrict__ block_off, int64_t ud, int64_t nb, int n_bits, SeedSpec sd,
+    int32_t step, unsigned long long* __restrict__ keys) {
+  __shared__ double logtab[32];
+  __shared__ float rowbuf[4][kRowChunk];
+  __shared__ unsigned long long wkey[4];
+  __shared__ int64_t wblk[4];
+  fill_logtab(logtab);
+  const uint32_t wv = wave_id();
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t rows = nb << n_bits;
+  const int64_t cmask = ((int64_t)1 << n_bits) - 1;
+  // the loop is uniform over the workgroup (its barriers) and a wave skips a
+  // row as a whole: exact_row_wave runs with all 64 lanes or not at all
+  for (int64_t r0 = 4 * (int64_t)blockIdx.x; r0 < rows; r0 += 4 * (int64_t)gridDim.x) {
+    const int64_t r = r0 + wv;
+    uint64_t k = 0;
+    int64_t g = -1;
+    if (r < rows) {
+      g = r >> n_bits;
+      const int64_t n = r & cmask;
+      const BlockSpan sp = block_span(block_off, ud, g);
+      if (sp.d > 0) {
+        const PhiloxStream st = generate_key(step_seed(sd.of(g), step), 42);
+        const float v = exact_row_wave<STEP0>(
+            st, (uint64_t)n * (uint64_t)sp.d, sp.d, loc_s + sp.off, scale_s + sp.off,
+            t_loc + sp.off, t_scale + sp.off, lognorm + sp.off,
+            STEP0 ? nullptr : best + sp.off, logtab, rowbuf[wv], lane);
+        k = argmax_key(v, (uint32_t)n);
+      }
+    }
+    if (lane == 0) {
+      wkey[wv] = k;
+      wblk[wv] = g;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+      // wave i's key, folded with those of the later waves on the same block;
+      // the first wave of each block sends it
+      const int i = (int)threadIdx.x;
+      uint64_t m = wkey[i];
+      bool first = true;
+      for (int j = 0; j < 4; ++j) {
+        if (j == i || wblk[j] != wblk[i]) continue;
+        if (j < i) first = false;
+        m = wkey[j] > m ? wkey[j] : m;
+      }
+      if (first && m) atomicMax(&keys[wblk[i]], (unsigned long long)m);
+    }
+    __syncthreads();
+  }
+}
+
 #ifndef CWQ_CSR_GTAU_SHARE
 #define CWQ_CSR_GTAU_SHARE 1  // 1: also share tau with the block's other tiles in the loop
 #endif
@@ -928,8 +995,8 @@ __device__ __forceinline__ float exact_row_wave(
 #define CWQ_CSR_SURVIVOR_CAP 512
 #endif
 #ifndef CWQ_CSR_COOP_ROWS_PER_LANE
-#define CWQ_CSR_COOP_ROWS_PER_LANE 8  // cooperative rows below this many rows per lane ...
-#endif
+#define CWQ_CSR_COOP_ROWS_PER_LANE 8  // cooperative rows below this many rows per lane, for
+#endif                                // blocks of at least CWQ_CSR_COOP_MIN_D dims (cwq_kernels.h)
 #ifndef CWQ_CSR_TILE
 #define CWQ_CSR_TILE 1024             // smallest tile (candidates), per-lane rows
 #endif
@@ -944,9 +1011,6 @@ __device__ __forceinline__ float exact_row_wave(
 #endif
 #ifndef CWQ_CSR_COOP_CLASS_WAVES
 #define CWQ_CSR_COOP_CLASS_WAVES 1    // 1: cooperative rows n = wave (mod 4) per wave
-#endif
-#ifndef CWQ_CSR_COOP_MIN_D
-#define CWQ_CSR_COOP_MIN_D 256        // ... for blocks of at least this many dims
 #endif
 #ifndef CWQ_CSR_COOP_MIN_WAVES
 #define CWQ_CSR_COOP_MIN_WAVES 4      // waves/SIMD the cooperative kernel's registers allow
@@ -3248,7 +3312,7 @@ static bool takes_uniform_pruned(const EncodeArgs& a) {
          a.n_cand * (a.ud / 4) <= (1LL << 32);
 }
 static bool takes_small_path(const EncodeArgs& a) {  // launch_small's d <= 64 shapes
-  return !takes_uniform_pruned(a) && !(a.prune >= 2 && a.sab != nullptr && a.n_cand >= 4096) &&
+  return !a.rows_wave && !takes_uniform_pruned(a) && !(a.prune >= 2 && a.sab != nullptr && a.n_cand >= 4096) &&
          a.prune >= 2 && a.sab != nullptr && a.slist != nullptr && a.ordu != nullptr &&
          a.n_cand >= CWQ_SMALL_MIN_CAND && CWQ_SMALL_FUSED && a.max_d >= 0 &&
          a.max_d <= CWQ_FUSED_DMAX && a.n_cand < 4096;
@@ -3311,10 +3375,26 @@ static bool launch_small(const EncodeArgs& a, int step, hipStream_t stream) {
   return false;
 }
 
+// A wave per candidate row (k_encode_rows_wave): four rows per workgroup
+// iteration, at most CWQ_ROWS_WAVE_WGS workgroups (8 per CU: DESIGN.md 4e).
+#ifndef CWQ_ROWS_WAVE_WGS
+#define CWQ_ROWS_WAVE_WGS (8 * 256)
+#endif
+template <bool STEP0>
+static void launch_rows_wave(const EncodeArgs& a, int step, hipStream_t stream) {
+  int n_bits = 0;
+  while (((int64_t)1 << n_bits) < a.n_cand) ++n_bits;
+  const int64_t rows = a.nb << n_bits;  // nb <= 2^31 and n_bits <= 30 (the C ABI's checks)
+  hipLaunchKernelGGL((k_encode_rows_wave<STEP0>), dim3(grid_for(rows, 4, CWQ_ROWS_WAVE_WGS)),
+                     dim3(256), 0, stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm,
+                     a.out_sample, a.block_off, a.ud, a.nb, n_bits, seeds_of(a), step, a.keys);
+}
+
 // Scoring launches of one step; true when they also finalized it (indices and
 // sample written), false when k_encode_finalize must follow.
 template <bool STEP0>
 static bool launch_eval_dc(const EncodeArgs& a, int step, hipStream_t stream) {
+  if (a.rows_wave) return launch_rows_wave<STEP0>(a, step, stream), false;
   if (takes_uniform_pruned(a)) {
     switch (a.ud) {
       case 8: return launch_prune_t<8, STEP0>(a, step, stream), false;

@@ -51,13 +51,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .binary_io import read_bin_code, write_bin_code
+from .binary_io import _pack_bits, read_bin_code, write_bin_code
 from .coded_greedy_sampler import (Normal, code_grouped_greedy_sample,
                                    decode_grouped_greedy_sample)
 from .coded_importance_sampler import (_kl, code_grouped_importance_sample,
                                        decode_grouped_importance_sample)
 from .coding import ArithmeticCoder
 from .misc import stateless_normal_sample
+from .varbits import code_grouped_greedy_sample_var, decode_grouped_greedy_sample_var
 
 # MIOpen's default find mode benchmarks every convolution solver, the naive
 # reference kernels included, on the first call of each shape: 4.6 s and 19.6 s
@@ -334,11 +335,59 @@ def _as_coder(ac):
     return ArithmeticCoder(_load_counts(ac, 0), precision=32)
 
 
+def _chars_of(code_bytes, n_bits):
+    """The first n_bits bits of a packed code as a '0'/'1' string, MSB first."""
+    flags = np.unpackbits(np.frombuffer(code_bytes, dtype=np.uint8))[:int(n_bits)]
+    return (flags + ord("0")).astype(np.uint8).tobytes().decode("ascii")
+
+
 def _group_differences(starts):
     d = np.diff(np.asarray(starts, dtype=np.int64))
     if d.size and (d <= 0).any():
         raise ValueError("an empty group would be coded as the EOF symbol 0 (pln.py:517-529)")
     return d
+
+
+def _budget_symbols(group_bits, cap):
+    """The level-1 bit budgets as arithmetic-coder symbols: a group of b bits
+    per step (0 <= b <= cap = n_bits_per_step) is symbol cap - b + 1, so the
+    full budget is symbol 1 and symbol 0 stays the EOF."""
+    cap = int(cap)
+    b = np.asarray(group_bits, dtype=np.int64).reshape(-1)
+    if b.size and (int(b.min()) < 0 or int(b.max()) > cap):
+        raise ValueError(f"a group budget lies outside [0, {cap}]")
+    return (cap - b + 1).tolist()
+
+
+def _budgets_from_symbols(symbols, cap):
+    """Inverse of _budget_symbols (np.int32 budgets); a symbol outside
+    [1, cap + 1] is refused."""
+    cap = int(cap)
+    s = np.asarray(symbols, dtype=np.int64).reshape(-1)
+    if s.size and (int(s.min()) < 1 or int(s.max()) > cap + 1):
+        raise ValueError(f"a budget symbol lies outside [1, {cap + 1}]")
+    return (cap + 1 - s).astype(np.int32)
+
+
+def _budget_coder(counts, cap):
+    """The budgets' count model: cap + 2 symbols (EOF, then the budgets cap
+    down to 0), uniform when none is given."""
+    c = _load_counts(counts, int(cap) + 2)
+    if c.size != int(cap) + 2:
+        raise ValueError(f"the budget count model holds {c.size} symbols, "
+                         f"n_bits_per_step + 2 = {int(cap) + 2} are needed")
+    return ArithmeticCoder(c, 32)
+
+
+def _encode_budgets(group_bits, cap, counts=""):
+    """The third variable bit string of a budget file; it must fit the
+    container's 16-bit length field."""
+    symbols = _budget_symbols(group_bits, cap)
+    code = _budget_coder(counts, cap).encode(symbols + [0])
+    if len(code) >= 1 << 16:
+        raise ValueError(f"the budgets of {len(symbols)} level-1 groups take {len(code)} bits: "
+                         "the container's length field holds 16")
+    return code
 
 
 def _kl_sum(q, p):
@@ -475,7 +524,8 @@ class ProbabilisticLadderNetwork(nn.Module):
                           return_first_level_group_sizes=False, return_first_level_indices=False,
                           return_second_level_group_sizes=False,
                           return_second_level_indices=False, verbose=False, *,
-                          capture=None):
+                          capture=None, first_level_group_bits=False, first_level_min_bits=0,
+                          first_level_bits_dist_counts=""):
         """pln.py:213-627.  ``session`` is ignored.  Writes the .miracle file to
         comp_file_path and returns ((sample2, sample1), summaries), or what the
         return_* flags ask for.  Group-size count models are .npy paths or
@@ -485,8 +535,18 @@ class ProbabilisticLadderNetwork(nn.Module):
         ``capture`` (keyword only, not in the reference; bench.py): a dict that
         receives each level's coder inputs (flattened, permuted float32 numpy
         q/p loc and scale) and results under "level2" / "level1", and the
-        coders' candidate-scoring milliseconds under "scoring_ms"."""
+        coders' candidate-scoring milliseconds under "scoring_ms".
+        ``first_level_group_bits`` (keyword only, not in the reference): the
+        greedy level 1 gets a bit budget per group (code_grouped_greedy_sample_var
+        with ``min_bits=first_level_min_bits``), never above n_bits_per_step;
+        the budgets travel as a third variable bit string, arithmetic-coded
+        under ``first_level_bits_dist_counts`` (symbol n_bits_per_step - bits + 1;
+        uniform over n_bits_per_step + 2 symbols when empty).  The decoder must
+        be given the same flag and count model."""
         del session, backfitting_steps_level_1, backfitting_steps_level_2, use_log_prob
+        if first_level_group_bits and use_importance_sampling:
+            raise ValueError("first_level_group_bits needs use_importance_sampling=False: the "
+                             "budgets belong to the greedy level-1 coder")
         if use_index_ac and not use_importance_sampling:
             raise ValueError("use_index_ac needs use_importance_sampling=True: the greedy "
                              "level-1 code is a bit string, not indices")
@@ -561,6 +621,17 @@ class ProbabilisticLadderNetwork(nn.Module):
             if use_index_ac:
                 code1 = ''.join(_as_coder(first_level_sample_ac).encode(list(code1) + [0]))
             outlier_extras1 = [np.asarray(x).reshape(-1) for x in outlier_extras1]
+        elif first_level_group_bits:
+            sample1, code1_bytes, total_bits, group_indices1, group_bits1 = \
+                code_grouped_greedy_sample_var(
+                    q1p, p1p, n_steps, n_bits_per_step, seed,
+                    max_group_size_bits=greedy_max_group_size_bits, rho=rho,
+                    min_bits=first_level_min_bits)
+            code1 = _chars_of(code1_bytes, total_bits)
+            keep("level1", q1p, p1p, (sample1, code1, group_indices1, group_bits1), "greedy_var")
+            if return_first_level_group_sizes:
+                return np.asarray(group_indices1)
+            outlier_extras1 = None
         else:
             sample1, code1, group_indices1 = code_grouped_greedy_sample(
                 None, q1p, p1p, n_steps, n_bits_per_step, seed,
@@ -590,9 +661,14 @@ class ProbabilisticLadderNetwork(nn.Module):
         coder1 = ArithmeticCoder(_load_counts(first_level_group_dist_counts, 1 + 2 ** g1_bits), 32)
         gi1_code = coder1.encode(np.concatenate((group_differences1, [0])))
         gi2_code = coder2.encode(np.concatenate((group_differences2, [0])))
+        extra_var_bits = [gi1_code, gi2_code]
+        if first_level_group_bits:
+            bits1_code = _encode_budgets(group_bits1, n_bits_per_step,
+                                         first_level_bits_dist_counts)
+            extra_var_bits.append(bits1_code)
         if comp_file_path is not None:
             write_bin_code(bitcode, comp_file_path, extras=extras,
-                           extra_var_bits=[gi1_code, gi2_code],
+                           extra_var_bits=extra_var_bits,
                            var_length_extras=var_length_extras, var_length_bits=var_length_bits)
 
         # Step 4: summaries (:543-625)
@@ -603,6 +679,8 @@ class ProbabilisticLadderNetwork(nn.Module):
         npix = shp[1] * shp[2]
         actual = os.path.getsize(comp_file_path) if comp_file_path is not None else None
         extra_bytes = len(gi1_code) + len(gi2_code) + 9 * 2 // 8
+        if first_level_group_bits:
+            extra_bytes += len(bits1_code)
         theo = lambda k: (k + 2 * np.log(k + 1)) / np.log(2) / 8
         summaries = {
             "image_shape": list(shp),
@@ -619,6 +697,10 @@ class ProbabilisticLadderNetwork(nn.Module):
             "first_level_avg_log_lik": _normal_log_prob_mean(q1p, torch.as_tensor(sample1)),
             "second_level_avg_log_lik": _normal_log_prob_mean(q2p, torch.as_tensor(sample2)),
         }
+        if first_level_group_bits:
+            summaries["first_level_code_bits"] = int(total_bits)
+            summaries["first_level_bits_histogram"] = np.bincount(
+                np.asarray(group_bits1, dtype=np.int64), minlength=n_bits_per_step + 1).tolist()
         if verbose:
             for k, v in summaries.items():
                 print("{}: {}".format(k, v))
@@ -640,17 +722,23 @@ class ProbabilisticLadderNetwork(nn.Module):
                             first_level_group_dist_counts="", second_level_sample_ac=None,
                             first_level_sample_ac=None, use_index_ac=False, verbose=False,
                             greedy_max_group_size_bits=12, first_level_max_group_size_bits=3,
-                            second_level_max_group_size_bits=4):
+                            second_level_max_group_size_bits=4, *, first_level_group_bits=False,
+                            first_level_bits_dist_counts=""):
         """pln.py:638-817.  Returns the reconstruction [H, W, 3] (float32 numpy,
         tf.squeeze of the NHWC output).  As in the reference,
         ``use_importance_sampling`` defaults to True and must match the encoder.
-        The *_max_group_size_bits only size the uniform default count models."""
+        The *_max_group_size_bits only size the uniform default count models.
+        ``first_level_group_bits`` / ``first_level_bits_dist_counts`` (keyword
+        only): as given to the encoder; the file does not say which mode wrote
+        it."""
         del session
+        if first_level_group_bits and use_importance_sampling:
+            raise ValueError("first_level_group_bits needs use_importance_sampling=False")
         dev = next(self.parameters()).device
         nvle = 4 if use_importance_sampling else 2
-        code, extras, extra_var_bits, vle = read_bin_code(comp_file_path, num_extras=NUM_EXTRAS,
-                                                          num_extra_var_bits=2,
-                                                          num_var_length_extras=nvle)
+        code, extras, extra_var_bits, vle = read_bin_code(
+            comp_file_path, num_extras=NUM_EXTRAS,
+            num_extra_var_bits=3 if first_level_group_bits else 2, num_var_length_extras=nvle)
         g1_bits = first_level_max_group_size_bits if use_importance_sampling else \
             greedy_max_group_size_bits
         coder2 = ArithmeticCoder(_load_counts(second_level_group_dist_counts,
@@ -691,6 +779,17 @@ class ProbabilisticLadderNetwork(nn.Module):
             else:
                 dec1 = decode_grouped_importance_sample(None, code1, gi1[:-1], p1p,
                                                         n_bits_group_1, seed, vle[2], vle[3])
+        elif first_level_group_bits:
+            symbols = _budget_coder(first_level_bits_dist_counts,
+                                    n_bits_per_step).decode_fast(extra_var_bits[2])[:-1]
+            group_bits1 = _budgets_from_symbols(symbols, n_bits_per_step)
+            if group_bits1.size != gi1.size - 1:
+                raise ValueError(f"{group_bits1.size} budgets for {gi1.size - 1} level-1 groups")
+            if len1 != n_steps * int(group_bits1.sum(dtype=np.int64)):
+                raise ValueError(f"the level-1 code holds {len1} bits, the budgets give "
+                                 f"{n_steps * int(group_bits1.sum(dtype=np.int64))}")
+            dec1 = decode_grouped_greedy_sample_var(_pack_bits(code1), gi1, group_bits1, p1p,
+                                                    n_steps, seed, rho=rho)
         else:
             dec1 = decode_grouped_greedy_sample(None, code1, gi1[:-1], p1p, n_bits_per_step,
                                                 n_steps, seed, rho=rho)

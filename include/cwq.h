@@ -85,8 +85,11 @@ extern "C" {
  *        cwq_greedy_encode_uniform_var, cwq_pack_indices_var,
  *        cwq_unpack_indices_var and their workspace sizes;
  *   0.9  per-block bit budgets for CSR blocks: cwq_block_bits_csr,
- *        cwq_greedy_encode_var and its workspace size. */
-#define CWQ_ABI_VERSION ((0 << 16) | 9)
+ *        cwq_greedy_encode_var and its workspace size;
+ *   0.10 cwq_selftest_encode_rows_wave; cwq_greedy_encode_var codes buckets of
+ *        long blocks below 4,096 candidates with a wave per candidate row
+ *        (same results as before). */
+#define CWQ_ABI_VERSION ((0 << 16) | 10)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -256,7 +259,12 @@ int cwq_block_bits_csr(const float* q_loc, const float* q_scale, const float* p_
  * bucket is coded by one launch sequence of the CSR encoder, highest bit count
  * first, on the caller's stream, sized by the bucket's own longest block (a
  * bucket of short blocks takes the short-block kernels whatever max_block_dim
- * says).  The results are scattered back to block order.  Like
+ * says).  A bucket below 4,096 candidates (bit count < 12) whose blocks
+ * average at least 256 dims is scored by the wave-per-row kernel unless
+ * opts->prune_mode is 0: every candidate exactly, one wave per row, the same
+ * results (the other paths there walk a row with one lane).  A
+ * bucket of many short blocks and a few long ones does not meet the rule and
+ * runs as before.  The results are scattered back to block order.  Like
  * cwq_greedy_encode_uniform_var this call SYNCHRONISES the stream, once, and
  * is NOT graph-capturable; everything after that is only enqueued.
  * CWQ_ERR_INVALID, before anything is coded or written to the outputs: a bit
@@ -620,6 +628,17 @@ int cwq_selftest_div(const float* a, const float* b, int64_t n, float* out, void
 /* out[w] = max(x[64 w .. 64 w + 63]): the wave-wide DPP max the pruned encoder
  * shares its threshold with. */
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream);
+/* cwq_greedy_encode (same arguments without opts, same workspace from
+ * cwq_greedy_encode_workspace_size, same validation and results) with every
+ * block scored by the wave-per-row kernel that cwq_greedy_encode_var uses for
+ * buckets of long blocks at few candidates, whatever the blocks' length or
+ * number: the tests reach short, odd and empty rows on that kernel this way. */
+int cwq_selftest_encode_rows_wave(const float* t_loc, const float* t_scale, const float* p_loc,
+                                  const float* p_scale, const int64_t* block_off, int64_t nb,
+                                  int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
+                                  int n_steps, int32_t seed, float rho, int64_t block_id_base,
+                                  int32_t* out_idx, float* out_sample, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 
 
