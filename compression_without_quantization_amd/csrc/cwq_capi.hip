@@ -57,20 +57,14 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct WsLayout {
   size_t keys, tq, loc_s, scale_s, lognorm, sab, cdim, bpre, ordu, grp, gtau, abp, slist;
   size_t sdmap, total;
-  bool csr;   // has the general pruned kernel's arrays
-  bool recs;  // ... and the visit-order records of blocks longer than CWQ_CSR_LDS_DIMS
+  bool csr;   // has_screen_arrays: the general pruned kernel's and the small paths' arrays
+  bool recs;  // has_long_block_records: visit-order records of blocks > CWQ_CSR_LDS_DIMS
 };
 
-// Blocks the uniform fast pruned kernel takes (d % 8 == 0, 8 <= d <= 64) need
-// only keys + the per-dim shard constants; everything else (CSR, other d) also
-// gets the general pruned kernel's screening constants and the screened small-candidate
-// path's survivor slots and the small-candidate pipeline's arrays (24 B/dim + 244 B/block),
-// and, when some block may exceed CWQ_CSR_LDS_DIMS dims, the visit-order
-// records of the long blocks (32 B/dim + 384 B per CWQ_CSR_LDS_DIMS + 1 dims,
-// csr_rec_entries: short blocks take no room, so a grouped call sized for
+// csr (has_screen_arrays, cwq_dispatch.h): 24 B/dim + 244 B/block; recs
+// (has_long_block_records): 32 B/dim + 384 B per CWQ_CSR_LDS_DIMS + 1 dims
+// (csr_rec_entries: short blocks take no room, so a grouped call sized for
 // D + 1 possible groups does not pay 384 B for each).
-bool uniform_fast(int64_t d) { return d % 8 == 0 && d >= 8 && d <= 64; }
-
 WsLayout ws_layout(int64_t nb, int64_t total_dims, bool csr, bool recs) {
   WsLayout l;
   size_t o = 0;
@@ -115,11 +109,12 @@ WsLayout ws_layout(int64_t nb, int64_t total_dims, bool csr, bool recs) {
 }
 // CSR blocks of at most max_block_dim dims
 WsLayout ws_layout_csr(int64_t nb, int64_t total_dims, int64_t max_block_dim) {
-  return ws_layout(nb, total_dims, true, max_block_dim > CWQ_CSR_LDS_DIMS);
+  return ws_layout(nb, total_dims, cwq::has_screen_arrays(true, 0, nb),
+                   cwq::has_long_block_records(true, max_block_dim, nb));
 }
 WsLayout ws_layout_uniform(int64_t nb, int64_t d) {
-  const bool csr = nb > 0 && !uniform_fast(d);
-  return ws_layout(nb, nb * d, csr, d > CWQ_CSR_LDS_DIMS);
+  return ws_layout(nb, nb * d, cwq::has_screen_arrays(false, d, nb),
+                   cwq::has_long_block_records(false, d, nb));
 }
 
 #ifndef CWQ_TARGET_TILES
@@ -878,15 +873,7 @@ int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float*
     const int64_t c = f.counts[b];
     if (c == 0) continue;
     const int64_t r0 = f.start[b], d0 = f.pre[b];
-    // Long rows at few candidates: below 4,096 candidates the
-    // other paths walk a row with one lane, so a bucket whose mean block reaches
-    // the length from which rows count as long gives every row to a wave.
-    // prune_mode 0 keeps k_encode_eval, as it promises.
-#ifndef CWQ_VAR_ROWS_WAVE
-#define CWQ_VAR_ROWS_WAVE 1  // 0: every bucket on the paths it took before (A/B builds)
-#endif
-    const bool rows_wave = CWQ_VAR_ROWS_WAVE && b < 12 &&
-                           f.dims[b] >= (int64_t)CWQ_CSR_COOP_MIN_D * c && o.prune_mode != 0;
+    const bool rows_wave = cwq::bucket_takes_rows_wave(b, f.dims[b], c, o.prune_mode);
     // the bucket's own longest block: short blocks stay off the long-block path
     rc = encode_impl(tl_s + d0, ts_s + d0, pl_s + d0, ps_s + d0, roff + r0 + b, 0, c, f.dims[b],
                      f.maxd[b], b, n_steps, seed, rho, block_id_base, stage + r0 * n_steps,

@@ -1,0 +1,133 @@
+// cwq_dispatch.h -- which encoder path one launch_encode call takes, defined
+// once for the workspace layout (cwq_capi.hip), the launchers
+// (cwq_kernels.hip) and the host, where tests/test_encode_plan.py checks a
+// table of shapes against it (DESIGN.md "Encode dispatch").
+//
+// Everything here is a pure function of the call's shape; no pointer is read.
+// Host only: no kernel needs it, and it includes nothing from HIP.
+#pragma once
+#include <stdint.h>
+
+// Tuning switches of the dispatch (tools/variants.sh builds with -D...).
+#ifndef CWQ_CSR_LDS_DIMS
+#define CWQ_CSR_LDS_DIMS 1024  // general pruned kernel: blocks up to this d keep their
+                               // screening constants in LDS (longer: abp records)
+#endif
+#ifndef CWQ_CSR_COOP_MIN_D
+#define CWQ_CSR_COOP_MIN_D 256  // rows of at least this many dims count as long: the general
+                                // pruned kernel walks them cooperatively, and a budget bucket
+                                // of this mean length takes k_encode_rows_wave
+#endif
+#ifndef CWQ_CSR_COOP_ROWS_PER_LANE
+#define CWQ_CSR_COOP_ROWS_PER_LANE 8  // cooperative rows below this many rows per lane, for
+#endif                                // blocks of at least CWQ_CSR_COOP_MIN_D dims
+#ifndef CWQ_SMALL_MIN_CAND
+#define CWQ_SMALL_MIN_CAND 64  // fewer candidates: the exact kernel (screening would not pay)
+#endif
+#ifndef CWQ_FUSED_DMAX
+#define CWQ_FUSED_DMAX 64  // longest block of the small pipeline
+#endif
+#ifndef CWQ_SMALL_FUSED
+#define CWQ_SMALL_FUSED 1  // 0: the three-kernel path for every block length (d <= 64 too)
+#endif
+#ifndef CWQ_SMALL_PIPE
+#define CWQ_SMALL_PIPE 1  // 0: the three-kernel path for these shapes too
+#endif
+#ifndef CWQ_VAR_ROWS_WAVE
+#define CWQ_VAR_ROWS_WAVE 1  // 0: every bucket on the paths it took before (A/B builds)
+#endif
+#ifndef CWQ_ENCODE_SPLIT
+#define CWQ_ENCODE_SPLIT 3  // most parts a multi-step CSR encode forks into
+#endif
+#ifndef CWQ_SPLIT_FEW
+#define CWQ_SPLIT_FEW 3  // parts of a cooperative (few long rows) launch
+#endif
+
+namespace cwq {
+
+// From this many candidates per block the general pruned kernel takes a
+// screened launch; below, the small-candidate paths.
+constexpr int64_t kCsrPrunedMinCand = 4096;
+constexpr int64_t kChipLanes = 1536 * 256;  // lanes the whole chip holds
+
+struct EncodeShape {
+  bool csr;        // ragged blocks (block_off given); false: uniform blocks of ud dims
+  int64_t ud;      // uniform block length (csr: unused)
+  int64_t max_d;   // longest block (uniform: ud); -1: unknown
+  int64_t nb;
+  int64_t n_cand;  // 2^n_bits_per_step
+  int prune;       // cwq_options.prune_mode
+  bool rows_wave;  // the caller forces k_encode_rows_wave (bucket_takes_rows_wave)
+};
+
+enum class EncodePath { RowsWave, UniformPruned, CsrPruned, SmallPipe, SmallThree, Eval };
+
+struct EncodePlan {
+  EncodePath path;
+  bool coop;             // CsrPruned: long rows are walked cooperatively by 16 lanes
+  bool self_finalizing;  // the small pipeline: no k_prep_dims before, no key reset between
+                         // steps, no k_encode_finalize* after them, k_destandardise folded in
+};
+
+// Blocks the uniform fast pruned kernel takes (d % 8 == 0, 8 <= d <= 64) need
+// only keys + the per-dim shard constants; everything else (CSR, other d) also
+// gets the general pruned kernel's screening constants, the screened
+// small-candidate path's survivor slots and the small pipeline's arrays.
+inline bool has_screen_arrays(bool csr, int64_t ud, int64_t nb) {
+  return csr || (nb > 0 && !(ud % 8 == 0 && ud >= 8 && ud <= 64));
+}
+// ... and, when some block may exceed CWQ_CSR_LDS_DIMS dims, the visit-order
+// records of the long blocks (max_d: the longest block; uniform: d).
+inline bool has_long_block_records(bool csr, int64_t max_d, int64_t nb) {
+  return has_screen_arrays(csr, max_d, nb) && max_d > CWQ_CSR_LDS_DIMS;
+}
+
+// Few long rows: fewer than CWQ_CSR_COOP_ROWS_PER_LANE candidate rows per lane
+// of the chip.  The general pruned kernel then walks long rows cooperatively,
+// and a forked call splits in CWQ_SPLIT_FEW parts.
+inline bool few_rows(int64_t nb, int64_t n_cand) {
+  return nb * n_cand < (int64_t)CWQ_CSR_COOP_ROWS_PER_LANE * kChipLanes;
+}
+
+// The path of one block range (a whole call, or one part of a forked call).
+inline EncodePlan encode_plan(const EncodeShape& s) {
+  const bool screened = s.prune >= 2 && has_screen_arrays(s.csr, s.ud, s.nb);
+  EncodePath path = EncodePath::Eval;
+  if (s.rows_wave)
+    path = EncodePath::RowsWave;
+  // uniform D % 8 == 0, D <= 64, Philox block index n*D/4 < 2^32
+  else if (!s.csr && s.prune >= 1 && s.ud % 8 == 0 && s.ud >= 8 && s.ud <= 64 &&
+           s.n_cand * (s.ud / 4) <= (1LL << 32))
+    path = EncodePath::UniformPruned;
+  else if (screened && s.n_cand >= kCsrPrunedMinCand)
+    path = EncodePath::CsrPruned;
+  else if (screened && s.n_cand >= CWQ_SMALL_MIN_CAND)
+    path = CWQ_SMALL_PIPE && CWQ_SMALL_FUSED && s.max_d >= 0 && s.max_d <= CWQ_FUSED_DMAX &&
+                   s.nb < (1LL << 32)
+               ? EncodePath::SmallPipe
+               : EncodePath::SmallThree;
+  return {path, path == EncodePath::CsrPruned && few_rows(s.nb, s.n_cand),
+          path == EncodePath::SmallPipe};
+}
+
+// Parts a call's block range forks into (1: no fork).  Only a multi-step CSR
+// encode forks; launches of few long rows overlap best in CWQ_SPLIT_FEW parts,
+// others in two (tools/stream_overlap.py).
+inline int encode_fork_parts(const EncodeShape& s, int n_steps) {
+  if (CWQ_ENCODE_SPLIT <= 1 || !s.csr || n_steps <= 1 || s.nb < 2) return 1;
+  int k = few_rows(s.nb, s.n_cand) ? CWQ_SPLIT_FEW : 2;
+  k = k < CWQ_ENCODE_SPLIT ? k : CWQ_ENCODE_SPLIT;
+  return (int64_t)k < s.nb ? k : (int)s.nb;
+}
+
+// cwq_greedy_encode_var's bucket rule.  Long rows at few candidates (DESIGN.md
+// 4e): below kCsrPrunedMinCand candidates the other paths walk a row with one
+// lane, so a bucket of `count` blocks at `bits` bits whose mean block reaches
+// the length from which rows count as long gives every row to a wave.
+// prune_mode 0 keeps k_encode_eval, as it promises.
+inline bool bucket_takes_rows_wave(int bits, int64_t dims, int64_t count, int prune) {
+  return CWQ_VAR_ROWS_WAVE && ((int64_t)1 << bits) < kCsrPrunedMinCand &&
+         dims >= (int64_t)CWQ_CSR_COOP_MIN_D * count && prune != 0;
+}
+
+}  // namespace cwq

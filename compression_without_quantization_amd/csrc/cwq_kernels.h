@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cwq_dispatch.h"
+
 namespace cwq {
 
 #ifndef CWQ_CSR_GTAU_STRIDE
@@ -11,11 +13,6 @@ namespace cwq {
 
 // Records `msg` for cwq_last_error() (thread-local) and returns `code`.
 int set_error(int code, const char* msg);
-
-#ifndef CWQ_CSR_LDS_DIMS
-#define CWQ_CSR_LDS_DIMS 1024  // general pruned kernel: blocks up to this d keep their
-                               // screening constants in LDS (longer: abp records)
-#endif
 
 // First entry of a long block's visit-order records (abp, 32 B per entry) for a
 // block at absolute dim offset off.  Only blocks of more than CWQ_CSR_LDS_DIMS
@@ -28,12 +25,6 @@ __host__ __device__ inline int64_t csr_rec_base(int64_t off) {
 __host__ __device__ inline int64_t csr_rec_entries(int64_t total_dims) {
   return total_dims + 12 * (total_dims / (CWQ_CSR_LDS_DIMS + 1) + 1);
 }
-
-#ifndef CWQ_CSR_COOP_MIN_D
-#define CWQ_CSR_COOP_MIN_D 256  // rows of at least this many dims count as long: the general
-                                // pruned kernel walks them cooperatively, and a budget bucket
-                                // of this mean length takes k_encode_rows_wave
-#endif
 
 constexpr int kTileQueueSlots = 64;
 
@@ -66,8 +57,9 @@ struct EncodeArgs {
   float* loc_s;              // [total_dims]
   float* scale_s;            // [total_dims]
   float* lognorm;            // [total_dims]
-  // screening constants of the general pruned kernel (k_encode_prune_csr);
-  // nullptr when the workspace was sized without them
+  // screening constants of the general pruned kernel (k_encode_prune_csr):
+  // there iff has_screen_arrays (cwq_dispatch.h), which sizes the workspace
+  // and picks the path; the launchers only check that they were given
   float2* sab;               // [total_dims + 8 nb] (sA, sB), 4 zero pads either side per block
   float* cdim;               // [total_dims] C_j of the screening bound (k_csr_prep scratch)
   float* bpre;               // [total_dims + 12 nb] drop bounds per visit position (k_csr_prep)
@@ -75,14 +67,15 @@ struct EncodeArgs {
   float4* grp;               // [nb] (c1, c2, As, Pq); c1 == 0: block not screened
   uint32_t* gtau;            // [nb] per-block shared threshold (ord)
   float4* abp;               // [2 (total_dims + 12 nb)] visit-order (sa, sb) records of the
-                             // blocks longer than CWQ_CSR_LDS_DIMS; nullptr if none are
+                             // blocks longer than CWQ_CSR_LDS_DIMS; there iff
+                             // has_long_block_records, else nullptr
   uint2* slist;              // screened small-candidate path: CWQ_SLIST_PER_BLOCK
                              // (row, upper bits) survivor slots per block; the
                              // per-block counts live in ordu[off + 12 g]
   // optional profiling events around the eval launches (hipEvent_t)
   void* ev_start;
   void* ev_stop;
-  // the small-candidate pipeline (k_small_*; nullptr: not sized for it):
+  // the small-candidate pipeline (k_small_*; there iff has_screen_arrays):
   // per-dim screening constants (sA, sB) by absolute dim offset (a view of
   // sab, set by launch_encode) and the dim -> block map [total_dims]
   const float2* pre_ab = nullptr;

@@ -994,9 +994,6 @@ __global__ void __launch_bounds__(256) k_encode_rows_wave(
 #ifndef CWQ_CSR_SURVIVOR_CAP
 #define CWQ_CSR_SURVIVOR_CAP 512
 #endif
-#ifndef CWQ_CSR_COOP_ROWS_PER_LANE
-#define CWQ_CSR_COOP_ROWS_PER_LANE 8  // cooperative rows below this many rows per lane, for
-#endif                                // blocks of at least CWQ_CSR_COOP_MIN_D dims (cwq_kernels.h)
 #ifndef CWQ_CSR_TILE
 #define CWQ_CSR_TILE 1024             // smallest tile (candidates), per-lane rows
 #endif
@@ -1584,9 +1581,6 @@ __global__ void __launch_bounds__(256, COOP ? CWQ_CSR_COOP_MIN_WAVES : CWQ_CSR_R
 #ifndef CWQ_SMALL_SCREEN_WAVES
 #define CWQ_SMALL_SCREEN_WAVES 8  // waves/SIMD k_small_screen's registers must allow
 #endif
-#ifndef CWQ_SMALL_MIN_CAND
-#define CWQ_SMALL_MIN_CAND 64  // fewer candidates: the exact kernel (screening would not pay)
-#endif
 
 // A wave prepares 64 consecutive blocks: lane i block i when it has at most
 // kSmallLaneD dims (C2's groups: ~5), sequentially; longer blocks afterwards
@@ -1913,9 +1907,6 @@ __global__ void __launch_bounds__(256) k_small_survivors(
 // blocks doing constants, screen, exact survivors and finalize); round 5
 // split it (see "The small-candidate step as a pipeline").
 // ---------------------------------------------------------------------------
-#ifndef CWQ_FUSED_DMAX
-#define CWQ_FUSED_DMAX 64  // longest block of the small pipeline
-#endif
 #ifndef CWQ_FUSED_LIST
 #define CWQ_FUSED_LIST 64  // listed rows per block
 #endif
@@ -3243,15 +3234,11 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
 }
 
 template <bool STEP0>
-static void launch_prune_csr(const EncodeArgs& a, int step, hipStream_t stream) {
-
+static void launch_prune_csr(const EncodeArgs& a, bool coop, int step, hipStream_t stream) {
   // own tiling: ~8192 tiles of >= 1024 candidates; tiles of a block share tau
-  // through gtau, and later tiles start from it.  With few rows per lane (a
-  // few large groups: the whole chip holds 1536 x 256 lanes) long rows are
-  // walked cooperatively by 16 lanes instead, in tiles of >= 128 candidates.
-  const int64_t kLanes = 1536 * 256;
-  const int64_t rows = a.nb * a.n_cand;
-  const bool coop = rows < CWQ_CSR_COOP_ROWS_PER_LANE * kLanes;
+  // through gtau, and later tiles start from it.  With few rows per lane
+  // (EncodePlan::coop: a few large groups) long rows are walked cooperatively
+  // by 16 lanes instead, in tiles of >= 128 candidates.
   int64_t tpb, max_tpb;
   if (coop) {
     tpb = (CWQ_CSR_COOP_TILES + a.nb - 1) / a.nb;
@@ -3297,67 +3284,42 @@ static void launch_prune_csr(const EncodeArgs& a, int step, hipStream_t stream) 
                        coop_min_d, (const float4*)a.abp);
 }
 
-#ifndef CWQ_SMALL_FUSED
-#define CWQ_SMALL_FUSED 1  // 0: the three-kernel path for every block length (d <= 64 too)
-#endif
-// true: the launches also wrote the step's indices and sample (the small pipeline)
-#ifndef CWQ_SMALL_PIPE
-#define CWQ_SMALL_PIPE 1  // 0: the three-kernel path for these shapes too
-#endif
-// launch_eval_dc's choices, shared with launch_encode (which leaves step 0's
-// prep to k_small_prep1 when the small pipeline runs)
-static bool takes_uniform_pruned(const EncodeArgs& a) {
-  // pruned path: uniform D % 8 == 0, D <= 64, Philox block index n*D/4 < 2^32
-  return a.block_off == nullptr && a.prune && a.ud % 8 == 0 && a.ud >= 8 && a.ud <= 64 &&
-         a.n_cand * (a.ud / 4) <= (1LL << 32);
-}
-static bool takes_small_path(const EncodeArgs& a) {  // launch_small's d <= 64 shapes
-  return !a.rows_wave && !takes_uniform_pruned(a) && !(a.prune >= 2 && a.sab != nullptr && a.n_cand >= 4096) &&
-         a.prune >= 2 && a.sab != nullptr && a.slist != nullptr && a.ordu != nullptr &&
-         a.n_cand >= CWQ_SMALL_MIN_CAND && CWQ_SMALL_FUSED && a.max_d >= 0 &&
-         a.max_d <= CWQ_FUSED_DMAX && a.n_cand < 4096;
-}
-static bool small_pipe_ok(const EncodeArgs& a) {  // ... and the pipeline's arrays are there
-  return a.sdmap && a.sab && a.slist && a.nb < (1LL << 32);
-}
-static bool takes_small_pipe(const EncodeArgs& a) {
-  return CWQ_SMALL_PIPE && takes_small_path(a) && small_pipe_ok(a);
+// The small pipeline (k_small_*): constants, persistent screen, finalize.  The
+// launches also write the step's indices and sample (EncodePlan::self_finalizing).
+template <bool STEP0>
+static void launch_small_pipe(const EncodeArgs& a, int step, hipStream_t stream) {
+  SmallRec* rec = (SmallRec*)a.slist;
+  float2* pab = const_cast<float2*>(a.pre_ab);  // by absolute dim (launch_encode)
+  const float nst = (float)a.n_steps;
+  const float sdiv = (float)__builtin_sqrt((double)a.n_steps);
+  const unsigned pgrid = grid_for(a.nb, kSmallPrepBlocks, 1u << 31);
+  if (STEP0)
+    hipLaunchKernelGGL(k_small_prep1<true>, dim3(pgrid), dim3(CWQ_PREP1_THREADS), 0, stream, a.t_loc,
+                       a.t_scale, a.p_loc, a.p_scale, nst, sdiv, a.rho, a.loc_s, a.scale_s,
+                       a.lognorm, a.out_sample, a.block_off, a.ud, a.nb, seeds_of(a), step,
+                       pab, rec, a.sdmap);
+  else
+    hipLaunchKernelGGL(k_small_prep1<false>, dim3(pgrid), dim3(CWQ_PREP1_THREADS), 0, stream, a.t_loc,
+                       a.t_scale, a.p_loc, a.p_scale, nst, sdiv, a.rho, a.loc_s, a.scale_s,
+                       a.lognorm, a.out_sample, a.block_off, a.ud, a.nb, seeds_of(a), step,
+                       pab, rec, a.sdmap);
+  const int64_t nu = a.nb;
+  for (int64_t u0 = 0; u0 < nu; u0 += (int64_t)1 << 30)
+    hipLaunchKernelGGL((k_small_one<STEP0>),
+                       dim3((unsigned)(nu - u0 < (1LL << 30) ? nu - u0 : (1LL << 30))),
+                       dim3(64), 0, stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm,
+                       a.out_sample, rec, a.pre_ab, a.nb, u0, a.n_cand, step, a.n_steps,
+                       a.out_idx);
+  const unsigned dgrid = grid_for(a.total_dims > a.nb ? a.total_dims : a.nb, 256, 16384);
+  hipLaunchKernelGGL((k_small_finalize<STEP0>), dim3(dgrid), dim3(256), 0, stream, a.loc_s,
+                     a.scale_s, rec, a.sdmap, a.out_idx, step, a.n_steps, a.block_off, a.ud,
+                     a.nb, a.out_sample, step == a.n_steps - 1 ? a.ds_out : nullptr, a.ds_loc,
+                     a.ds_scale);
 }
 
+// The three-kernel small-candidate path (k_small_prep/screen/survivors).
 template <bool STEP0>
-static bool launch_small(const EncodeArgs& a, int step, hipStream_t stream) {
-  if (CWQ_SMALL_PIPE && CWQ_SMALL_FUSED && a.max_d >= 0 && a.max_d <= CWQ_FUSED_DMAX &&
-      a.n_cand < 4096 && small_pipe_ok(a)) {
-    // the small pipeline (k_small_*): constants, persistent screen, finalize
-    SmallRec* rec = (SmallRec*)a.slist;
-    float2* pab = const_cast<float2*>(a.pre_ab);  // by absolute dim (launch_encode)
-    const float nst = (float)a.n_steps;
-    const float sdiv = (float)__builtin_sqrt((double)a.n_steps);
-    const unsigned pgrid = grid_for(a.nb, kSmallPrepBlocks, 1u << 31);
-    if (STEP0)
-      hipLaunchKernelGGL(k_small_prep1<true>, dim3(pgrid), dim3(CWQ_PREP1_THREADS), 0, stream, a.t_loc,
-                         a.t_scale, a.p_loc, a.p_scale, nst, sdiv, a.rho, a.loc_s, a.scale_s,
-                         a.lognorm, a.out_sample, a.block_off, a.ud, a.nb, seeds_of(a), step,
-                         pab, rec, a.sdmap);
-    else
-      hipLaunchKernelGGL(k_small_prep1<false>, dim3(pgrid), dim3(CWQ_PREP1_THREADS), 0, stream, a.t_loc,
-                         a.t_scale, a.p_loc, a.p_scale, nst, sdiv, a.rho, a.loc_s, a.scale_s,
-                         a.lognorm, a.out_sample, a.block_off, a.ud, a.nb, seeds_of(a), step,
-                         pab, rec, a.sdmap);
-    const int64_t nu = a.nb;
-    for (int64_t u0 = 0; u0 < nu; u0 += (int64_t)1 << 30)
-      hipLaunchKernelGGL((k_small_one<STEP0>),
-                         dim3((unsigned)(nu - u0 < (1LL << 30) ? nu - u0 : (1LL << 30))),
-                         dim3(64), 0, stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm,
-                         a.out_sample, rec, a.pre_ab, a.nb, u0, a.n_cand, step, a.n_steps,
-                         a.out_idx);
-    const unsigned dgrid = grid_for(a.total_dims > a.nb ? a.total_dims : a.nb, 256, 16384);
-    hipLaunchKernelGGL((k_small_finalize<STEP0>), dim3(dgrid), dim3(256), 0, stream, a.loc_s,
-                       a.scale_s, rec, a.sdmap, a.out_idx, step, a.n_steps, a.block_off, a.ud,
-                       a.nb, a.out_sample, step == a.n_steps - 1 ? a.ds_out : nullptr, a.ds_loc,
-                       a.ds_scale);
-    return true;
-  }
+static void launch_small_three(const EncodeArgs& a, int step, hipStream_t stream) {
   const int64_t ntiles = a.nb * a.tiles_per_block;
   hipLaunchKernelGGL((k_small_prep<STEP0>), dim3(grid_for(a.nb, 4 * 64, 16384)), dim3(256), 0,
                      stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
@@ -3372,7 +3334,6 @@ static bool launch_small(const EncodeArgs& a, int step, hipStream_t stream) {
                      a.out_sample, a.block_off, a.ud, a.nb, a.n_cand, seeds_of(a), step,
                      (const float4*)a.grp, (const uint32_t*)a.gtau, (const uint32_t*)a.ordu,
                      (const uint2*)a.slist, (const float*)a.bpre, a.keys);
-  return false;
 }
 
 // A wave per candidate row (k_encode_rows_wave): four rows per workgroup
@@ -3390,47 +3351,48 @@ static void launch_rows_wave(const EncodeArgs& a, int step, hipStream_t stream) 
                      a.out_sample, a.block_off, a.ud, a.nb, n_bits, seeds_of(a), step, a.keys);
 }
 
-// Scoring launches of one step; true when they also finalized it (indices and
-// sample written), false when k_encode_finalize must follow.
+static EncodeShape shape_of(const EncodeArgs& a) {
+  return {a.block_off != nullptr, a.ud, a.max_d, a.nb, a.n_cand, a.prune, a.rows_wave};
+}
+
+// Scoring launches of one step on the plan's path (encode_plan, cwq_dispatch.h).
 template <bool STEP0>
-static bool launch_eval_dc(const EncodeArgs& a, int step, hipStream_t stream) {
-  if (a.rows_wave) return launch_rows_wave<STEP0>(a, step, stream), false;
-  if (takes_uniform_pruned(a)) {
-    switch (a.ud) {
-      case 8: return launch_prune_t<8, STEP0>(a, step, stream), false;
-      case 16: return launch_prune_t<16, STEP0>(a, step, stream), false;
-      case 24: return launch_prune_t<24, STEP0>(a, step, stream), false;
-      case 32: return launch_prune_t<32, STEP0>(a, step, stream), false;
-      case 40: return launch_prune_t<40, STEP0>(a, step, stream), false;
-      case 48: return launch_prune_t<48, STEP0>(a, step, stream), false;
-      case 56: return launch_prune_t<56, STEP0>(a, step, stream), false;
-      case 64: return launch_prune_t<64, STEP0>(a, step, stream), false;
-      default: break;
-    }
+static void launch_eval_dc(const EncodeArgs& a, const EncodePlan& plan, int step,
+                           hipStream_t stream) {
+  switch (plan.path) {
+    case EncodePath::RowsWave: return launch_rows_wave<STEP0>(a, step, stream);
+    case EncodePath::UniformPruned:
+      switch (a.ud) {
+        case 8: return launch_prune_t<8, STEP0>(a, step, stream);
+        case 16: return launch_prune_t<16, STEP0>(a, step, stream);
+        case 24: return launch_prune_t<24, STEP0>(a, step, stream);
+        case 32: return launch_prune_t<32, STEP0>(a, step, stream);
+        case 40: return launch_prune_t<40, STEP0>(a, step, stream);
+        case 48: return launch_prune_t<48, STEP0>(a, step, stream);
+        case 56: return launch_prune_t<56, STEP0>(a, step, stream);
+        default: return launch_prune_t<64, STEP0>(a, step, stream);  // the plan admits no other
+      }
+    case EncodePath::CsrPruned: return launch_prune_csr<STEP0>(a, plan.coop, step, stream);
+    case EncodePath::SmallPipe: return launch_small_pipe<STEP0>(a, step, stream);
+    case EncodePath::SmallThree: return launch_small_three<STEP0>(a, step, stream);
+    case EncodePath::Eval:
+      if (a.block_off == nullptr) {
+        switch (a.ud) {
+          case 8: return launch_eval_t<8, STEP0>(a, step, stream);
+          case 16: return launch_eval_t<16, STEP0>(a, step, stream);
+          case 32: return launch_eval_t<32, STEP0>(a, step, stream);
+          default: break;
+        }
+      }
+      return launch_eval_t<0, STEP0>(a, step, stream);
   }
-  // general pruned path (screening): CSR or other uniform d, >= 4096 candidates
-  if (a.prune >= 2 && a.sab != nullptr && a.n_cand >= 4096)
-    return launch_prune_csr<STEP0>(a, step, stream), false;
-  // screened small-candidate path (k_small_*): few candidates per block
-  if (a.prune >= 2 && a.sab != nullptr && a.slist != nullptr && a.ordu != nullptr &&
-      a.n_cand >= CWQ_SMALL_MIN_CAND)
-    return launch_small<STEP0>(a, step, stream);
-  if (a.block_off == nullptr) {
-    switch (a.ud) {
-      case 8: return launch_eval_t<8, STEP0>(a, step, stream), false;
-      case 16: return launch_eval_t<16, STEP0>(a, step, stream), false;
-      case 32: return launch_eval_t<32, STEP0>(a, step, stream), false;
-      default: break;
-    }
-  }
-  launch_eval_t<0, STEP0>(a, step, stream);
-  return false;
 }
 
 // The step loop of one block range on one stream: reset the argmax keys, score
 // the candidates, finalize (index + best) -- steps are sequential per block.
 static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool events) {
   hipError_t e;
+  const EncodePlan plan = encode_plan(shape_of(a));
   // the general finalize covers max(nb, dims of this block range) threads
 #ifndef CWQ_FIN_MAX_WGS
 #define CWQ_FIN_MAX_WGS 16384
@@ -3440,7 +3402,7 @@ static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool eve
   for (int s = 0; s < a.n_steps; ++s) {
     // step 0's keys were zeroed by k_prep_dims (launch_encode); the small
     // pipeline keeps its argmax in registers and LDS and never reads keys
-    if (s > 0 && !takes_small_pipe(a) &&
+    if (s > 0 && !plan.self_finalizing &&
         (e = hipMemsetAsync(a.keys, 0, (size_t)a.nb * sizeof(unsigned long long), stream)) !=
             hipSuccess)
       return e;
@@ -3448,15 +3410,17 @@ static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool eve
       e = hipEventRecord((hipEvent_t)a.ev_start, stream);
       if (e != hipSuccess) return e;
     }
-    const bool finalized =
-        s == 0 ? launch_eval_dc<true>(a, s, stream) : launch_eval_dc<false>(a, s, stream);
+    if (s == 0)
+      launch_eval_dc<true>(a, plan, s, stream);
+    else
+      launch_eval_dc<false>(a, plan, s, stream);
     if (events && s == a.n_steps - 1 && a.ev_stop) {
       e = hipEventRecord((hipEvent_t)a.ev_stop, stream);
       if (e != hipSuccess) return e;
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (finalized) continue;
+    if (plan.self_finalizing) continue;
     if (q4_shape(a.block_off, a.ud) && aligned16(a.loc_s, a.scale_s, a.out_sample)) {
       const uint32_t qpb = (uint32_t)(a.ud / 4), bpw = 64u / qpb;
       hipLaunchKernelGGL(k_encode_finalize_q4, dim3(grid_for(a.nb, 4 * (int64_t)bpw, 1u << 20)),
@@ -3480,9 +3444,6 @@ static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool eve
 // a step, and the finalize/prep launches between steps) overlaps the other
 // half's work.  Fork and join are events on the caller's stream, so the call
 // stays stream-ordered (and capturable) for the caller.
-#ifndef CWQ_ENCODE_SPLIT
-#define CWQ_ENCODE_SPLIT 3  // most parts a multi-step CSR encode forks into
-#endif
 namespace {
 constexpr int kMaxSplit = CWQ_ENCODE_SPLIT > 3 ? CWQ_ENCODE_SPLIT : 3;
 constexpr int kMaxDevices = 16;
@@ -3550,7 +3511,14 @@ hipError_t launch_encode(const EncodeArgs& a_in, hipStream_t stream) {
   // the small pipeline's per-dim screening constants, by absolute dim offset: a
   // view of sab (the other paths' scratch) taken before a fork shifts it per part
   a.pre_ab = a.sab;
-  if (takes_small_pipe(a))
+  const EncodeShape shape = shape_of(a);
+  const EncodePlan plan = encode_plan(shape);  // of the whole call; encode_steps: of each part
+  // a guard, not a dispatch input: the screened paths' arrays were given
+  const bool screened = plan.path == EncodePath::CsrPruned ||
+                        plan.path == EncodePath::SmallPipe || plan.path == EncodePath::SmallThree;
+  if (screened && !(a.sab && a.cdim && a.bpre && a.ordu && a.grp && a.gtau && a.slist && a.sdmap))
+    return hipErrorInvalidValue;
+  if (plan.self_finalizing)
     e = hipSuccess;  // its step 0 does k_prep_dims' work in k_small_prep1
   else
     e = launch_prep_dims(a.t_scale, a.p_loc, a.p_scale, a.total_dims, a.n_steps, a.rho, a.loc_s,
@@ -3559,32 +3527,21 @@ hipError_t launch_encode(const EncodeArgs& a_in, hipStream_t stream) {
   if (a.nb == 0) return hipSuccess;
   // :292 destandardise after the last step: the small pipeline's finalize
   // does it, anything else one k_destandardise on the caller's stream
-  const bool ds_after = a.ds_out != nullptr && !takes_small_pipe(a);
+  const bool ds_after = a.ds_out != nullptr && !plan.self_finalizing;
   auto ds = [&]() -> hipError_t {
     if (!ds_after) return hipSuccess;
     return launch_destandardise(a.out_sample, a.ds_loc, a.ds_scale, a.total_dims, a.ds_out,
                                 stream);
   };
-  ForkStreams* f = (CWQ_ENCODE_SPLIT > 1 && a.block_off != nullptr && a.n_steps > 1 &&
-                    a.nb >= 2)
-                       ? fork_streams(stream)
-                       : nullptr;
+  const int k = encode_fork_parts(shape, a.n_steps);
+  ForkStreams* f = k > 1 ? fork_streams(stream) : nullptr;
   if (f == nullptr) {
     if ((e = encode_steps(a, stream, true)) != hipSuccess) return e;
     return ds();
   }
   // k parts of the block range: block-indexed arrays move by g0, the padded
   // per-block regions of the general kernel by 8 g0 / 12 g0 (their layout is
-  // off + 8 g / off + 12 g with absolute dim offsets off).  Launches of few
-  // long rows (the cooperative mode) overlap best in three parts, others in two
-  // (tools/stream_overlap.py).
-  const bool few_rows = a.nb * a.n_cand < (int64_t)CWQ_CSR_COOP_ROWS_PER_LANE * 1536 * 256;
-#ifndef CWQ_SPLIT_FEW
-#define CWQ_SPLIT_FEW 3  // parts of a cooperative (few long rows) launch
-#endif
-  int k = few_rows ? CWQ_SPLIT_FEW : 2;
-  k = k < CWQ_ENCODE_SPLIT ? k : CWQ_ENCODE_SPLIT;
-  k = (int64_t)k < a.nb ? k : (int)a.nb;
+  // off + 8 g / off + 12 g with absolute dim offsets off).
   if (a.ev_start && (e = hipEventRecord((hipEvent_t)a.ev_start, stream)) != hipSuccess) return e;
   if ((e = hipEventRecord(f->fork, stream)) != hipSuccess) return e;
   int forked = 0;

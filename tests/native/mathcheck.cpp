@@ -1,10 +1,13 @@
 // Host build of the product's device-math restatement (csrc/cwq_math.h) and of
-// the screening bound (csrc/cwq_screen.h).  tests/test_math_exhaustive.py
-// compares the former with the host glibc over the full Box-Muller input
-// domains; tests/test_screen_bound.py checks the latter's inequalities.
+// the screening bound (csrc/cwq_screen.h), and of the encode dispatch
+// (csrc/cwq_dispatch.h).  tests/test_math_exhaustive.py compares the first
+// with the host glibc over the full Box-Muller input domains;
+// tests/test_screen_bound.py checks the second's inequalities and
+// tests/test_encode_plan.py the third's table of shapes.
 // Test-only shim; not part of the product.
 #include <stdint.h>
 #include <vector>
+#include "../../compression_without_quantization_amd/csrc/cwq_dispatch.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_math.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_screen.h"
 
@@ -98,5 +101,31 @@ int mc_screen_row_bounds(int step0, int64_t d, const float* ls, const float* ss,
     out[3 * r + 2] = cwq::screen_row_upper(s, b.c1, b.bf);
   }
   return 1;
+}
+
+// The encode dispatch (csrc/cwq_dispatch.h) of one block range.
+// out = (path, coop, self_finalizing, fork parts); path in EncodePath's order.
+void mc_encode_plan(int csr, int64_t ud, int64_t max_d, int64_t nb, int64_t n_cand, int prune,
+                    int rows_wave, int n_steps, int* out) {
+  const cwq::EncodeShape s = {csr != 0, ud, max_d, nb, n_cand, prune, rows_wave != 0};
+  const cwq::EncodePlan p = cwq::encode_plan(s);
+  out[0] = (int)p.path; out[1] = p.coop; out[2] = p.self_finalizing;
+  out[3] = cwq::encode_fork_parts(s, n_steps);
+}
+int mc_has_screen_arrays(int csr, int64_t ud, int64_t nb) {
+  return cwq::has_screen_arrays(csr != 0, ud, nb);
+}
+int mc_has_long_block_records(int csr, int64_t max_d, int64_t nb) {
+  return cwq::has_long_block_records(csr != 0, max_d, nb);
+}
+int mc_few_rows(int64_t nb, int64_t n_cand) { return cwq::few_rows(nb, n_cand); }
+int mc_bucket_takes_rows_wave(int bits, int64_t dims, int64_t count, int prune) {
+  return cwq::bucket_takes_rows_wave(bits, dims, count, prune);
+}
+// (CWQ_CSR_COOP_ROWS_PER_LANE * lanes of the chip, CWQ_CSR_COOP_MIN_D, CWQ_CSR_LDS_DIMS)
+void mc_dispatch_consts(int64_t* out) {
+  out[0] = (int64_t)CWQ_CSR_COOP_ROWS_PER_LANE * cwq::kChipLanes;
+  out[1] = CWQ_CSR_COOP_MIN_D;
+  out[2] = CWQ_CSR_LDS_DIMS;
 }
 }

@@ -1,0 +1,265 @@
+"""The encode dispatch (csrc/cwq_dispatch.h, DESIGN.md "Encode dispatch") on the
+host: which path a launch_encode call of a given shape takes.
+
+Every path is bit-exact by design, so the GPU tests, which compare outputs with
+the oracle, cannot see a shape being rerouted.  These tests can: a table of
+shapes to paths, the thresholds, and every shape for which a GPU test names a
+path in its docstring."""
+import ctypes
+
+import pytest
+
+import encode_shapes as S
+
+ROWS_WAVE, UNIFORM_PRUNED, CSR_PRUNED, SMALL_PIPE, SMALL_THREE, EVAL = range(6)
+I64 = ctypes.c_int64
+
+
+@pytest.fixture(scope="module")
+def mc(mathcheck):
+    mathcheck.mc_encode_plan.argtypes = [ctypes.c_int, I64, I64, I64, I64, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_int)]
+    mathcheck.mc_encode_plan.restype = None
+    mathcheck.mc_has_screen_arrays.argtypes = [ctypes.c_int, I64, I64]
+    mathcheck.mc_has_long_block_records.argtypes = [ctypes.c_int, I64, I64]
+    mathcheck.mc_few_rows.argtypes = [I64, I64]
+    mathcheck.mc_bucket_takes_rows_wave.argtypes = [ctypes.c_int, I64, I64, ctypes.c_int]
+    mathcheck.mc_dispatch_consts.argtypes = [ctypes.POINTER(I64)]
+    mathcheck.mc_dispatch_consts.restype = None
+    return mathcheck
+
+
+def plan(mc, *, csr, bits, prune, nb=4, ud=0, max_d=None, rows_wave=False, n_steps=1):
+    """(path, coop, self_finalizing, fork parts) of one block range, as
+    encode_impl fills the shape: uniform blocks have max_d == ud."""
+    if max_d is None:
+        assert not csr
+        max_d = ud
+    out = (ctypes.c_int * 4)()
+    mc.mc_encode_plan(int(csr), ud, max_d, nb, 1 << bits, prune, int(rows_wave), n_steps, out)
+    return out[0], bool(out[1]), bool(out[2]), out[3]
+
+
+def part_sizes(nb, k):
+    """launch_encode's split of nb blocks in k parts."""
+    return [nb * (i + 1) // k - nb * i // k for i in range(k)]
+
+
+def csr_paths(mc, sizes, bits, n_steps, prune=2):
+    """Plans of a ragged call as launch_encode runs it: the whole call's plan
+    (prep, destandardise, fork) and the plan of every block range that
+    encode_steps is given (the parts of a forked call, else the whole)."""
+    nb, max_d = len(sizes), max(sizes)
+    whole = plan(mc, csr=True, bits=bits, prune=prune, nb=nb, max_d=max_d, n_steps=n_steps)
+    k = whole[3]
+    ranges = [plan(mc, csr=True, bits=bits, prune=prune, nb=n, max_d=max_d, n_steps=n_steps)
+              for n in (part_sizes(nb, k) if k > 1 else [nb])]
+    return whole, ranges
+
+
+TABLE = [
+    # uniform blocks: (ud, bits, prune, nb) -> path
+    (dict(csr=False, ud=32, bits=16, prune=1), UNIFORM_PRUNED),
+    (dict(csr=False, ud=32, bits=16, prune=2), UNIFORM_PRUNED),
+    (dict(csr=False, ud=32, bits=16, prune=0), EVAL),
+    # n_cand * 16 > 2^32 and no screening arrays for d = 64
+    (dict(csr=False, ud=64, bits=30, prune=2), EVAL),
+    (dict(csr=False, ud=64, bits=28, prune=2), UNIFORM_PRUNED),  # n_cand * 16 == 2^32
+    (dict(csr=False, ud=5, bits=13, prune=2), CSR_PRUNED),
+    (dict(csr=False, ud=5, bits=13, prune=1), EVAL),
+    (dict(csr=False, ud=12, bits=8, prune=2), SMALL_PIPE),
+    (dict(csr=False, ud=72, bits=8, prune=2), SMALL_THREE),
+    # ragged blocks
+    (dict(csr=True, max_d=64, bits=6, prune=2), SMALL_PIPE),
+    (dict(csr=True, max_d=64, bits=11, prune=2), SMALL_PIPE),
+    (dict(csr=True, max_d=64, bits=5, prune=2), EVAL),
+    (dict(csr=True, max_d=64, bits=12, prune=2), CSR_PRUNED),
+    (dict(csr=True, max_d=64, bits=8, prune=1), EVAL),
+    (dict(csr=True, max_d=64, bits=12, prune=1), EVAL),
+    (dict(csr=True, max_d=0, bits=8, prune=2), SMALL_PIPE),
+    (dict(csr=True, max_d=65, bits=8, prune=2), SMALL_THREE),
+    (dict(csr=True, max_d=130, bits=8, prune=2), SMALL_THREE),
+    (dict(csr=True, max_d=-1, bits=8, prune=2), SMALL_THREE),
+    (dict(csr=True, max_d=8, bits=8, prune=2, nb=(1 << 32) - 1), SMALL_PIPE),
+    (dict(csr=True, max_d=8, bits=8, prune=2, nb=1 << 32), SMALL_THREE),
+    # block lengths do not matter from 4,096 candidates on
+    (dict(csr=True, max_d=-1, bits=12, prune=2), CSR_PRUNED),
+    (dict(csr=True, max_d=4095, bits=30, prune=2), CSR_PRUNED),
+]
+
+
+@pytest.mark.parametrize("shape,path", TABLE)
+def test_shape_takes_path(mc, shape, path):
+    got, coop, self_finalizing, _ = plan(mc, **shape)
+    assert got == path, shape
+    assert self_finalizing == (path == SMALL_PIPE)
+    assert not coop or path == CSR_PRUNED
+
+
+@pytest.mark.parametrize("shape,path", TABLE)
+def test_rows_wave_overrides_every_path(mc, shape, path):
+    got, coop, self_finalizing, _ = plan(mc, rows_wave=True, **shape)
+    assert (got, coop, self_finalizing) == (ROWS_WAVE, False, False), shape
+
+
+def test_coop_threshold(mc):
+    """Cooperative rows below 8 candidate rows per lane of the chip."""
+    c = (I64 * 3)()
+    mc.mc_dispatch_consts(c)
+    limit = c[0]
+    assert limit == 8 * 1536 * 256
+    for nb, n_cand in ((limit - 1, 1), (1, limit - 1)):
+        assert nb * n_cand == limit - 1 and mc.mc_few_rows(nb, n_cand)
+    for nb, n_cand in ((limit, 1), (768, 1 << 12), (3, 1 << 20)):
+        assert nb * n_cand == limit and not mc.mc_few_rows(nb, n_cand)
+    n_cand = 1 << 12
+    assert limit % n_cand == 0
+    nb = limit // n_cand
+    below = plan(mc, csr=True, bits=12, prune=2, nb=nb - 1, max_d=300)
+    at = plan(mc, csr=True, bits=12, prune=2, nb=nb, max_d=300)
+    assert below[:2] == (CSR_PRUNED, True) and at[:2] == (CSR_PRUNED, False)
+    # nb * n_cand == limit - 1 has no power-of-two n_cand but 1: the flag is the
+    # general pruned path's alone, the fork's part count reads the same product
+    assert plan(mc, csr=True, bits=0, prune=2, nb=limit - 1, max_d=300, n_steps=2)[::3] == (EVAL, 3)
+    assert plan(mc, csr=True, bits=0, prune=2, nb=limit, max_d=300, n_steps=2)[::3] == (EVAL, 2)
+    # a small-candidate launch of few rows is not cooperative
+    assert plan(mc, csr=True, bits=8, prune=2, nb=2, max_d=300)[:2] == (SMALL_THREE, False)
+
+
+def test_fork_parts_and_per_part_coop(mc):
+    c = (I64 * 3)()
+    mc.mc_dispatch_consts(c)
+    nb = c[0] >> 12  # nb * 4,096 candidates: exactly at the few-rows limit
+    # the whole is not a few-rows launch, so it forks in two; each half is
+    whole, ranges = csr_paths(mc, [300] * nb, 12, 2)
+    assert whole[:2] == (CSR_PRUNED, False) and whole[3] == 2
+    assert [r[:2] for r in ranges] == [(CSR_PRUNED, True)] * 2
+    # few rows: three parts, never more parts than blocks
+    assert plan(mc, csr=True, bits=12, prune=2, nb=nb - 1, max_d=300, n_steps=2)[3] == 3
+    assert plan(mc, csr=True, bits=12, prune=2, nb=2, max_d=300, n_steps=2)[3] == 2
+    # no fork: one step, one block, uniform blocks
+    assert plan(mc, csr=True, bits=12, prune=2, nb=nb, max_d=300, n_steps=1)[3] == 1
+    assert plan(mc, csr=True, bits=12, prune=2, nb=1, max_d=300, n_steps=2)[3] == 1
+    assert plan(mc, csr=False, ud=5, bits=12, prune=2, nb=nb, n_steps=2)[3] == 1
+    # the fork does not depend on the path
+    assert plan(mc, csr=True, bits=8, prune=0, nb=9, max_d=64, n_steps=3)[3] == 3
+
+
+def test_has_screen_arrays(mc):
+    fast = set(range(8, 65, 8))
+    for d in list(range(0, 140)) + [1024, 1025, 4095]:
+        assert bool(mc.mc_has_screen_arrays(0, d, 3)) == (d not in fast), d
+        assert not mc.mc_has_screen_arrays(0, d, 0)  # no uniform block at all
+        for nb in (0, 3):
+            assert mc.mc_has_screen_arrays(1, 0, nb)  # ragged blocks: always
+            assert mc.mc_has_screen_arrays(1, d, nb)
+
+
+def test_has_long_block_records(mc):
+    c = (I64 * 3)()
+    mc.mc_dispatch_consts(c)
+    lds = c[2]
+    assert lds == 1024
+    for csr in (0, 1):
+        assert not mc.mc_has_long_block_records(csr, lds, 3)
+        assert mc.mc_has_long_block_records(csr, lds + 1, 3)
+    assert mc.mc_has_long_block_records(1, lds + 1, 0)
+    assert not mc.mc_has_long_block_records(0, lds + 1, 0)
+    assert not mc.mc_has_long_block_records(1, -1, 3) and not mc.mc_has_long_block_records(1, 0, 3)
+
+
+def test_bucket_rule(mc):
+    """cwq_greedy_encode_var: a bucket below 4,096 candidates whose mean block
+    reaches 256 dims takes the wave-per-row kernel, unless prune_mode is 0."""
+    c = (I64 * 3)()
+    mc.mc_dispatch_consts(c)
+    assert c[1] == 256
+    for count in (1, 3, 1000):
+        for prune in (1, 2):
+            assert mc.mc_bucket_takes_rows_wave(11, 256 * count, count, prune)
+            assert not mc.mc_bucket_takes_rows_wave(12, 256 * count, count, prune)
+            assert not mc.mc_bucket_takes_rows_wave(11, 256 * count - 1, count, prune)
+            assert mc.mc_bucket_takes_rows_wave(0, 256 * count, count, prune)
+            assert not mc.mc_bucket_takes_rows_wave(30, 4095 * count, count, prune)
+        assert not mc.mc_bucket_takes_rows_wave(11, 256 * count, count, 0)
+        assert not mc.mc_bucket_takes_rows_wave(0, 4095 * count, count, 0)
+
+
+# ---------------------------------------------------------------------------
+# the shapes for which a GPU test names a path
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("bits,n_steps", S.SMALL_PATH_BITS_STEPS)
+@pytest.mark.parametrize("name,path", [("pipeline", SMALL_PIPE), ("three_kernel", SMALL_THREE)])
+def test_small_path_adversarial_shapes(mc, name, path, bits, n_steps):
+    """test_gpu.py::test_small_path_adversarial: mode 2 takes the named
+    small-candidate path, in the whole call and in every part of a forked one;
+    mode 0 the exact kernel."""
+    sizes = S.SMALL_PATH_SIZES[name]
+    whole, ranges = csr_paths(mc, sizes, bits, n_steps)
+    assert whole[0] == path and whole[2] == (path == SMALL_PIPE)
+    assert whole[3] == (1 if n_steps == 1 else 3) and len(ranges) == whole[3]
+    for r in ranges:
+        assert r[:3] == (path, False, path == SMALL_PIPE)
+    whole, ranges = csr_paths(mc, sizes, bits, n_steps, prune=0)
+    assert {r[0] for r in ranges + [whole]} == {EVAL}
+
+
+@pytest.mark.parametrize("d,bits,nb", S.UNIFORM_GENERAL_PRUNED)
+def test_uniform_odd_d_general_pruned_shapes(mc, d, bits, nb):
+    """test_gpu.py::test_uniform_odd_d_general_pruned: no d of it is one the
+    uniform pruned kernel takes, so mode 2 runs the general pruned kernel
+    (cooperatively: few rows), unforked, and mode 0 the exact kernel."""
+    n_steps = S.UNIFORM_GENERAL_PRUNED_STEPS
+    assert plan(mc, csr=False, ud=d, bits=bits, prune=2, nb=nb, n_steps=n_steps) == \
+        (CSR_PRUNED, True, False, 1)
+    assert plan(mc, csr=False, ud=d, bits=bits, prune=0, nb=nb, n_steps=n_steps)[0] == EVAL
+    assert mc.mc_has_screen_arrays(0, d, nb)
+
+
+@pytest.mark.parametrize("sizes,bits,n_steps,kind", S.CSR_COOP)
+def test_csr_cooperative_rows_shapes(mc, sizes, bits, n_steps, kind):
+    """test_gpu.py::test_csr_cooperative_rows_vs_oracle: mode 2 runs the general
+    pruned kernel with cooperative rows in every block range, and its blocks
+    reach the length from which a row is walked cooperatively."""
+    c = (I64 * 3)()
+    mc.mc_dispatch_consts(c)
+    assert max(sizes) >= c[1]
+    whole, ranges = csr_paths(mc, sizes, bits, n_steps)
+    assert whole[:3] == (CSR_PRUNED, True, False)
+    assert whole[3] == (1 if n_steps == 1 else min(3, len(sizes)))
+    for r in ranges:
+        assert r[:3] == (CSR_PRUNED, True, False)
+    assert bool(mc.mc_has_long_block_records(1, max(sizes), len(sizes))) == (max(sizes) > c[2])
+    assert {r[0] for r in csr_paths(mc, sizes, bits, n_steps, prune=0)[1]} == {EVAL}
+
+
+@pytest.mark.parametrize("bits", S.ROWS_WAVE_BITS)
+@pytest.mark.parametrize("n_steps", [1, 3])
+def test_forced_rows_wave_shapes(mc, bits, n_steps):
+    """test_rows_wave_gpu.py: cwq_selftest_encode_rows_wave forces the
+    wave-per-row kernel (default options: prune_mode 2) in every block range."""
+    sizes = S.ROWS_WAVE_LENGTHS
+    nb, max_d = len(sizes), max(sizes)
+    whole = plan(mc, csr=True, bits=bits, prune=2, nb=nb, max_d=max_d, rows_wave=True,
+                 n_steps=n_steps)
+    assert whole[:3] == (ROWS_WAVE, False, False)
+    for n in part_sizes(nb, whole[3]):
+        assert plan(mc, csr=True, bits=bits, prune=2, nb=n, max_d=max_d, rows_wave=True,
+                    n_steps=n_steps)[:3] == (ROWS_WAVE, False, False)
+    # without the flag these bit counts would leave every long row to one lane
+    assert plan(mc, csr=True, bits=bits, prune=2, nb=nb, max_d=max_d)[0] in (EVAL, SMALL_THREE)
+
+
+@pytest.mark.parametrize("n_short", [0, 40])
+def test_encode_var_long_bucket_shapes(mc, n_short):
+    """test_rows_wave_gpu.py::test_encode_var_long_buckets: with no short block
+    every bucket takes the wave-per-row kernel; 40 blocks of 3 dims keep the
+    9-bit bucket off it; prune_mode 0 keeps every bucket off it."""
+    lens = S.LONG_LENS + [3] * n_short
+    bits = S.LONG_BITS + [9] * n_short
+    for b in set(bits):
+        mine = [n for n, bb in zip(lens, bits) if bb == b]
+        assert bool(mc.mc_bucket_takes_rows_wave(b, sum(mine), len(mine), 2)) == \
+            (not (n_short and b == 9)), b
+        assert not mc.mc_bucket_takes_rows_wave(b, sum(mine), len(mine), 0)

@@ -16,6 +16,8 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from encode_shapes import (CSR_COOP, SMALL_PATH_BITS_STEPS, SMALL_PATH_SIZES,
+                           UNIFORM_GENERAL_PRUNED, UNIFORM_GENERAL_PRUNED_STEPS)
 
 pytestmark = pytest.mark.gpu
 
@@ -809,7 +811,7 @@ def test_csr_pruned_adversarial(cwq, cwqlib, oracle, kind):
 @pytest.mark.parametrize("kind", ["normal", "far_locs", "huge_locs", "tiny_locs", "flat",
                                   "posterior_is_prior", "inf_scale", "zero_scale", "nan_scale",
                                   "nan_loc_one_dim"])
-@pytest.mark.parametrize("bits,n_steps", [(6, 1), (8, 2), (11, 1)])
+@pytest.mark.parametrize("bits,n_steps", SMALL_PATH_BITS_STEPS)
 @pytest.mark.parametrize("path", ["pipeline", "three_kernel"])
 def test_small_path_adversarial(cwq, cwqlib, oracle, kind, bits, n_steps, path):
     """The screened small-candidate paths (64 <= 2^b < 4096) on
@@ -818,10 +820,9 @@ def test_small_path_adversarial(cwq, cwqlib, oracle, kind, bits, n_steps, path):
     the gate (exact fallback); every mode equals the oracle.  "pipeline": every
     block <= 64 dims, so the small pipeline takes the launch (k_small_prep1,
     k_small_one, k_small_finalize); "three_kernel": a 130-dim block sends it to
-    k_small_prep/screen/survivors."""
+    k_small_prep/screen/survivors (test_encode_plan.py checks both claims)."""
     rng = np.random.default_rng(sum(map(ord, kind)) + bits)
-    sizes = [3, 20, 1, 45, 0, 7, 64, 130] if path == "three_kernel" else \
-        [3, 20, 1, 45, 0, 7, 64, 33, 64, 2, 0, 0, 5]
+    sizes = SMALL_PATH_SIZES[path]
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     D = int(off[-1])
     pl = (0.2 * rng.standard_normal(D)).astype(np.float32)
@@ -884,29 +885,20 @@ def test_csr_random_stress(cwq, cwqlib, trial):
     _assert_bits_equal(s2, s0, f"csr stress trial {trial}")
 
 
-@pytest.mark.parametrize("d,bits,nb", [(5, 13, 7), (12, 12, 4), (100, 14, 2), (72, 12, 3)])
+@pytest.mark.parametrize("d,bits,nb", UNIFORM_GENERAL_PRUNED)
 def test_uniform_odd_d_general_pruned(cwq, cwqlib, oracle, d, bits, nb):
     rng = np.random.default_rng(d * bits)
     tl, ts, pl, ps = _heavy_inputs(rng, nb * d)
     off = np.arange(nb + 1, dtype=np.int64) * d
-    wi, ws = oracle.greedy_encode(tl, ts, pl, ps, off, bits, 2, 11)
+    n_steps = UNIFORM_GENERAL_PRUNED_STEPS
+    wi, ws = oracle.greedy_encode(tl, ts, pl, ps, off, bits, n_steps, 11)
     for mode in (0, 2):
-        gi, gs = _uniform_encode(cwq, cwqlib, tl, ts, pl, ps, d, bits, 2, 11, 1.0, mode)
+        gi, gs = _uniform_encode(cwq, cwqlib, tl, ts, pl, ps, d, bits, n_steps, 11, 1.0, mode)
         assert np.array_equal(gi, wi), (d, mode)
         _assert_bits_equal(gs, ws, f"uniform d={d} mode {mode}")
 
 
-@pytest.mark.parametrize("sizes,bits,n_steps,kind", [
-    ([4095, 2000, 300, 257], 14, 2, "normal"),   # few long rows: cooperative 16-lane rows
-    ([1500, 255, 256, 40], 13, 3, "normal"),     # coop and per-lane rows in one launch
-    ([600] * 3, 14, 1, "flat"),                  # near-ties: survivor overflow, redo, exact
-    ([700, 900], 12, 2, "heavy"),
-    # row lengths around the loops' unit strides (4 units per lane of a 16-lane
-    # slot: 64 units per iteration; 2 units per iteration of a per-lane row)
-    # and the LDS / visit-order-record boundary at 1024 dims
-    ([256, 257, 259, 255, 1021, 1024, 1025, 1027], 12, 2, "normal"),
-    ([1087, 1089, 4093, 513, 511, 7, 3, 1], 12, 2, "heavy"),
-])
+@pytest.mark.parametrize("sizes,bits,n_steps,kind", CSR_COOP)
 def test_csr_cooperative_rows_vs_oracle(cwq, cwqlib, oracle, sizes, bits, n_steps, kind):
     rng = np.random.default_rng(sum(sizes) * bits)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)

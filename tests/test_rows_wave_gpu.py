@@ -7,14 +7,13 @@ import numpy as np
 import pytest
 import torch
 
+from encode_shapes import LONG_BITS, LONG_LENS, ROWS_WAVE_BITS
+from encode_shapes import ROWS_WAVE_LENGTHS as LENGTHS
+
 pytestmark = pytest.mark.gpu
 
 SEED = 2147483647 - 5  # seed + base + g wraps past 2^31 - 1 inside every call below
 BASE = 3               # block_id_base
-# the 248-dim chunk boundary, the 8-wide vector / tail boundary, odd lengths (a
-# Philox block straddles two rows), an empty block between non-empty ones, and
-# the longest group of the PLN codec
-LENGTHS = [1, 3, 0, 4, 5, 7, 8, 9, 247, 4095, 248, 249, 255, 256, 257, 496, 1023, 1025]
 
 
 @pytest.fixture(scope="module")
@@ -88,7 +87,7 @@ def test_inputs_cover_the_paths():
 # (18 .. 576), more rows than the grid holds (36,864 > 4 * 2,048 waves)
 @pytest.mark.parametrize("rho", [1.0, 0.7])
 @pytest.mark.parametrize("n_steps", [1, 3])
-@pytest.mark.parametrize("n_bits", [0, 1, 5, 9, 11])
+@pytest.mark.parametrize("n_bits", ROWS_WAVE_BITS)
 def test_rows_wave_vs_oracle(cwqlib, oracle, n_bits, n_steps, rho):
     off, tl, ts, pl, ps = _ragged()
     want_idx, want_sample = oracle.greedy_encode(tl, ts, pl, ps, off, n_bits, n_steps,
@@ -125,10 +124,6 @@ def test_rows_wave_adversarial(cwqlib, oracle):
 # ---------------------------------------------------------------------------
 # (c) cwq_greedy_encode_var sends buckets of long blocks there
 # ---------------------------------------------------------------------------
-LONG_LENS = [4095, 300, 256, 1024, 2049, 700]
-LONG_BITS = [9, 9, 1, 5, 9, 11]
-
-
 @functools.lru_cache(maxsize=None)
 def _long(n_short):
     rng = np.random.Generator(np.random.PCG64(31))
