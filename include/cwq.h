@@ -40,6 +40,15 @@
  *     A multi-step CSR encode forks its two block halves onto two library
  *     streams (created once per host thread and device) and joins them back
  *     with events on the caller's stream.
+ *   - `workspace` (device) and `host_workspace` (host) are scratch of at least
+ *     the entry point's *_workspace_size bytes: their contents on entry are
+ *     ignored (they may be uninitialised, or another call's leftovers) and are
+ *     unspecified on return.  Output buffers are written in full, whatever they
+ *     held: every element a call defines is stored (an empty block's index is
+ *     0; out_sample is a sum over steps that starts from 0, not from the
+ *     buffer); only capacity past the returned counts (bits_cap, starts_cap,
+ *     out_cap) is left untouched.  tests/test_workspace_state_gpu.py holds
+ *     every entry point to this.
  *   - Blocks ("groups" in the reference) are described in CSR form:
  *     block g covers dims [block_off[g], block_off[g+1]) of the flat arrays;
  *     block_off is a device int64 array of nb+1 entries.  The *_uniform

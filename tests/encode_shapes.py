@@ -36,3 +36,20 @@ ROWS_WAVE_LENGTHS = [1, 3, 0, 4, 5, 7, 8, 9, 247, 4095, 248, 249, 255, 256, 257,
 ROWS_WAVE_BITS = [0, 1, 5, 9, 11]
 LONG_LENS = [4095, 300, 256, 1024, 2049, 700]
 LONG_BITS = [9, 9, 1, 5, 9, 11]
+
+# test_workspace_state_gpu.py: the smallest shape at which each encoder path
+# exists.  Uniform shapes are (d, bits, nb, n_steps), ragged ones
+# (sizes, bits, n_steps).  The tile-queue shape is the fast pruned kernel with
+# its tile queue on: 2^12 candidates make one tile of 4,096 per block
+# (k_encode_prune draws tiles from the workspace counter from 4,096 candidates
+# per tile and more than 1,536 tiles on), and 16,384 blocks make 16,384 tiles.
+WS_UNIFORM_PRUNED = (16, 12, 16, 1)        # prune_mode 1 and 2; prune_mode 0: the exact kernel
+WS_TILE_QUEUE = (16, 12, 16384, 1)
+WS_EVAL_RAGGED = ([3, 20, 0, 45], 4, 2)    # 16 candidates: below the small paths' 64
+WS_UNIFORM_GENERAL = [(5, 13, 7, 2), (100, 14, 2, 2)]  # rows of UNIFORM_GENERAL_PRUNED
+# per-lane rows (every block below 256 dims), constants in LDS; two steps and
+# more than one block: the call forks
+WS_CSR_LANE = ([5, 12, 100, 72, 33, 0, 255], 12, 2)
+WS_CSR_ALL = CSR_COOP[4][:3]               # cooperative rows, records, the 1,024-dim boundary
+WS_SMALL = {"pipeline": (SMALL_PATH_SIZES["pipeline"], 8, 2),
+            "three_kernel": (SMALL_PATH_SIZES["three_kernel"], 8, 2)}

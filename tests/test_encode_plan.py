@@ -263,3 +263,57 @@ def test_encode_var_long_bucket_shapes(mc, n_short):
         assert bool(mc.mc_bucket_takes_rows_wave(b, sum(mine), len(mine), 2)) == \
             (not (n_short and b == 9)), b
         assert not mc.mc_bucket_takes_rows_wave(b, sum(mine), len(mine), 0)
+
+
+# ---------------------------------------------------------------------------
+# test_workspace_state_gpu.py: each case's shape takes the path its name says
+# ---------------------------------------------------------------------------
+def test_workspace_state_uniform_shapes(mc):
+    for d, bits, nb, n_steps in (S.WS_UNIFORM_PRUNED, S.WS_TILE_QUEUE):
+        for prune in (1, 2):
+            assert plan(mc, csr=False, ud=d, bits=bits, prune=prune, nb=nb, n_steps=n_steps) == \
+                (UNIFORM_PRUNED, False, False, 1)
+        assert plan(mc, csr=False, ud=d, bits=bits, prune=0, nb=nb, n_steps=n_steps) == \
+            (EVAL, False, False, 1)
+        assert not mc.mc_has_screen_arrays(0, d, nb)  # keys, tile queue, shard constants only
+    # the tile queue's own conditions (launch_prune_t): one tile of >= 4,096
+    # candidates per block, more tiles than the 1,536 resident workgroups
+    d, bits, nb, _ = S.WS_TILE_QUEUE
+    assert (1 << bits) >= 4096 and nb > 1536 and nb >= 16384
+    d, bits, nb, _ = S.WS_UNIFORM_PRUNED
+    assert nb <= 1536
+    for d, bits, nb, n_steps in S.WS_UNIFORM_GENERAL:
+        assert (d, bits, nb) in S.UNIFORM_GENERAL_PRUNED
+        assert n_steps == S.UNIFORM_GENERAL_PRUNED_STEPS
+
+
+def test_workspace_state_ragged_shapes(mc):
+    c = (I64 * 3)()
+    mc.mc_dispatch_consts(c)
+    coop_min_d, lds = c[1], c[2]
+    # the exact kernel: too few candidates for any screened path; forked (two steps)
+    sizes, bits, n_steps = S.WS_EVAL_RAGGED
+    whole, ranges = csr_paths(mc, sizes, bits, n_steps)
+    assert whole[0] == EVAL and whole[3] == 3 and {r[0] for r in ranges} == {EVAL}
+    assert 0 in sizes
+    # per-lane rows: the general pruned kernel, no block long enough for a
+    # cooperative row or a record, forked in three
+    sizes, bits, n_steps = S.WS_CSR_LANE
+    whole, ranges = csr_paths(mc, sizes, bits, n_steps)
+    assert whole[0] == CSR_PRUNED and whole[3] == 3 and len(ranges) == 3
+    assert {r[0] for r in ranges} == {CSR_PRUNED}
+    assert max(sizes) < coop_min_d and 0 in sizes
+    assert not mc.mc_has_long_block_records(1, max(sizes), len(sizes))
+    # every sub-case in one call: cooperative rows, blocks on both sides of the
+    # LDS / record boundary
+    sizes, bits, n_steps = S.WS_CSR_ALL
+    whole, ranges = csr_paths(mc, sizes, bits, n_steps)
+    assert whole[:3] == (CSR_PRUNED, True, False) and whole[3] == 3
+    assert [r[:2] for r in ranges] == [(CSR_PRUNED, True)] * 3
+    assert min(sizes) < coop_min_d <= sorted(sizes)[1] and lds in sizes
+    assert any(s > lds for s in sizes) and mc.mc_has_long_block_records(1, max(sizes), len(sizes))
+    for name, path in (("pipeline", SMALL_PIPE), ("three_kernel", SMALL_THREE)):
+        sizes, bits, n_steps = S.WS_SMALL[name]
+        whole, ranges = csr_paths(mc, sizes, bits, n_steps)
+        assert whole[0] == path and whole[2] == (path == SMALL_PIPE) and whole[3] == 3
+        assert {r[:3] for r in ranges} == {(path, False, path == SMALL_PIPE)}

@@ -1,0 +1,874 @@
+"""GPU: no result may depend on what a workspace, an output buffer or the host
+staging held on entry (include/cwq.h: "contents on entry are ignored").
+
+Every entry point of libcwq.so works in memory its caller hands in
+uninitialised; the argmax keys, tile-queue counters, survivor lists, zero pads,
+visit orders, sort histograms and bit offsets that live there have to be
+written by the library itself on every call and every step (DESIGN.md
+"Workspace state").  Two kinds of test:
+
+* each call under tests/poison.py's three patterns (0x00, 0xFF, seeded random
+  bytes in every buffer the wrappers allocate, outputs included): indices are
+  integer-equal and samples, streams and bit counts bit-equal across the three
+  runs and to the CPU oracle -- which also proves every output element was
+  written (an empty block's index 0, a zero-length item);
+* the encoders back to back on one workspace that nothing clears, so each
+  call's arrays land on the previous call's leftovers at other offsets, once
+  with a synchronise between calls and once enqueued on one non-default stream.
+
+The shapes are the smallest at which each encoder path exists
+(tests/encode_shapes.py; tests/test_encode_plan.py checks on the CPU that each
+takes the path its case names).
+"""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import encode_shapes as S
+from poison import poisoned
+
+pytestmark = pytest.mark.gpu
+
+PATTERNS = (0x00, 0xFF, "random")
+SEED, BASE = 42, 3
+_ORIGINALS = (torch.empty, torch.empty_like, np.empty)
+
+
+@pytest.fixture(scope="module")
+def cwq(cwqlib):
+    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
+    import compression_without_quantization_amd as C
+    C.coded_greedy_sampler.VERBOSE = False
+    C.coded_importance_sampler.VERBOSE = False
+    return C
+
+
+# ---------------------------------------------------------------------------
+# helpers
+# ---------------------------------------------------------------------------
+def _canon(x):
+    """An output in a form == compares bit for bit: float arrays as their bit
+    patterns, integer arrays as int64, containers element by element."""
+    if isinstance(x, (str, bytes, int, type(None))):
+        return x
+    if isinstance(x, (tuple, list)):
+        return tuple(_canon(v) for v in x)
+    if isinstance(x, dict):
+        return tuple((k, _canon(v)) for k, v in sorted(x.items()))
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]).copy()
+    return a.astype(np.int64)
+
+
+def _same(got, want, what):
+    if isinstance(want, tuple):
+        assert isinstance(got, tuple) and len(got) == len(want), f"{what}: {len(got)} parts"
+        for k, (g, w) in enumerate(zip(got, want)):
+            _same(g, w, f"{what}[{k}]")
+    elif isinstance(want, np.ndarray):
+        assert isinstance(got, np.ndarray) and got.shape == want.shape, \
+            f"{what}: shape {getattr(got, 'shape', None)} != {want.shape}"
+        bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+        assert bad.size == 0, f"{what}: {bad.size} of {want.size} differ, first at {bad[:8]}"
+    else:
+        assert got == want, f"{what}: {got!r} != {want!r}"
+
+
+def _drop_wrapper_caches():
+    """The wrappers keep host staging between calls (a thread's page-locked
+    scratch, the deferred calls' pools): dropped, so each pattern's run takes
+    its staging through the patched allocators again."""
+    import compression_without_quantization_amd.coded_greedy_sampler as G
+    for name in ("pinned", "buf", "decode_pending"):
+        if hasattr(G._scratch, name):
+            delattr(G._scratch, name)
+    del G._bits_free[:]
+    del G._pinned_free[:]
+
+
+def _three(run, what, need=None, check=None):
+    """run() under each pattern; the three results must agree.  ``need``: the
+    entry point's workspace size, which a poisoned device uint8 buffer must
+    reach (entry points without a workspace pass ``check(filled)`` instead).
+    Returns the 0x00 result."""
+    out = {}
+    for p in PATTERNS:
+        _drop_wrapper_caches()
+        with poisoned(p) as filled:
+            res = run()
+            torch.cuda.synchronize()
+            out[p] = _canon(res)
+        if need is not None:
+            filled.assert_workspace(int(need), f"{what} ({p!r})")
+        if check is not None:
+            assert check(filled), f"{what} ({p!r}): its buffers were not poisoned: {filled.buffers}"
+    for p in PATTERNS[1:]:
+        _same(out[p], out[0x00], f"{what}: pattern {p!r} against 0x00")
+    return out[0x00]
+
+
+def test_poison_reaches_device_and_pinned_memory():
+    """The fill itself, where the CPU suite cannot check it."""
+    for p in PATTERNS:
+        with poisoned(p) as filled:
+            d = torch.empty(1000, dtype=torch.float32, device="cuda")
+            h = torch.empty(1000, dtype=torch.int32, pin_memory=True)
+            z = torch.empty(0, dtype=torch.uint8, device="cuda")
+            s = torch.empty((), dtype=torch.int64, device="cuda")
+        assert filled.count("device") == 3 and filled.count("pinned", torch.int32, 4000) == 1
+        assert z.numel() == 0 and s.dim() == 0
+        db, hb = d.cpu().numpy().view(np.uint8), h.numpy().view(np.uint8)
+        if p == "random":
+            assert len(set(db.tolist())) > 200 and len(set(hb.tolist())) > 200
+            assert not np.array_equal(db, hb)
+        else:
+            assert (db == p).all() and (hb == p).all()
+            assert int(s.item()) == (0 if p == 0 else -1)
+    assert (torch.empty, torch.empty_like, np.empty) == _ORIGINALS
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _values(rng, D):
+    tl = rng.standard_normal(D).astype(np.float32)
+    ts = rng.uniform(0.3, 0.9, D).astype(np.float32)
+    pl = (0.25 * rng.standard_normal(D)).astype(np.float32)
+    ps = rng.uniform(0.8, 1.3, D).astype(np.float32)
+    return tl, ts, pl, ps
+
+
+def _offsets(sizes):
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------
+# the encoder's cases
+# ---------------------------------------------------------------------------
+def _uniform(shape, prune):
+    d, bits, nb, n_steps = shape
+    return dict(d=d, sizes=None, bits=bits, nb=nb, n_steps=n_steps, prune=prune)
+
+
+def _csr(shape):
+    sizes, bits, n_steps = shape
+    return dict(d=None, sizes=list(sizes), bits=bits, nb=len(sizes), n_steps=n_steps, prune=None)
+
+
+ENC_CASES = {
+    "uniform_pruned_mode1": _uniform(S.WS_UNIFORM_PRUNED, 1),
+    "uniform_pruned_mode2": _uniform(S.WS_UNIFORM_PRUNED, 2),
+    "tile_queue": _uniform(S.WS_TILE_QUEUE, None),
+    "eval_uniform": _uniform(S.WS_UNIFORM_PRUNED, 0),
+    "eval_ragged": _csr(S.WS_EVAL_RAGGED),
+    "general_d5": _uniform(S.WS_UNIFORM_GENERAL[0], None),
+    "general_d100": _uniform(S.WS_UNIFORM_GENERAL[1], None),
+    "csr_lane_rows": _csr(S.WS_CSR_LANE),
+    "csr_all": _csr(S.WS_CSR_ALL),
+    "small_pipe": _csr(S.WS_SMALL["pipeline"]),
+    "small_three": _csr(S.WS_SMALL["three_kernel"]),
+}
+# the oracle scores every candidate of every block on the CPU: the tile-queue
+# shape's 2^30 normals are checked on every 16th block (and whole against the
+# exact kernel, which "eval_uniform" pins to the oracle at the same d and bits)
+ORACLE_STRIDE = {"tile_queue": 16}
+
+
+@functools.lru_cache(maxsize=None)
+def _enc_case(name):
+    """The case with its inputs on the host and on the device, and its
+    workspace size."""
+    from compression_without_quantization_amd import _lib
+    from compression_without_quantization_amd.synthetic import make_blocks
+    c = dict(ENC_CASES[name], name=name)
+    lib = _lib.load()
+    if c["sizes"] is None:
+        b = make_blocks(c["nb"], c["d"], c["bits"], seed=77 + c["d"] + c["bits"])
+        host = tuple(np.ascontiguousarray(b[k].reshape(-1)) for k in
+                     ("post_loc", "post_scale", "prior_loc", "prior_scale"))
+        c["off"] = np.arange(c["nb"] + 1, dtype=np.int64) * c["d"]
+        c["need"] = int(lib.cwq_greedy_encode_uniform_workspace_size(c["nb"], c["d"]))
+    else:
+        c["off"] = _offsets(c["sizes"])
+        rng = np.random.Generator(np.random.PCG64(1000 + sum(c["sizes"]) + c["bits"]))
+        host = _values(rng, int(c["off"][-1]))
+        c["need"] = int(lib.cwq_greedy_encode_workspace_size(c["nb"], int(c["off"][-1]),
+                                                             max(c["sizes"])))
+        c["off_dev"] = _dev(c["off"])
+    c["D"] = int(c["off"][-1])
+    c["host"] = host
+    c["dev"] = tuple(_dev(a) for a in host)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _enc_want(name):
+    """(block numbers, idx, sample of those blocks' dims) from the CPU oracle."""
+    from oracle import oracle as O
+    c = _enc_case(name)
+    tl, ts, pl, ps = c["host"]
+    off = c["off"]
+    stride = ORACLE_STRIDE.get(name, 1)
+    if stride == 1:
+        wi, ws = O.greedy_encode(tl, ts, pl, ps, off, c["bits"], c["n_steps"], SEED, 1.0, BASE)
+        return np.arange(c["nb"]), wi, ws
+    blocks = np.unique(np.concatenate([np.arange(0, c["nb"], stride), [c["nb"] - 1]]))
+    d = c["d"]
+    dims = (blocks[:, None] * d + np.arange(d)[None, :]).reshape(-1)
+    # block g alone, numbered g: the same seed as inside the whole call
+    wi = np.zeros((blocks.size, c["n_steps"]), np.int32)
+    ws = np.zeros(blocks.size * d, np.float32)
+    for k, g in enumerate(blocks):
+        sl = slice(g * d, (g + 1) * d)
+        i, s = O.greedy_encode(tl[sl], ts[sl], pl[sl], ps[sl], [0, d], c["bits"], c["n_steps"],
+                               SEED, 1.0, BASE + int(g))
+        wi[k], ws[k * d:(k + 1) * d] = i[0], s
+    assert np.array_equal(dims, np.concatenate([np.arange(g * d, (g + 1) * d) for g in blocks]))
+    return blocks, wi, ws
+
+
+def _check_enc(name, got, what):
+    """got = _canon((idx, sample)) against the oracle."""
+    c = _enc_case(name)
+    blocks, wi, ws = _enc_want(name)
+    idx, sample = got
+    assert idx.shape == (c["nb"], c["n_steps"]) and sample.shape == (c["D"],)
+    _same(idx[blocks], _canon(wi), f"{what}: indices against the oracle")
+    if blocks.size == c["nb"]:
+        _same(sample, _canon(ws), f"{what}: sample against the oracle")
+    else:
+        d = c["d"]
+        dims = (blocks[:, None] * d + np.arange(d)[None, :]).reshape(-1)
+        _same(sample[dims], _canon(ws), f"{what}: sample against the oracle")
+    if c["sizes"] is not None:  # an empty block gets no key and still emits index 0
+        empty = np.flatnonzero(np.diff(c["off"]) == 0)
+        assert (idx[empty] == 0).all(), f"{what}: empty blocks {empty} -> {idx[empty]}"
+    assert idx.min() >= 0 and idx.max() < (1 << c["bits"])
+
+
+def _encode(cwq, c):
+    """encode_blocks with explicit outputs; inside ``poisoned`` they and the
+    wrapper's workspace hold the pattern."""
+    tl, ts, pl, ps = c["dev"]
+    kw = dict(rho=1.0, block_id_base=BASE, prune_mode=c["prune"])
+    if c["sizes"] is None:
+        kw["block_dim"] = c["d"]
+    else:
+        kw["block_off"] = c["off"]
+    kw["out_idx"] = torch.empty((c["nb"], c["n_steps"]), dtype=torch.int32, device="cuda")
+    kw["out_sample"] = torch.empty(c["D"], dtype=torch.float32, device="cuda")
+    idx, sample = cwq.encode_blocks(tl, ts, pl, ps, c["bits"], c["n_steps"], SEED, **kw)
+    assert idx.data_ptr() == kw["out_idx"].data_ptr()
+    assert sample.data_ptr() == kw["out_sample"].data_ptr()
+    return idx, sample
+
+
+_CLEAN = {}  # case name -> its 0x00 result (section 4 compares with it)
+
+
+def _clean_encode(cwq, name):
+    if name not in _CLEAN:
+        with poisoned(0x00):
+            res = _encode(cwq, _enc_case(name))
+            torch.cuda.synchronize()
+            _CLEAN[name] = _canon(res)
+    return _CLEAN[name]
+
+
+@pytest.mark.parametrize("name", list(ENC_CASES))
+def test_encode_blocks_ignores_buffer_contents(cwq, oracle, name):
+    c = _enc_case(name)
+    got = _three(lambda: _encode(cwq, c), f"encode_blocks {name}", need=c["need"])
+    _CLEAN[name] = got
+    _check_enc(name, got, name)
+    if name == "tile_queue":  # every block, against the exact kernel's clean run
+        with poisoned(0x00):
+            ref = _canon(_encode(cwq, dict(c, prune=0)))
+        _same(got, ref, "tile queue against the exact kernel")
+
+
+# ---------------------------------------------------------------------------
+# stale state from a real call: one workspace, nothing cleared between calls
+# ---------------------------------------------------------------------------
+STALE_ORDER = ["csr_all", "small_pipe", "small_three", "tile_queue", "eval_uniform",
+               "general_d5", "csr_lane_rows", "csr_all"]
+
+
+def _encode_capi(lib, c, ws, stream):
+    """The C ABI itself on pre-uploaded inputs: nothing here waits for the
+    device, so calls queued on one stream are ordered by the stream alone.
+    Returns the outputs and the tensors that must outlive the queued work."""
+    tl, ts, pl, ps = c["dev"]
+    idx = torch.full((c["nb"], c["n_steps"]), -77, dtype=torch.int32, device="cuda")
+    sample = torch.full((c["D"],), float("nan"), dtype=torch.float32, device="cuda")
+    opts = None
+    if c["prune"] is not None:
+        from compression_without_quantization_amd import _lib
+        opts = _lib.options(c["prune"])
+    common = (c["bits"], c["n_steps"], SEED, 1.0, BASE, idx.data_ptr(), sample.data_ptr(),
+              ws.data_ptr(), ws.numel(), opts, stream)
+    if c["sizes"] is None:
+        rc = lib.cwq_greedy_encode_uniform(tl.data_ptr(), ts.data_ptr(), pl.data_ptr(),
+                                           ps.data_ptr(), c["nb"], c["d"], *common)
+    else:
+        rc = lib.cwq_greedy_encode(tl.data_ptr(), ts.data_ptr(), pl.data_ptr(), ps.data_ptr(),
+                                   c["off_dev"].data_ptr(), c["nb"], c["D"], max(c["sizes"]),
+                                   *common)
+    assert rc == 0, lib.cwq_last_error()
+    return (idx, sample), (opts,)
+
+
+@pytest.mark.parametrize("mode", ["synchronised", "one_stream"])
+def test_encode_blocks_on_a_stale_workspace(cwq, cwqlib, oracle, mode):
+    """The encoder paths back to back on one buffer sized for the largest: nb
+    and total_dims differ from call to call, so every array of a call lies on
+    other arrays of the call before it."""
+    cases = [_enc_case(n) for n in STALE_ORDER]
+    assert len({(c["nb"], c["D"]) for c in cases}) >= 6
+    ws = torch.empty(max(c["need"] for c in cases), dtype=torch.uint8, device="cuda")
+    runs = []
+    if mode == "synchronised":
+        st = torch.cuda.current_stream().cuda_stream
+        for c in cases:
+            runs.append(_encode_capi(cwqlib, c, ws, st))
+            torch.cuda.synchronize()
+    else:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):  # the output fills run on it too
+            assert torch.cuda.current_stream() == side
+            for c in cases:
+                runs.append(_encode_capi(cwqlib, c, ws, side.cuda_stream))
+        side.synchronize()
+        torch.cuda.current_stream().wait_stream(side)
+    for k, (name, (out, _keep)) in enumerate(zip(STALE_ORDER, runs)):
+        got = _canon(out)
+        _same(got, _clean_encode(cwq, name), f"call {k} ({name}, {mode}) against its clean run")
+        _check_enc(name, got, f"call {k} ({name}, {mode})")
+
+
+# ---------------------------------------------------------------------------
+# encode_blocks_var: uniform, ragged, and the wave-per-row buckets
+# ---------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _var_case(kind):
+    import test_rows_wave_gpu as RW
+    import test_varbits_csr_gpu as VC
+    import test_varbits_gpu as VB
+    from compression_without_quantization_amd import _lib
+    from compression_without_quantization_amd.varbits import encode_var_workspace_bytes
+    lib = _lib.load()
+    if kind == "uniform":
+        nb, d, n_steps, max_bits = VB.SHAPES[0]
+        assert n_steps == 2
+        tl, ts, pl, ps, bits = VB._inputs(nb, d, max_bits)
+        want = VB._oracle_blocks(nb, d, n_steps, max_bits, 1.0)
+        kw = dict(block_dim=d)
+        need = encode_var_workspace_bytes(nb, d, n_steps)
+        seed, off = VB.SEED, np.arange(nb + 1, dtype=np.int64) * d
+    elif kind == "csr":
+        off, tl, ts, pl, ps, bits = VC._ragged()
+        n_steps, seed = 2, VC.SEED
+        want = VC._oracle_ragged("ragged", n_steps, 1.0, VC.BASE)
+        kw = dict(block_off=off, block_id_base=VC.BASE)
+        need = int(lib.cwq_greedy_encode_var_workspace_size(
+            len(bits), int(off[-1]), int(np.diff(off).max()), n_steps))
+    else:  # every bucket's mean block reaches 256 dims: k_encode_rows_wave
+        assert S.LONG_LENS and S.LONG_BITS
+        off, tl, ts, pl, ps, bits = RW._long(0)
+        n_steps, seed = 3, RW.SEED
+        want = RW._oracle_long(0, n_steps)
+        kw = dict(block_off=off)
+        need = int(lib.cwq_greedy_encode_var_workspace_size(
+            len(bits), int(off[-1]), int(np.diff(off).max()), n_steps))
+    return dict(kind=kind, args=tuple(_dev(a) for a in (tl, ts, pl, ps)), bits=bits,
+                n_steps=n_steps, seed=seed, kw=kw, need=need, want=want, off=off,
+                nb=len(bits), D=int(off[-1]))
+
+
+def _encode_var(cwq, c, workspace=None):
+    out_idx = torch.empty((c["nb"], c["n_steps"]), dtype=torch.int32, device="cuda")
+    out_sample = torch.empty(c["D"], dtype=torch.float32, device="cuda")
+    return cwq.encode_blocks_var(*c["args"], c["bits"], c["n_steps"], c["seed"], out_idx=out_idx,
+                                 out_sample=out_sample, workspace=workspace, **c["kw"])
+
+
+def _check_var(c, got, what):
+    wi, ws = c["want"]
+    _same(got, (_canon(wi), _canon(ws)), f"{what} against the oracle")
+    empty = np.flatnonzero(np.diff(c["off"]) == 0)
+    assert (got[0][empty] == 0).all() and (got[0][c["bits"] == 0] == 0).all()
+
+
+_CLEAN_VAR = {}
+
+
+@pytest.mark.parametrize("kind", ["uniform", "csr", "rows_wave"])
+def test_encode_blocks_var_ignores_buffer_contents(cwq, oracle, kind):
+    c = _var_case(kind)
+    got = _three(lambda: _encode_var(cwq, c), f"encode_blocks_var {kind}", need=c["need"])
+    _CLEAN_VAR[kind] = got
+    _check_var(c, got, kind)
+
+
+@pytest.mark.parametrize("mode", ["synchronised", "one_stream"])
+def test_encode_blocks_var_on_a_stale_workspace(cwq, oracle, mode):
+    """Both forms and the wave-per-row buckets on one buffer.  (These calls
+    wait for the device once themselves: the bucket sizes decide their
+    launches.)"""
+    order = ["uniform", "csr", "rows_wave", "uniform", "csr"]
+    cases = [_var_case(k) for k in order]
+    ws = torch.empty(max(c["need"] for c in cases), dtype=torch.uint8, device="cuda")
+    if mode == "synchronised":
+        runs = []
+        for c in cases:
+            runs.append(_encode_var(cwq, c, ws))
+            torch.cuda.synchronize()
+    else:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            runs = [_encode_var(cwq, c, ws) for c in cases]
+        side.synchronize()
+        torch.cuda.current_stream().wait_stream(side)
+    for k, (kind, c, out) in enumerate(zip(order, cases, runs)):
+        got = _canon(out)
+        if kind not in _CLEAN_VAR:
+            with poisoned(0x00):
+                _CLEAN_VAR[kind] = _canon(_encode_var(cwq, c))
+        _same(got, _CLEAN_VAR[kind], f"call {k} ({kind}, {mode}) against its clean run")
+        _check_var(c, got, f"call {k} ({kind}, {mode})")
+
+
+# ---------------------------------------------------------------------------
+# block_bits, the packed stream, the decoders, the RNG
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("form", ["uniform", "csr"])
+def test_block_bits_ignores_buffer_contents(cwq, oracle, form):
+    rng = np.random.Generator(np.random.PCG64(2024))
+    if form == "uniform":
+        nb, d, n_steps = 37, 7, 1
+        lens = np.full(nb, d)
+    else:
+        nb, n_steps = 41, 3
+        lens = rng.choice(np.array([0, 1, 3, 7, 64, 65, 200]), nb)
+        lens[:3] = [200, 0, 65]
+    off = _offsets(lens)
+    D = int(off[-1])
+    blk = np.repeat(np.arange(nb), lens)
+    shift = rng.uniform(0.0, 1.5, nb)[blk] / np.sqrt(np.maximum(lens[blk], 1) / 8.0)
+    ql = (shift * rng.standard_normal(D)).astype(np.float32)
+    qs = (rng.uniform(0.5, 1.0, nb)[blk] * rng.uniform(0.8, 1.2, D)).astype(np.float32)
+    pl, ps = np.zeros(D, np.float32), np.ones(D, np.float32)
+    kl = oracle.kl_normal_normal(ql, qs, pl, ps)
+    Sg = np.array([np.cumsum(kl[off[g]:off[g + 1]].astype(np.float64))[-1] if lens[g] else 0.0
+                   for g in range(nb)])
+    x = (Sg / np.log(2.0) + 1.0 / math.log(2.0)) / float(n_steps)
+    assert np.abs(x - np.round(x)).min() > 1e-6  # no block on an integer boundary
+    want = np.clip(np.ceil(x), 0, 30).astype(np.int32)
+    assert len(set(want.tolist())) > 3
+    args = tuple(_dev(a) for a in (ql, qs, pl, ps))
+    kw = dict(block_dim=int(lens[0])) if form == "uniform" else dict(block_off=off, n_steps=n_steps)
+    got = _three(lambda: cwq.block_bits(*args, return_kl_bits=True, **kw), f"block_bits {form}",
+                 check=lambda f: f.count("device", torch.int32, 4 * nb) >= 1 and
+                 f.count("device", torch.float32, 4 * nb) >= 1)
+    _same(got, (_canon(want), _canon((Sg / np.log(2.0)).astype(np.float32))), f"block_bits {form}")
+
+
+@functools.lru_cache(maxsize=None)
+def _stream_case():
+    """37 blocks, 3 steps, widths 0..13 (zero-width runs at both ends and
+    inside); the total is no multiple of 8, so the last byte is padded."""
+    rng = np.random.Generator(np.random.PCG64(5))
+    nb, n_steps = 37, 3
+    bits = rng.integers(0, 14, nb).astype(np.int32)
+    bits[0] = bits[-1] = bits[10] = bits[11] = 0
+    bits[5] = 13
+    if (int(bits.sum()) * n_steps) % 8 == 0:
+        bits[6] += 1
+    idx = (rng.integers(0, 1 << 13, (nb, n_steps)) & ((1 << bits.astype(np.int64)) - 1)[:, None])
+    return idx.astype(np.int32), bits, n_steps
+
+
+def test_pack_unpack_ignore_buffer_contents(cwq, cwqlib):
+    import test_varbits_gpu as VB
+    idx, bits, n_steps = _stream_case()
+    want, total = VB._ref_stream_numpy(idx, bits)
+    assert total % 8 != 0 and len(want) == (total + 7) // 8
+    need = int(cwqlib.cwq_pack_indices_var_workspace_size(len(bits)))
+
+    def run():
+        code, got_total = cwq.pack_indices(idx, bits)
+        back = cwq.unpack_indices(code, bits, n_steps)
+        return code.cpu().numpy().tobytes(), got_total, back
+
+    got = _three(run, "pack / unpack", need=need,
+                 check=lambda f: f.count("device", torch.uint8, need) >= 2)
+    _same(got, (want, total, _canon(idx)), "pack / unpack against binary_io's stream")
+
+
+def test_decode_blocks_var_from_the_stream(cwq, cwqlib, oracle):
+    import test_varbits_gpu as VB
+    nb, d, n_steps, max_bits = VB.SHAPES[1]
+    _, _, pl, ps, bits = VB._inputs(nb, d, max_bits)
+    widx, _ = VB._oracle_blocks(nb, d, n_steps, max_bits, 1.0)
+    code, total = VB._ref_stream_numpy(widx, bits)
+    want = np.concatenate([
+        oracle.decode_greedy_sample(widx[g], pl[g * d:(g + 1) * d], ps[g * d:(g + 1) * d],
+                                    int(bits[g]), n_steps, VB._wrap32(VB.SEED + g), 1.0)
+        for g in range(nb)])
+    pld, psd = _dev(pl), _dev(ps)
+
+    def run():
+        out = torch.empty(nb * d, dtype=torch.float32, device="cuda")
+        return cwq.decode_blocks_var(code, bits, pld, psd, n_steps, VB.SEED, block_dim=d,
+                                     out_sample=out)
+
+    got = _three(run, "decode_blocks_var",
+                 need=int(cwqlib.cwq_pack_indices_var_workspace_size(nb)))
+    _same(got, _canon(want), "decode_blocks_var against the oracle")
+
+
+# d = 12: three Philox blocks per row, 21 rows per wave; d = 36: nine per row,
+# 63 of 64 lanes active; d = 256: a wave per row; ragged: the general kernel
+DECODE_CASES = [("d12_1step", 12, 37, 1), ("d12_3steps", 12, 37, 3), ("d36", 36, 9, 1),
+                ("d256", 256, 3, 1), ("ragged", [3, 20, 0, 45, 1, 64, 130, 0], None, 2)]
+
+
+@pytest.mark.parametrize("name,d,nb,n_steps", DECODE_CASES)
+def test_decode_blocks_ignores_buffer_contents(cwq, oracle, name, d, nb, n_steps):
+    bits = 10
+    rng = np.random.Generator(np.random.PCG64(300 + n_steps + (d if nb else 1)))
+    off = _offsets(d) if nb is None else np.arange(nb + 1, dtype=np.int64) * d
+    nb, D = off.size - 1, int(off[-1])
+    idx = rng.integers(0, 1 << bits, (nb, n_steps)).astype(np.int32)
+    idx[0, 0], idx[-1, -1] = 0, (1 << bits) - 1
+    pl = rng.standard_normal(D).astype(np.float32)
+    ps = rng.uniform(0.25, 3.0, D).astype(np.float32)
+    want = oracle.greedy_decode(idx, pl, ps, off, bits, n_steps, SEED, 0.8, BASE)
+    pld, psd, idxd = _dev(pl), _dev(ps), _dev(idx)
+    kw = dict(block_off=off) if name == "ragged" else dict(block_dim=d)
+
+    def run():
+        out = torch.empty(D, dtype=torch.float32, device="cuda")
+        return cwq.decode_blocks(idxd, pld, psd, bits, n_steps, SEED, rho=0.8,
+                                 block_id_base=BASE, out_sample=out, **kw)
+
+    got = _three(run, f"decode_blocks {name}",
+                 check=lambda f: f.count("device", torch.float32, 4 * D) >= 1)
+    _same(got, _canon(want), f"decode_blocks {name} against the oracle")
+
+
+def test_stateless_normal_sample_ignores_buffer_contents(cwq, oracle):
+    d, n, seed = 7, 1001, -5
+    rng = np.random.default_rng(d)
+    loc = rng.standard_normal(d).astype(np.float32)
+    scale = rng.uniform(0.1, 3, d).astype(np.float32)
+    want = oracle.stateless_normal_sample(loc, scale, n, seed)
+    got = _three(lambda: cwq.stateless_normal_sample(loc, scale, n, seed),
+                 "stateless_normal_sample",
+                 check=lambda f: f.count("device", torch.float32, 4 * d * n) >= 1)
+    _same(got.reshape(-1), _canon(want).reshape(-1), "stateless_normal_sample against the oracle")
+
+
+# ---------------------------------------------------------------------------
+# the grouped greedy coder: single call, batch (also deferred), batch decoder
+# ---------------------------------------------------------------------------
+def test_grouped_greedy_ignores_buffer_contents(cwq, cwqlib, golden):
+    g = golden("oracle_grouped.npz")
+    D = int(g["p_loc"].size)
+    target = cwq.Normal(_dev(g["q_loc"]), _dev(g["q_scale"]))
+    proposal = cwq.Normal(_dev(g["p_loc"]), _dev(g["p_scale"]))
+
+    def run():
+        sample, bitcode, starts = cwq.code_grouped_greedy_sample(None, target, proposal, 1, 8, 42)
+        dec = cwq.decode_grouped_greedy_sample(None, bitcode, starts, proposal, 8, 1, 42)
+        return np.array(sample), bitcode, [int(v) for v in starts], dec
+
+    got = _three(run, "code_grouped_greedy_sample",
+                 need=int(cwqlib.cwq_code_grouped_greedy_workspace_size(D, 1)))
+    want = (_canon(g["sample"]), cwq.indices_to_bitcode(g["idx"], 8),
+            tuple(int(v) for v in g["starts"]), _canon(g["sample"]))
+    _same(got, want, "grouped greedy coder against the oracle's fixture")
+
+
+@functools.lru_cache(maxsize=None)
+def _batch_items():
+    """Items of 1, 3, 37 and 4,096 dims with the oracle's whole pipeline on
+    each: 2 steps x 6 bits, groups of at most 2^4 dims."""
+    from compression_without_quantization_amd import group_size_threshold
+    from compression_without_quantization_amd.synthetic import make_latents
+    from oracle import oracle as O
+    n_steps, bits, seeds = 2, 6, [7, 2147483647, -3, 42]
+    lat, want = [], []
+    for k, D in enumerate([1, 3, 37, 4096]):
+        q_loc, q_scale, p_loc, p_scale = make_latents(D, bits_per_dim=1.1, seed=100 + k)
+        lat.append((q_loc, q_scale, p_loc, p_scale))
+        s32 = int(np.int32(np.uint32(seeds[k] & 0xFFFFFFFF)))
+        ws, wi, wst = O.code_grouped_greedy_sample(q_loc, q_scale, p_loc, p_scale, n_steps, bits,
+                                                   s32, group_size_threshold(4))
+        want.append((ws, wi, wst))
+    return lat, want, n_steps, bits, seeds
+
+
+def test_grouped_greedy_batch_ignores_buffer_contents(cwq, cwqlib, oracle):
+    lat, want, n_steps, bits, seeds = _batch_items()
+    targets = [cwq.Normal(_dev(a), _dev(b)) for a, b, _, _ in lat]
+    props = [cwq.Normal(_dev(c), _dev(d)) for _, _, c, d in lat]
+    D = sum(a[0].size for a in lat)
+
+    def items(res):
+        return [(np.array(s), code, np.array(st)) for s, code, st in res]
+
+    def run():
+        enc = cwq.code_grouped_greedy_sample_batch(None, targets, props, n_steps, bits, seeds,
+                                                   max_group_size_bits=4)
+        # two deferred calls in flight on their own staging, collected in order
+        h1 = cwq.code_grouped_greedy_sample_batch(None, targets, props, n_steps, bits, seeds,
+                                                  max_group_size_bits=4, defer=True)
+        h2 = cwq.code_grouped_greedy_sample_batch(None, targets[::-1], props[::-1], n_steps, bits,
+                                                  seeds[::-1], max_group_size_bits=4, defer=True)
+        r1, r2 = h1.result(), h2.result()
+        dec = cwq.decode_grouped_greedy_sample_batch(None, [e[1] for e in enc],
+                                                     [e[2] for e in enc], props, bits, n_steps,
+                                                     seeds)
+        return items(enc), items(r1), items(r2)[::-1], [np.array(x) for x in dec]
+
+    need = int(cwqlib.cwq_code_grouped_greedy_batch_workspace_size(D, len(lat), n_steps))
+    G_cap = sum(len(w[2]) for w in want)
+    need_dec = int(cwqlib.cwq_decode_grouped_greedy_batch_workspace_size(D, G_cap, n_steps))
+    got = _three(run, "grouped greedy batch", need=need,
+                 check=lambda f: f.count("device", torch.uint8, need) >= 3 and
+                 f.count("device", torch.uint8, need_dec) >= 1 and f.count("pinned") >= 3)
+    w_items = tuple((_canon(ws), cwq.indices_to_bitcode(wi, bits), _canon(np.array(wst)))
+                    for ws, wi, wst in want)
+    for k, what in enumerate(("batch", "deferred batch 1", "deferred batch 2")):
+        _same(got[k], w_items, f"{what} against the oracle")
+    _same(got[3], tuple(_canon(w[0]) for w in want), "batch decoder against the oracle")
+
+
+# ---------------------------------------------------------------------------
+# the importance coder
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["random", "ties"])
+def test_importance_encode_ignores_buffer_contents(cwq, cwqlib, oracle, kind):
+    """test_gpu.py::test_importance_small_group_threshold's inputs: groups on
+    both sides of the 128-candidate threshold between k_imp_small and
+    k_imp_eval's tiles."""
+    rng = np.random.default_rng(31 if kind == "random" else 32)
+    counts = [1, 2, 63, 64, 65, 127, 128, 129, 130, 255, 256, 257, 1000, 5000]
+    ns = np.array(counts * 3, dtype=np.int64)
+    rng.shuffle(ns)
+    sizes = rng.integers(1, 17, ns.size)
+    off = _offsets(sizes)
+    D = int(off[-1])
+    tl = (rng.standard_normal(D) * 0.8).astype(np.float32)
+    ts = rng.uniform(0.25, 0.95, D).astype(np.float32)
+    if kind == "ties":
+        tl[:], ts[:] = 0.0, 1.0
+    pl, ps = np.zeros(D, np.float32), np.ones(D, np.float32)
+    wi, ws = oracle.importance_encode(tl, ts, pl, ps, off, ns, 4321, 5)
+    args = tuple(_dev(a) for a in (tl, ts, pl, ps))
+
+    def run():
+        gi, gs = cwq.importance_encode_blocks(*args, off, ns, 4321, block_id_base=5)
+        dec = cwq.importance_decode_blocks(wi, args[2], args[3], off, 4321, block_id_base=5)
+        return gi, gs, dec
+
+    got = _three(run, f"importance_encode_blocks {kind}",
+                 need=int(cwqlib.cwq_importance_workspace_size(ns.size, D)))
+    _same(got, (_canon(wi), _canon(ws), _canon(ws)),
+          f"importance coder ({kind}) against the oracle")
+
+
+@functools.lru_cache(maxsize=None)
+def _importance_items():
+    """test_decode_batch_gpu.py's items: 600 (three outlier dims), 5, 1 and 257
+    dims, 12 bits per group, groups of at most 2^8 dims."""
+    from compression_without_quantization_amd.synthetic import make_latents
+    from oracle import oracle as O
+    arrs = []
+    for k, D in enumerate([600, 5, 1, 257]):
+        arrs.append(list(make_latents(D, bits_per_dim=0.6, seed=200 + k)))
+    arrs[0][0][[3, 77, 512]] += np.float32(40.0) * arrs[0][3][[3, 77, 512]]
+    seeds = [11, 2147483647, -9, 3]
+    want = [O.code_grouped_importance_sample(*a, int(np.int32(np.uint32(s & 0xFFFFFFFF))), 12, 8,
+                                             12) for a, s in zip(arrs, seeds)]
+    return arrs, seeds, want
+
+
+def _imp_item(res):
+    sample, code, starts, (oi, oq) = res
+    return np.array(sample), (tuple(code) if not isinstance(code, str) else code), \
+        np.array(starts), np.array(oi), np.array(oq)
+
+
+def test_grouped_importance_ignores_buffer_contents(cwq, cwqlib, oracle):
+    arrs, seeds, want = _importance_items()
+    n_bits = 12
+    targets = [cwq.Normal(_dev(a[0]), _dev(a[1])) for a in arrs]
+    props = [cwq.Normal(_dev(a[2]), _dev(a[3])) for a in arrs]
+    D = sum(a[0].size for a in arrs)
+    assert want[0][3][0].size >= 3 and list(want[2][2]) == [0, 0, 1]
+
+    def run():
+        single = [_imp_item(cwq.code_grouped_importance_sample(
+            None, t, p, s, n_bits, max_group_size_bits=8, return_indices=True))
+            for t, p, s in zip(targets, props, seeds)]
+        batch = [_imp_item(r) for r in cwq.code_grouped_importance_sample_batch(
+            None, targets, props, seeds, n_bits, max_group_size_bits=8, return_indices=True)]
+        dec = cwq.decode_grouped_importance_sample_batch(
+            None, [b[1] for b in batch], [b[2][:-1] for b in batch], props, n_bits, seeds,
+            [b[3] for b in batch], [b[4] for b in batch], use_indices=True)
+        return single, batch, [np.array(x) for x in dec]
+
+    need1 = int(cwqlib.cwq_code_grouped_importance_workspace_size(600))
+    needb = int(cwqlib.cwq_code_grouped_importance_batch_workspace_size(D, len(arrs)))
+    G = sum(len(w[2]) - 1 for w in want)
+    needd = int(cwqlib.cwq_decode_grouped_importance_batch_workspace_size(D, G))
+    got = _three(run, "grouped importance coder", need=needb,
+                 check=lambda f: f.count("device", torch.uint8, need1) >= 1 and
+                 f.count("device", torch.uint8, needd) >= 1)
+    w_items = tuple((_canon(ws), tuple(wi), _canon(np.array(wst)), _canon(oi), _canon(oq))
+                    for ws, wi, wst, (oi, oq) in want)
+    _same(got[0], w_items, "fused single calls against the oracle")
+    _same(got[1], w_items, "batch against the oracle")
+    view = tuple(_canon(_imp_decoder_view(oracle, wi, wst, oi, oq, a[2], a[3], s))
+                 for (ws, wi, wst, (oi, oq)), a, s in zip(want, arrs, seeds))
+    _same(got[2], view, "batch decoder against the oracle's decoder view")
+
+
+def _imp_decoder_view(oracle, ind, st, oi, oq, pl, ps, seed):
+    """What decode_grouped_importance_sample reconstructs (:337-361): group g's
+    row at seed + g (int32 wrap) destandardised, dequantised outliers where
+    non-zero."""
+    n = pl.size
+    z, o = np.zeros(n, np.float32), np.ones(n, np.float32)
+    coded = np.zeros(n, np.float32)
+    for g, (a, b) in enumerate(zip(st[:-1], st[1:])):
+        sg = int(np.int32(np.uint32((int(seed) + g) & 0xFFFFFFFF)))
+        coded[a:b] = oracle.importance_decode_block(ind[g] - 1, z[a:b], o[a:b], sg)
+    coded = oracle.destandardise(coded, pl, ps)
+    upd = np.zeros(n, np.float32)
+    upd[np.asarray(oi, np.int64)] = oracle.dequantize_quint16(oq)
+    return np.where(upd == 0, coded, upd).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------
+# the device partition, through its debug entry
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [3, 2049, 5000])
+def test_device_partition_ignores_buffer_contents(cwq, cwqlib, D):
+    import test_partition_gpu as TP
+    import compression_without_quantization_amd.coded_greedy_sampler as G
+    kl = np.random.default_rng(5 + D).exponential(0.8, D).astype(np.float32)
+    kd = _dev(kl)
+    T, n_nats = G.group_size_threshold(12), 8 * np.log(2) - 1
+    want = TP._host(kl, T, n_nats)
+    wsz = int(cwqlib.cwq_debug_partition_workspace_size(D))
+
+    def run():
+        st = torch.empty(D + 2, dtype=torch.int64, device="cuda")
+        ws = torch.empty(wsz, dtype=torch.uint8, device="cuda")
+        info = np.zeros(8, np.uint64)
+        n = cwqlib.cwq_debug_group_starts_device(kd.data_ptr(), D, T, float(n_nats), st.data_ptr(),
+                                                 ws.data_ptr(), wsz, info.ctypes.data,
+                                                 torch.cuda.current_stream().cuda_stream)
+        assert n > 0, (n, cwqlib.cwq_last_error())
+        return st[:n], int(info[0]), int(info[1])
+
+    got = _three(run, f"device partition D={D}", need=wsz)
+    _same(got, (_canon(want), want.size - 1, int(np.diff(want).max())), "device partition")
+
+
+# ---------------------------------------------------------------------------
+# the PLN codec at the smallest image tests/test_pln_gpu.py uses
+# ---------------------------------------------------------------------------
+def _oracle_level1_budgets(oracle, L1, seed, kw):
+    """test_pln_var_gpu.py's level-1 composition on the oracle (its partition,
+    NumPy-float64 budgets from the float32 per-dim KLs, its greedy coder per
+    group at the group's budget), from the latents the codec itself coded."""
+    from compression_without_quantization_amd import group_size_threshold
+    q1l, q1s, p1l, p1s = (L1[k] for k in ("q_loc", "q_scale", "p_loc", "p_scale"))
+    n_steps, cap = kw["n_steps"], kw["n_bits_per_step"]
+    tl, ts = oracle.standardise(q1l, q1s, p1l, p1s)
+    kl = oracle.kl_normal_normal(q1l, q1s, p1l, p1s)
+    starts = oracle.group_starts(kl, cap * n_steps,
+                                 group_size_threshold(kw["greedy_max_group_size_bits"]))
+    G = len(starts) - 1
+    Sg = np.array([np.cumsum(kl[starts[g]:starts[g + 1]].astype(np.float64))[-1]
+                   if starts[g + 1] > starts[g] else 0.0 for g in range(G)])
+    x = (Sg / np.log(2.0) + 1.0 / math.log(2.0)) / float(n_steps)
+    assert np.abs(x - np.round(x)).min() > 1e-6  # no group on an integer boundary
+    bits = np.clip(np.ceil(x), 0, cap).astype(np.int32)
+    samp = np.zeros(q1l.size, np.float32)
+    z, o = np.zeros(q1l.size, np.float32), np.ones(q1l.size, np.float32)
+    for g in range(G):
+        sl = slice(starts[g], starts[g + 1])
+        if sl.stop > sl.start:
+            sg = int(np.int32(np.uint32((seed + g) & 0xFFFFFFFF)))
+            _, samp[sl] = oracle.code_greedy_sample(tl[sl], ts[sl], z[sl], o[sl], int(bits[g]),
+                                                    n_steps, sg, 1.0)
+    return oracle.destandardise(samp, p1l, p1s)
+
+
+@pytest.mark.parametrize("group_bits", [False, True])
+def test_pln_codec_ignores_buffer_contents(cwq, cwqlib, oracle, tmp_path, group_bits):
+    """The coding around the transforms against the oracle, on the latents the
+    codec itself coded (its ``capture``: at this size the transforms' float32
+    outputs are not pinned from one call to the next outside the codec)."""
+    import test_pln_gpu as TP
+    import test_pln_var_gpu as TV
+    from compression_without_quantization_amd import group_size_threshold
+    from compression_without_quantization_amd import pln as P
+    torch.backends.cudnn.benchmark = False
+    torch.backends.cudnn.deterministic = True
+    model = TP._model(P, seed=3)
+    img = TP._image(64, 64, seed=3)
+    seed = 11
+    if group_bits:
+        kw = dict(TV.KW, first_level_group_bits=True)
+        dec_kw = dict(TV.DEC, first_level_group_bits=True)
+    else:
+        kw = dict(TP.KW)
+        dec_kw = dict(use_importance_sampling=False, greedy_max_group_size_bits=12,
+                      first_level_max_group_size_bits=4, second_level_max_group_size_bits=2)
+    n = {"k": 0}
+
+    def run():
+        n["k"] += 1
+        path = str(tmp_path / f"img{n['k']}.miracle")
+        (sample2, sample1), _ = model.code_image_greedy(None, img, seed, comp_file_path=path, **kw)
+        rec = model.decode_image_greedy(None, path, **dec_kw)
+        return np.array(sample2), np.array(sample1), open(path, "rb").read(), np.array(rec)
+
+    n2 = model.second_level_latent_channels * 1 * 1  # a 64 x 64 image: a 1 x 1 level-2 grid
+    got = _three(run, f"PLN codec (group bits {group_bits})",
+                 need=int(cwqlib.cwq_code_grouped_importance_workspace_size(n2)),
+                 check=lambda f: f.count("device", torch.uint8) >= 2)
+    # a clean run that also hands out the latents it coded (and takes the
+    # grouped coder's one-shot entry instead of its begin / end pair)
+    cap = {}
+    (c2, c1), _ = model.code_image_greedy(None, img, seed, capture=cap, **kw)
+    _same((_canon(c2), _canon(c1)), got[:2], "the capturing run against the three")
+    L2, L1 = cap["level2"], cap["level1"]
+    assert L2["q_loc"].size == n2
+    w2 = oracle.code_grouped_importance_sample(
+        L2["q_loc"], L2["q_scale"], L2["p_loc"], L2["p_scale"], seed,
+        kw["second_level_n_bits_per_group"], kw["second_level_max_group_size_bits"],
+        kw["second_level_dim_kl_bit_limit"])[0]
+    if group_bits:
+        w1 = _oracle_level1_budgets(oracle, L1, seed, kw)
+    else:
+        w1 = oracle.code_grouped_greedy_sample(
+            L1["q_loc"], L1["q_scale"], L1["p_loc"], L1["p_scale"], kw["n_steps"],
+            kw["n_bits_per_step"], seed, group_size_threshold(kw["greedy_max_group_size_bits"]))[0]
+    _same(got[0], _canon(w2), "level-2 sample against the oracle")
+    _same(got[1], _canon(w1), "level-1 sample against the oracle")
+    assert got[3].shape == (64, 64, 3)
