@@ -149,7 +149,8 @@ __global__ void __launch_bounds__(256) k_encode_eval(
 // [s - 2^-14|s| - L, s + 2^-14|s| + B_D].  Candidates whose upper end reaches
 // tau go to an LDS survivor list; at the end of the tile the survivors whose
 // upper end reaches the final tau are re-evaluated exactly (natural order,
-// Eigen summation, eval_row) and only those produce argmax keys.
+// Eigen summation: eval_row's value, computed with a lane per Philox block by
+// score_rows_wave) and only those produce argmax keys.
 //
 // Lanes keep one candidate each and refill from a per-wave counter with
 // ballot/mbcnt when theirs completes or is dropped, so waves stay full even
@@ -189,6 +190,59 @@ __device__ __forceinline__ float lp_from_z(float z, float cc) {
 // and a completed row has E >= (1 + 2^-13) s + As - Pq sqrt(-s), which
 // feeds tau.  Survivors are re-evaluated exactly as in the exact pass.
 
+// What the screening loop reads at one visit position, in one LDS record: the
+// loop carries the record's byte offset, so the three reads share one address
+// register and differ in their immediate offsets only.
+struct VisitRec {
+  float4 sa, sb;  // a_j = RN(sa z' + sb) of the group's four dims
+  int grp;        // Philox group of this visit position
+  int bk;         // bits of B_{k+1}
+  int pad[2];
+};
+static_assert(sizeof(VisitRec) == 48, "VisitRec: 48 bytes");
+
+// Up to RW = min(64 / G, 8) survivor rows of a D-dim block (G = D / 4) scored
+// exactly by one wave (a lane per row would run a whole row's arithmetic with
+// the other 63 idle when, as usual, a tile has one such row).  Lane l <
+// cnt * G computes the four terms of Philox block l % G of row rows[l / G]
+// into buf; lane 8 r + a then sums row r's terms a, a + 8, ... in order: the
+// eight accumulators of eval_row_f, whose tail sum stays the +0 it starts from
+// since D % 8 == 0.  Returns to every lane of 8 r .. 8 r + 7 the value of row
+// r < cnt, eval_row<D, STEP0>'s bit for bit.  Full exec mask; cnt is uniform.
+template <int D, bool STEP0>
+__device__ __forceinline__ float score_rows_wave(
+    const PhiloxStream& st, const uint32_t* rows, uint32_t cnt, const float* __restrict__ loc_s,
+    const float* __restrict__ scale_s, const float* __restrict__ mu,
+    const float* __restrict__ sg, const float* __restrict__ lognorm,
+    const float* __restrict__ best, const double* logtab, float* buf, uint32_t lane) {
+  constexpr uint32_t G = D / 4;
+  const uint32_t r = lane / G, u = lane - r * G;
+  if (r < cnt) {
+    const F4 z = normal4_dev(st, (uint64_t)rows[r] * G + u, logtab);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t j = 4u * u + (uint32_t)t;
+      const float zz = t == 0 ? z.a : (t == 1 ? z.b : (t == 2 ? z.c : z.d));
+      float v = scale_s[j] * zz;  // misc.py:14
+      v = loc_s[j] + v;           // misc.py:15
+      const float tv = STEP0 ? v : best[j] + v;
+      buf[r * D + j] = log_prob(tv, mu[j], sg[j], lognorm[j]);
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  float acc = 0.0f;
+  const uint32_t fr = lane >> 3;
+  if (fr < cnt)
+    for (uint32_t e = lane & 7u; e < (uint32_t)D; e += 8u) acc = acc + buf[fr * D + e];
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  float p[8];
+#pragma unroll
+  for (int l = 0; l < 8; ++l) p[l] = __shfl(acc, (int)((lane & ~7u) + (uint32_t)l), 64);
+  return eigen_fold8(p, 0.0f);
+}
+
 #ifdef CWQ_TILE_TIMES
 // timing builds only (tools/tile_times.py): per tile of k_encode_prune its
 // start / end wall clock (s_memrealtime, 100 MHz) and the workgroup that ran it
@@ -221,11 +275,14 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
   static_assert(D % 8 == 0 && D >= 8 && D <= 64, "pruned path: D % 8 == 0, D <= 64");
   constexpr int G = D / 4;
   constexpr int NF = STEP0 ? 6 : 7;  // loc_s, scale_s, mu, sigma, c, 1/sigma[, best]
-  constexpr int NS = 2;              // screening: sA, sB
+  // survivor rows one wave scores per pass: a lane per Philox block of a row,
+  // eight lanes per row in the fold (score_rows_wave)
+  constexpr int RW = (64 / G) < 8 ? (64 / G) : 8;
   __shared__ double logtab[32];
   __shared__ float4 cst[G * NF];     // constants of the k-th visited group
-  __shared__ float4 scst[G * NS];    // screening constants of the k-th visited group
+  __shared__ VisitRec vrec[G];       // screening pass: all it reads at the k-th visited group
   __shared__ int2 meta[G];           // {Philox group of visit k, bits of B_{k+1}}
+  __shared__ float rowbuf[4][RW * D];  // per wave: the terms of RW survivor rows
   __shared__ float dscore[D];
   __shared__ float dA[D];            // screening: A_j (additive error, a units)
   __shared__ float dC[D];            // screening: C_j
@@ -339,6 +396,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       }
       gpos[q] = r;
       meta[r].x = q;
+      vrec[r].grp = q;
     }
     __syncthreads();
     // (d) constants in visit order (reloaded: nothing is held across the syncs)
@@ -360,9 +418,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       den_ok = markstein_ok_den(sgj) ? 1 : 0;
       // screening constants; the gate includes den_ok's test of sigma
       const ScreenDim o = screen_dim<STEP0>(fj[0], fj[1], fj[2], sgj, fj[4], fj[6]);
-      float* sc = reinterpret_cast<float*>(scst);
-      sc[(k * NS + 0) * 4 + w] = o.sa;
-      sc[(k * NS + 1) * 4 + w] = o.sb;
+      float* sc = reinterpret_cast<float*>(&vrec[k]);
+      sc[w] = o.sa;
+      sc[4 + w] = o.sb;
       dA[j] = o.A;
       dC[j] = o.C;
       scr_ok = o.ok ? 1 : 0;
@@ -401,7 +459,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       if (kb <= G) {
         const float bk = screen ? round_up_f32(msum + cvis * (1.0 + 0x1p-20) + sl)
                                 : round_up_f32(rf + 0x1p-14 * kk + marg);
-        if (kb >= 1) meta[kb - 1].y = (int)f2u(bk);
+        if (kb >= 1) {
+          meta[kb - 1].y = (int)f2u(bk);
+          vrec[kb - 1].bk = (int)f2u(bk);
+        }
         if (kb == G) lowc = round_up_f32(0x1p-14 * kk + marg);
       } else if (screen) {  // As, Pq with this kernel's fixed 2^-14 slack
         scr_a = screen_as(msum, sl, a2);
@@ -432,13 +493,19 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     // this wave's contiguous share of the tile's candidates
     const int64_t per_wave = (n1 - n0 + 3) / 4;
     const int64_t w0 = n0 + (int64_t)wv * per_wave;
-    // candidate indices stay below 2^32 in this kernel (launch_prune_t):
-    // 32-bit counters (a 64-bit add and compare cost two VALU slots each)
-    const uint32_t w1 = (uint32_t)((w0 + per_wave < n1) ? w0 + per_wave : n1);
-    uint32_t wnext = (uint32_t)w0 + 64u;
-    uint32_t n = (uint32_t)w0 + lane;
-    int k = 0;
-    float s = 0.0f;
+    const int64_t w1 = (w0 + per_wave < n1) ? w0 + per_wave : n1;
+    // A lane carries its row as ng = (n - w0) * G, the row's first Philox block
+    // relative to the wave's: the block of a visit is then one add (ng + group
+    // + w0g), the range test one compare with ng_end, and the refill one
+    // shift-add or mad.  Rows and Philox blocks stay below 2^32 in this kernel
+    // (launch_prune_t), and w0g + ng + group is taken mod 2^32 like n * G +
+    // group; ng itself is at most (per_wave + 64 (G + 1)) * G, far below 2^32
+    // (a wave's share is a quarter of a tile).  The wave-uniform values are
+    // made scalar once per tile, so the loop's counters run on the SALU.
+    const uint32_t w0g =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)w0 * (uint32_t)G));
+    const uint32_t ng_end = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(w1 > w0 ? (uint32_t)(w1 - w0) * (uint32_t)G : 0u));
 #ifndef CWQ_TAU_FROM_KEYS
 #define CWQ_TAU_FROM_KEYS 1  // INTER: start the lanes' tau at keys[g]'s value, not at the first share
 #endif
@@ -447,26 +514,48 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     tau = tau_seed;
 #endif
     uint64_t bestk = 0;
-    uint32_t iter = 0;
 
     const PhiloxLo lok = philox_lo_key(st);  // block indices < 2^32 (launch_prune_t)
     auto pass = [&](auto screen_tag) {
       constexpr bool SCREEN = decltype(screen_tag)::value;
-      for (;;) {
-        // a lane is active while its row index is in the wave's range (a
-        // compare each iteration, not a flag carried in a VGPR)
-        const bool active = n < w1;
-        if (__ballot(active) == 0ull) break;
-        const int2 mt = meta[k];
-        const uint32_t grp = (uint32_t)n * (uint32_t)G + (uint32_t)mt.x;
-        const U4 x = philox10_lo(grp, lok, st.k0, st.k1);
+      // visit position: the screening pass carries it as the byte offset of
+      // its VisitRec, the exact pass as the index k of meta[k] and cst
+      constexpr uint32_t KS = SCREEN ? (uint32_t)sizeof(VisitRec) : 1u;
+      uint32_t ng = lane * (uint32_t)G;
+      uint32_t wnext_g = 64u * (uint32_t)G;  // (next unassigned row - w0) * G: wave-uniform
+      uint32_t kp = 0;
+      float s = 0.0f;
+      uint32_t iter = 0;
+      // a lane is active while its row is in the wave's range: one compare per
+      // iteration, taken after the refill, its mask carried in SGPRs.  The
+      // loop's only exit is at its end, so its wave-uniform counters (iter,
+      // wnext_g) stay scalar.
+      bool active = ng < ng_end;
+      uint64_t m_act = __builtin_amdgcn_ballot_w64(active);
+      while (m_act != 0ull) {
+        int2 mt;
+        float4 sa, sb;
+        if constexpr (SCREEN) {
+          const char* rp = reinterpret_cast<const char*>(vrec) + kp;
+          sa = *reinterpret_cast<const float4*>(rp);
+          sb = *reinterpret_cast<const float4*>(rp + 16);
+          mt = *reinterpret_cast<const int2*>(rp + 32);
+        } else {
+          mt = meta[kp];
+        }
+        const uint32_t grp = (ng + (uint32_t)mt.x) + w0g;
+        // the key through an opaque move each iteration: the fourteen round
+        // keys are then formed here by scalar adds, not held in SGPRs across
+        // the loop, where they pushed the loop's lane masks and counters out
+        // into VGPR lanes (v_writelane / v_readlane every iteration)
+        uint32_t pk0 = st.k0, pk1 = st.k1;
+        asm volatile("" : "+s"(pk0), "+s"(pk1));
+        const U4 x = philox10_lo(grp, lok, pk0, pk1);
         float z0, z1, z2, z3;
         float upper;
         if constexpr (SCREEN) {
           box_muller_screen(x.x, x.y, z0, z1);
           box_muller_screen(x.z, x.w, z2, z3);
-          const float4* cq = scst + k * NS;
-          const float4 sa = cq[0], sb = cq[1];
           const float a0 = __builtin_fmaf(sa.x, z0, sb.x);
           const float a1 = __builtin_fmaf(sa.y, z1, sb.y);
           const float a2 = __builtin_fmaf(sa.z, z2, sb.z);
@@ -479,7 +568,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         } else {
           box_muller_dev(x.x, x.y, logtab, z0, z1);
           box_muller_dev(x.z, x.w, logtab, z2, z3);
-          const float4* cq = cst + k * NF;
+          const float4* cq = cst + kp * NF;
           const float4 ls = cq[0], ss = cq[1], mu = cq[2], sg = cq[3], cc = cq[4], ry = cq[5];
           const float4 bb = STEP0 ? float4{0.f, 0.f, 0.f, 0.f} : cq[6];
           const float d0 = cand_diff<STEP0>(z0, ls.x, ss.x, mu.x, bb.x);
@@ -508,18 +597,39 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           s = s + lp_from_z(y3, cc.w);
           upper = (s + __builtin_fabsf(s) * kPruneC1) + u2f((uint32_t)mt.y);
         }
-        k += 1;
-        const bool complete = (k == G);
+        kp += KS;
+        const bool complete = (kp == KS * (uint32_t)G);
         const bool below = upper < tau;
+        // Screening pass: one compare of (upper, tau) serves the drop test and
+        // the keep test, !(upper < tau) == (upper >= tau), because neither is
+        // NaN there.  upper = fma(s, c1, B_k): behind the gate sa and sb are
+        // finite with |sa|, |sb| < 2^51 (screen_dim: mag / sigma <= 2^50), z'
+        // is finite with |z'| < 5 for every Philox word (u1 is clamped to
+        // [1e-7, 1], sin and cos take an angle in [1, 2)), so |a| < 2^54 and s,
+        // a sum of at most 64 terms -a^2, is finite; B_k is finite or +inf,
+        // never NaN (round_up_f32).  tau starts at -inf or at a clamped key's
+        // value and only ever takes fmaxf(tau, x), which drops a NaN x.  The
+        // exact pass, whose s may be NaN, keeps both compares: a NaN row is
+        // neither dropped early nor kept.
+        const bool reach = SCREEN ? !below : (upper >= tau);
 #ifdef CWQ_PRUNE_STATS
         const bool prune = !complete && below;
+        const uint32_t k = kp / KS;
 #endif
         const bool done = complete || below || !active;
-        // the finished lanes' mask from the compares' own masks (SALU): a
-        // ballot of the combined flag costs a v_cndmask + v_cmp to rebuild it
-        const uint64_t m = __ballot(complete) | __ballot(below) |
-                           (__builtin_amdgcn_read_exec() & ~__ballot(active));
-        if (complete && active && upper >= tau) {  // may be the best: keep it
+        // the finished lanes' mask from the compares' own masks (SALU).  The
+        // empty asm keeps it here, in the compares' block: moved behind the
+        // branch below, each ballot is rebuilt there with a v_cndmask + v_cmp.
+        uint64_t m = __builtin_amdgcn_ballot_w64(complete) |
+                     __builtin_amdgcn_fcmpf(upper, tau, 4 /* olt */) |
+                     (__builtin_amdgcn_read_exec() & ~m_act);
+        asm volatile("" : "+s"(m));
+        if (__builtin_expect(complete && active && reach, 0)) {  // may be the best: keep it
+          // the row, n = (w0g + ng) / G (exact: n * G < 2^32), from an opaque
+          // copy of ng, so that w0g + ng is not shared with the loop's grp
+          uint32_t ngc = ng;
+          asm volatile("" : "+v"(ngc));
+          const uint32_t n = (w0g + ngc) / (uint32_t)G;
           float lower;
           if constexpr (SCREEN)
             lower = screen_row_lower(s, kScreenC2, sA, sPq);
@@ -549,16 +659,18 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         if (done) {
-          n = wnext + rank;
-          k = 0;
+          ng = wnext_g + rank * (uint32_t)G;
+          kp = 0;
           s = 0.0f;
         }
-        wnext += (uint32_t)__builtin_popcountll(m);
+        wnext_g += (uint32_t)__builtin_popcountll(m) * (uint32_t)G;
         if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {  // share tau across the workgroup's waves
           const float tm = wave_max_f32(tau);
           if (lane == 0) atomicMax(&tau_ord, ord_f32(tm));
           tau = fmaxf(tau, unord_f32(__atomic_load_n(&tau_ord, __ATOMIC_RELAXED)));
         }
+        active = ng < ng_end;
+        m_act = __builtin_amdgcn_ballot_w64(active);
       }
     };
 #ifdef CWQ_PRUNE_STATS
@@ -577,17 +689,40 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     __syncthreads();
     const float tau_final = unord_f32(tau_ord);
     const uint32_t nsurv = sq_cnt < CWQ_SURVIVOR_CAP ? sq_cnt : CWQ_SURVIVOR_CAP;
-    for (uint32_t i = tid; i < nsurv; i += blockDim.x) {
-      if (sq_ub[i] >= tau_final) {
+    // A wave takes the list 64 entries at a time, packs those that reach
+    // tau_final to the front of its 64 (in place: every lane has read its
+    // entry before any writes) and scores them RW rows per pass, a lane per
+    // Philox block (score_rows_wave).  All of it is wave-uniform.  The lane
+    // comes from the tile's opaque tid, so that the rows' per-lane addresses
+    // are not hoisted out of the tile loop and spilled.
+    const uint32_t nsurv_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)nsurv);
+    const uint32_t sl = tid & 63u;
+    for (uint32_t c0 = wv * 64u; c0 < nsurv_u; c0 += 256u) {
+      const uint32_t i = c0 + sl;
+      const bool q = i < nsurv_u && sq_ub[i] >= tau_final;
+      const uint32_t nn = i < nsurv_u ? sq_n[i] : 0u;
+      const uint64_t qm = __builtin_amdgcn_ballot_w64(q);
+      if (qm == 0ull) continue;
 #ifdef CWQ_PRUNE_STATS
-        atomicAdd(&g_prune_stats[68], 1ull);
+      if (q) atomicAdd(&g_prune_stats[68], 1ull);
 #endif
-        const uint32_t nn = sq_n[i];
-        const float v = eval_row<D, STEP0>(st, (uint64_t)nn * D, D, 0, loc_s + off,
-                                           scale_s + off, t_loc + off, t_scale + off,
-                                           lognorm + off, STEP0 ? nullptr : best + off, logtab);
-        const uint64_t kv = argmax_key(v, nn);
-        bestk = kv > bestk ? kv : bestk;
+      const uint32_t qr = __builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (q) sq_n[c0 + qr] = nn;
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      const uint32_t qn = (uint32_t)__builtin_popcountll(qm);
+      for (uint32_t b = 0; b < qn; b += (uint32_t)RW) {
+        const uint32_t cnt = qn - b < (uint32_t)RW ? qn - b : (uint32_t)RW;
+        const float v = score_rows_wave<D, STEP0>(
+            st, sq_n + c0 + b, cnt, loc_s + off, scale_s + off, t_loc + off, t_scale + off,
+            lognorm + off, STEP0 ? nullptr : best + off, logtab, rowbuf[wv], sl);
+        if ((sl & 7u) == 0u && (sl >> 3) < cnt) {
+          const uint64_t kv = argmax_key(v, sq_n[c0 + b + (sl >> 3)]);
+          bestk = kv > bestk ? kv : bestk;
+        }
       }
     }
 
