@@ -350,6 +350,48 @@ __device__ __forceinline__ float wave_max_f32(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 #endif
+// max(a, b) as one v_max_f32, for thresholds that are never NaN.  fmaxf adds a
+// v_max_f32 x, x, x per operand the compiler cannot prove quiet (a value out of
+// a readlane or an LDS atomic, for instance).
+__device__ __forceinline__ float max_f32_quiet(float a, float b) {
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// The pruned loops' threshold tau, kept wave-uniform.  Raising it: the wave max
+// of `lower` over the lanes with `on` set (the others contribute the identity,
+// -inf; a NaN `lower` is dropped, as fmaxf would), then every lane's
+// tau = max(tau, that).  Requires a full exec mask, so the caller branches on
+// the ballot of `on`, not on `on`.
+__device__ __forceinline__ float tau_raise_wave(float tau, bool on, float lower) {
+  return max_f32_quiet(tau, wave_max_f32((on && lower == lower) ? lower : -__builtin_inff()));
+}
+// Sharing it through the workgroup's LDS cell (a float, never NaN): lane 0
+// does one returning max, cell = max(cell, tau), and every lane takes
+// max(tau, old cell).  tau is the same in all lanes before and after.
+// Written out, with the exec mask set to lane 0 around the one ds_max_rtn_f32:
+// as an atomicrmw the compiler's atomic optimizer wraps it in a lane election
+// of its own (two v_mbcnt and a compare) or, for a value it cannot prove
+// uniform, in a lane-by-lane reduction loop.  Full exec mask on entry.
+__device__ __forceinline__ float tau_share_wave(float* cell, float tau) {
+  const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)cell;
+  uint64_t sv;
+  float old;
+  int oldu;
+  asm volatile(
+      "s_mov_b64 %1, exec\n\t"
+      "s_mov_b64 exec, 1\n\t"
+      "ds_max_rtn_f32 %0, %2, %3\n\t"
+      "s_mov_b64 exec, %1\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(old), "=&s"(sv)
+      : "v"(addr), "v"(tau)
+      : "memory");
+  oldu = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, old));
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "s"(oldu), "v"(tau));
+  return r;
+}
 // Sum over each 16-lane DPP row, the same value in all 16 lanes: butterflies
 // (quad xor 1, quad xor 2, half-row mirror, row mirror) pair lanes
 // symmetrically and float addition commutes, so every lane forms the

@@ -164,7 +164,13 @@ constexpr float kPruneC1 = 0x1p-14f;
 #define CWQ_XCD_BALANCE 1  // INTER tiles: each XCD runs every block (see k_encode_prune)
 #endif
 #ifndef CWQ_TAU_SHARE_MASK
-#define CWQ_TAU_SHARE_MASK 15u  // share tau across the workgroup every 16 units
+// k_encode_prune shares tau across the workgroup every 8 units: a share is one
+// returning LDS max and two VALU instructions (tau_share_wave).  Every 16: C4
+// 280.9 against 279.6 ms, C5 33.40 against 33.45 (DESIGN.md 4 "VALU budget")
+#define CWQ_TAU_SHARE_MASK 7u
+#endif
+#ifndef CWQ_CSR_TAU_SHARE_MASK
+#define CWQ_CSR_TAU_SHARE_MASK 15u  // k_encode_prune_csr: a wave reduce per share, every 16 units
 #endif
 #ifndef CWQ_SURVIVOR_CAP
 #define CWQ_SURVIVOR_CAP 1024
@@ -290,7 +296,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
   __shared__ int gpos[G];
   __shared__ float lowc;             // L: lower-end constant of a completed row
   __shared__ float scr_a, scr_pq;    // screening: As, Pq
-  __shared__ uint32_t tau_ord;
+  __shared__ float tau_cell;         // the workgroup's tau (a float, never NaN: LDS float max)
   __shared__ uint32_t sq_cnt;
   __shared__ uint32_t sq_n[CWQ_SURVIVOR_CAP];
   __shared__ float sq_ub[CWQ_SURVIVOR_CAP];
@@ -469,24 +475,26 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         scr_pq = screen_pq(amax, D);
       }
       if (kb == 0) {
-        uint32_t t0 = ord_f32(-__builtin_inff());
+        // the cell holds tau as a float; the keys' order is undone here, once
+        // per tile
+        float t0 = -__builtin_inff();
         if (inter) {  // an actual row's exact value: no larger than the block's best
           const unsigned long long kv =
               __hip_atomic_load(&keys[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((uint32_t)(kv >> 32) > kArgmaxClampOrd) t0 = (uint32_t)(kv >> 32);
+          if ((uint32_t)(kv >> 32) > kArgmaxClampOrd) t0 = unord_f32((uint32_t)(kv >> 32));
         }
-        tau_ord = t0;
 #ifdef CWQ_PRUNE_STATS
         if (g_seed_tau && g < kDbgBlocks && (g_dbg_best[g] >> 32) > kArgmaxClampOrd)
-          tau_ord = (uint32_t)(g_dbg_best[g] >> 32);
+          t0 = unord_f32((uint32_t)(g_dbg_best[g] >> 32));
 #endif
+        tau_cell = t0;
         sq_cnt = 0u;
       }
     }
     __syncthreads();
     const float lc = lowc;
 #ifdef CWQ_PRUNE_STATS
-    const float tau_seed = unord_f32(tau_ord);
+    const float tau_seed = tau_cell;
 #endif
     const float sA = scr_a, sPq = scr_pq;
 
@@ -509,7 +517,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
 #ifndef CWQ_TAU_FROM_KEYS
 #define CWQ_TAU_FROM_KEYS 1  // INTER: start the lanes' tau at keys[g]'s value, not at the first share
 #endif
-    float tau = (INTER && CWQ_TAU_FROM_KEYS) ? unord_f32(tau_ord) : -__builtin_inff();
+    // tau is wave-uniform from here to the end of the tile: it starts so, and
+    // the keep branch and the share below both leave the same value in every lane
+    float tau = (INTER && CWQ_TAU_FROM_KEYS) ? tau_cell : -__builtin_inff();
 #ifdef CWQ_PRUNE_STATS
     tau = tau_seed;
 #endif
@@ -608,9 +618,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // [1e-7, 1], sin and cos take an angle in [1, 2)), so |a| < 2^54 and s,
         // a sum of at most 64 terms -a^2, is finite; B_k is finite or +inf,
         // never NaN (round_up_f32).  tau starts at -inf or at a clamped key's
-        // value and only ever takes fmaxf(tau, x), which drops a NaN x.  The
-        // exact pass, whose s may be NaN, keeps both compares: a NaN row is
-        // neither dropped early nor kept.
+        // value and only ever takes a max with a lower bound that is not NaN
+        // (tau_raise_wave leaves a NaN out) or with the workgroup's cell, which
+        // holds such values only.  The exact pass, whose s may be NaN, keeps
+        // both compares: a NaN row is neither dropped early nor kept.
         const bool reach = SCREEN ? !below : (upper >= tau);
 #ifdef CWQ_PRUNE_STATS
         const bool prune = !complete && below;
@@ -620,41 +631,68 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // the finished lanes' mask from the compares' own masks (SALU).  The
         // empty asm keeps it here, in the compares' block: moved behind the
         // branch below, each ballot is rebuilt there with a v_cndmask + v_cmp.
-        uint64_t m = __builtin_amdgcn_ballot_w64(complete) |
-                     __builtin_amdgcn_fcmpf(upper, tau, 4 /* olt */) |
-                     (__builtin_amdgcn_read_exec() & ~m_act);
-        asm volatile("" : "+s"(m));
-        if (__builtin_expect(complete && active && reach, 0)) {  // may be the best: keep it
-          // the row, n = (w0g + ng) / G (exact: n * G < 2^32), from an opaque
-          // copy of ng, so that w0g + ng is not shared with the loop's grp
-          uint32_t ngc = ng;
-          asm volatile("" : "+v"(ngc));
-          const uint32_t n = (w0g + ngc) / (uint32_t)G;
+        // The keep mask (complete, active, reaching tau) is formed the same
+        // way, for the same reason: as the ballot of a bool it cost a second
+        // compare of (upper, tau), a v_cndmask and a v_cmp every iteration.
+        const uint64_t m_cpl = __builtin_amdgcn_ballot_w64(complete);
+        const uint64_t m_below = __builtin_amdgcn_fcmpf(upper, tau, 4 /* olt */);
+        uint64_t m = m_cpl | m_below | (__builtin_amdgcn_read_exec() & ~m_act);
+        uint64_t m_keep =
+            m_cpl & m_act &
+            (SCREEN ? ~m_below : (uint64_t)__builtin_amdgcn_fcmpf(upper, tau, 3 /* oge */));
+        asm volatile("" : "+s"(m), "+s"(m_keep));
+        // Rows that completed and may be the best.  The branch is taken by the
+        // whole wave (on the scalar m_keep, so the exec mask stays full for the
+        // wave max): tau is raised to the largest lower end among these rows in
+        // every lane at once, and of these rows only those whose upper end
+        // reaches the raised tau go to the survivor list.
+        //   * tau stays a lower bound of the exact value of a row completed in
+        //     this tile: each `lower` is one (screening bound / kPruneC1).
+        //   * A row with upper < tau has an exact value <= upper < tau <= the
+        //     exact value of a completed row: neither the argmax nor a tie.
+        //   * A row whose exact value E equals the best row's has upper >= E >=
+        //     every lower bound of every row, so upper >= tau: ties reach the
+        //     list, the best row among them, whatever the order of completion.
+        //   * Exact pass: keep is false for a row with a NaN upper (reach is the
+        //     ordered compare), so it is neither dropped above nor pushed here; a
+        //     NaN lower (s = +inf) is left out of the max and the row, whose
+        //     upper is +inf, is pushed.
+        if (__builtin_expect(m_keep != 0ull, 0)) {
+          const bool keep = complete && active && reach;
           float lower;
           if constexpr (SCREEN)
             lower = screen_row_lower(s, kScreenC2, sA, sPq);
           else
             lower = (s - __builtin_fabsf(s) * kPruneC1) - lc;
-          tau = fmaxf(tau, lower);
-          const uint32_t slot = atomicAdd(&sq_cnt, 1u);
-          if (slot < CWQ_SURVIVOR_CAP) {
-            sq_n[slot] = (uint32_t)n;
-            sq_ub[slot] = upper;
-          } else {  // list full (near-ties everywhere): evaluate exactly now
+          tau = tau_raise_wave(tau, keep, lower);
+          if (__builtin_expect(keep && upper >= tau, 0)) {
+            // the row, n = (w0g + ng) / G (exact: n * G < 2^32), from an opaque
+            // copy of ng, so that w0g + ng is not shared with the loop's grp
+            uint32_t ngc = ng;
+            asm volatile("" : "+v"(ngc));
+            const uint32_t n = (w0g + ngc) / (uint32_t)G;
 #ifdef CWQ_PRUNE_STATS
-            atomicAdd(&g_prune_stats[69], 1ull);
+            atomicAdd(&s_ps[66], 1u);
 #endif
-            const float v = eval_row<D, STEP0>(st, (uint64_t)n * D, D, 0, loc_s + off,
-                                               scale_s + off, t_loc + off, t_scale + off,
-                                               lognorm + off, STEP0 ? nullptr : best + off, logtab);
-            const uint64_t kv = argmax_key(v, (uint32_t)n);
-            bestk = kv > bestk ? kv : bestk;
+            const uint32_t slot = atomicAdd(&sq_cnt, 1u);
+            if (slot < CWQ_SURVIVOR_CAP) {
+              sq_n[slot] = (uint32_t)n;
+              sq_ub[slot] = upper;
+            } else {  // list full (near-ties everywhere): evaluate exactly now
+#ifdef CWQ_PRUNE_STATS
+              atomicAdd(&g_prune_stats[69], 1ull);
+#endif
+              const float v = eval_row<D, STEP0>(st, (uint64_t)n * D, D, 0, loc_s + off,
+                                                 scale_s + off, t_loc + off, t_scale + off,
+                                                 lognorm + off, STEP0 ? nullptr : best + off, logtab);
+              const uint64_t kv = argmax_key(v, (uint32_t)n);
+              bestk = kv > bestk ? kv : bestk;
+            }
           }
         }
 #ifdef CWQ_PRUNE_STATS
         if (active && (complete || prune)) atomicAdd(&s_ps[k], 1u);
         if (active && complete) atomicAdd(&s_ps[65], 1u);
-        if (active && complete && upper >= tau) atomicAdd(&s_ps[66], 1u);
 #endif
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -664,11 +702,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           s = 0.0f;
         }
         wnext_g += (uint32_t)__builtin_popcountll(m) * (uint32_t)G;
-        if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {  // share tau across the workgroup's waves
-          const float tm = wave_max_f32(tau);
-          if (lane == 0) atomicMax(&tau_ord, ord_f32(tm));
-          tau = fmaxf(tau, unord_f32(__atomic_load_n(&tau_ord, __ATOMIC_RELAXED)));
-        }
+        // share tau across the workgroup's waves: it is wave-uniform already,
+        // so one returning LDS max by lane 0 and one v_max, no reduce (and no
+        // "raised since the last share" flag: both of its arms would be this)
+        if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) tau = tau_share_wave(&tau_cell, tau);
         active = ng < ng_end;
         m_act = __builtin_amdgcn_ballot_w64(active);
       }
@@ -682,12 +719,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       pass(std::false_type{});
 
     // exact evaluation of the survivors that can still reach the final tau
-    {
-      const float tm = wave_max_f32(tau);
-      if (lane == 0) atomicMax(&tau_ord, ord_f32(tm));
-    }
+    tau_share_wave(&tau_cell, tau);
     __syncthreads();
-    const float tau_final = unord_f32(tau_ord);
+    const float tau_final = tau_cell;
     const uint32_t nsurv = sq_cnt < CWQ_SURVIVOR_CAP ? sq_cnt : CWQ_SURVIVOR_CAP;
     // A wave takes the list 64 entries at a time, packs those that reach
     // tau_final to the front of its 64 (in place: every lane has read its
@@ -1404,7 +1438,7 @@ __global__ void __launch_bounds__(256, COOP ? CWQ_CSR_COOP_MIN_WAVES : CWQ_CSR_R
           }
           wnext += (uint32_t)__builtin_popcountll(m);
           active = r < r1;
-          if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {  // share with the workgroup
+          if (((++iter) & CWQ_CSR_TAU_SHARE_MASK) == 0u) {  // share with the workgroup
             const float tm = wave_max_f32(tau);
             if (lane == 0) atomicMax(&tau_ord, ord_f32(tm));
             uint32_t o = __atomic_load_n(&tau_ord, __ATOMIC_RELAXED);
@@ -1586,7 +1620,7 @@ __global__ void __launch_bounds__(256, COOP ? CWQ_CSR_COOP_MIN_WAVES : CWQ_CSR_R
           }
           wnext += (uint32_t)(__builtin_popcountll(m) >> 4);
           active = q < q1;
-          if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {  // share with the workgroup
+          if (((++iter) & CWQ_CSR_TAU_SHARE_MASK) == 0u) {  // share with the workgroup
             const float tm = wave_max_f32(tau);
             if (lane == 0) atomicMax(&tau_ord, ord_f32(tm));
             tau = fmaxf(tau, unord_f32(__atomic_load_n(&tau_ord, __ATOMIC_RELAXED)));
