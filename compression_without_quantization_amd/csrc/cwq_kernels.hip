@@ -23,6 +23,7 @@
 
 #include "cwq_device.h"
 #include "cwq_kernels.h"
+#include "cwq_refill.h"
 
 namespace cwq {
 
@@ -152,9 +153,11 @@ __global__ void __launch_bounds__(256) k_encode_eval(
 // Eigen summation: eval_row's value, computed with a lane per Philox block by
 // score_rows_wave) and only those produce argmax keys.
 //
-// Lanes keep one candidate each and refill from a per-wave counter with
-// ballot/mbcnt when theirs completes or is dropped, so waves stay full even
-// though candidates stop after different numbers of groups.
+// Lanes keep one candidate each and take another when theirs completes or is
+// dropped, so waves stay full even though candidates stop after different
+// numbers of groups: first the lane's own rows of the wave's share, a stride
+// of 64 apart, then rows of a common pool from a per-wave counter with
+// ballot/mbcnt (cwq_refill.h).
 // ---------------------------------------------------------------------------
 constexpr float kPruneC1 = 0x1p-14f;
 #ifndef CWQ_PRUNE_MIN_WAVES
@@ -174,6 +177,11 @@ constexpr float kPruneC1 = 0x1p-14f;
 #endif
 #ifndef CWQ_SURVIVOR_CAP
 #define CWQ_SURVIVOR_CAP 1024
+#endif
+#ifndef CWQ_LINKED_VISIT
+// the screening loop takes its next visit position from the record it has just
+// read (VisitRec::next); 0: it adds the record size (A/B builds)
+#define CWQ_LINKED_VISIT 1
 #endif
 
 // best + (loc_s + scale_s z) - mu  (misc.py:14-15, coded_greedy_sampler.py:57, TFP _z numerator)
@@ -203,7 +211,8 @@ struct VisitRec {
   float4 sa, sb;  // a_j = RN(sa z' + sb) of the group's four dims
   int grp;        // Philox group of this visit position
   int bk;         // bits of B_{k+1}
-  int pad[2];
+  int next;       // byte offset of the next visit position's record; 0 in the last
+  int pad;
 };
 static_assert(sizeof(VisitRec) == 48, "VisitRec: 48 bytes");
 
@@ -258,7 +267,8 @@ __device__ unsigned int g_tile_wg[kTileTimes];
 #endif
 #ifdef CWQ_PRUNE_STATS
 // tuning builds only (tools/prune_stats.py): [0..64] candidates finished after
-// k units, [65] completed rows, [66] survivors pushed, [67] screened tiles;
+// k units, [65] completed rows, [66] survivors pushed, [67] screened tiles,
+// [70] wave-iterations that took the pool refill, [71] wave-iterations;
 // general kernel (tools/csr_stats.py): [40]/[41] screened/exact tiles, [42] rows
 // finished, [43] dims screened, [44] rows completed, [45] survivors pushed,
 // [46] list-full exact rows, [47] survivors re-evaluated, [48] lane-iterations
@@ -403,6 +413,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       gpos[q] = r;
       meta[r].x = q;
       vrec[r].grp = q;
+      vrec[r].next = r + 1 < G ? (r + 1) * (int)sizeof(VisitRec) : 0;
     }
     __syncthreads();
     // (d) constants in visit order (reloaded: nothing is held across the syncs)
@@ -507,13 +518,42 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     // + w0g), the range test one compare with ng_end, and the refill one
     // shift-add or mad.  Rows and Philox blocks stay below 2^32 in this kernel
     // (launch_prune_t), and w0g + ng + group is taken mod 2^32 like n * G +
-    // group; ng itself is at most (per_wave + 64 (G + 1)) * G, far below 2^32
-    // (a wave's share is a quarter of a tile).  The wave-uniform values are
-    // made scalar once per tile, so the loop's counters run on the SALU.
+    // group; ng itself stays below (per_wave + 128) * G, far below 2^32 (a
+    // wave's share is a quarter of a tile; see the refill below).  The
+    // wave-uniform values are made scalar once per tile, so the loop's
+    // counters run on the SALU.
     const uint32_t w0g =
         (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)w0 * (uint32_t)G));
-    const uint32_t ng_end = (uint32_t)__builtin_amdgcn_readfirstlane(
-        (int)(w1 > w0 ? (uint32_t)(w1 - w0) * (uint32_t)G : 0u));
+    const uint32_t wrows = w1 > w0 ? (uint32_t)(w1 - w0) : 0u;  // R, the wave's share
+    const uint32_t ng_end =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(wrows * (uint32_t)G));
+    // Static-stride refill (cwq_refill.h).  The first S = refill_static_rows(R)
+    // rows of the share are handed out without any lane arithmetic: lane l
+    // owns rows l, l + 64, ... below S, and a finished lane moves on with
+    // ng += 64 G.  The rows [S, R) are the dynamic pool, handed to finished
+    // lanes by rank from the wave-uniform counter wnext_g, which starts at
+    // refill_pool_start(S) * G.  ng_stat = S * G.
+    //   * Every row of [0, R) is started by exactly one lane, and no row
+    //     outside it: the static rows of different lanes are disjoint by
+    //     construction (S is a multiple of 64, so each lane owns S / 64 of
+    //     them), a lane's ng reaches or passes ng_stat only when its last
+    //     static row is done, and from then on it takes pool rows only, which
+    //     the rank arithmetic hands out once each (refill_sim.cpp replays
+    //     this on the host).  A row at or past ng_end makes its lane inactive.
+    //   * With S = 0 (R < 128: tiles of 256 candidates, short tail tiles)
+    //     every lane starts on row `lane`, ng >= ng_stat = 0 always holds and
+    //     every finished lane refills from the pool, which starts at row 64.
+    //   * ng + 64 G cannot wrap: a lane's ng is below ng_end + 64 G before the
+    //     add (static rows are below ng_stat <= ng_end, pool rows below
+    //     wnext_g + 64 G with wnext_g kept at or below ng_end), and ng_end
+    //     is at most a quarter of a tile's Philox blocks, far below 2^32.
+    //   * Which lane scores a row, and when, changes nothing else: tau stays
+    //     wave-uniform (the keep branch and the share are as they were), and
+    //     a survivor's row is n = (w0g + ng) / G as before.
+    const uint32_t ng_stat = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(cwq::refill_static_rows(wrows) * (uint32_t)G));
+    const uint32_t ng_pool0 = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(cwq::refill_pool_start(cwq::refill_static_rows(wrows)) * (uint32_t)G));
 #ifndef CWQ_TAU_FROM_KEYS
 #define CWQ_TAU_FROM_KEYS 1  // INTER: start the lanes' tau at keys[g]'s value, not at the first share
 #endif
@@ -531,25 +571,29 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       // visit position: the screening pass carries it as the byte offset of
       // its VisitRec, the exact pass as the index k of meta[k] and cst
       constexpr uint32_t KS = SCREEN ? (uint32_t)sizeof(VisitRec) : 1u;
+      constexpr bool LINKED = SCREEN && CWQ_LINKED_VISIT;
       uint32_t ng = lane * (uint32_t)G;
-      uint32_t wnext_g = 64u * (uint32_t)G;  // (next unassigned row - w0) * G: wave-uniform
+      uint32_t wnext_g = ng_pool0;  // (next unassigned pool row - w0) * G: wave-uniform
       uint32_t kp = 0;
       float s = 0.0f;
       uint32_t iter = 0;
-      // a lane is active while its row is in the wave's range: one compare per
-      // iteration, taken after the refill, its mask carried in SGPRs.  The
-      // loop's only exit is at its end, so its wave-uniform counters (iter,
-      // wnext_g) stay scalar.
+      // a lane is active while its row is in the wave's range: the compare is
+      // taken in the pool refill only (static rows are in range), its mask
+      // carried in SGPRs.  The loop's only exit is at its end, so its
+      // wave-uniform counters (iter, wnext_g) stay scalar.
       bool active = ng < ng_end;
       uint64_t m_act = __builtin_amdgcn_ballot_w64(active);
       while (m_act != 0ull) {
         int2 mt;
         float4 sa, sb;
+        uint32_t kp_next = 0;
         if constexpr (SCREEN) {
           const char* rp = reinterpret_cast<const char*>(vrec) + kp;
           sa = *reinterpret_cast<const float4*>(rp);
           sb = *reinterpret_cast<const float4*>(rp + 16);
-          mt = *reinterpret_cast<const int2*>(rp + 32);
+          const int4 lk = *reinterpret_cast<const int4*>(rp + 32);
+          mt = int2{lk.x, lk.y};
+          kp_next = (uint32_t)lk.z;
         } else {
           mt = meta[kp];
         }
@@ -607,8 +651,13 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           s = s + lp_from_z(y3, cc.w);
           upper = (s + __builtin_fabsf(s) * kPruneC1) + u2f((uint32_t)mt.y);
         }
-        kp += KS;
-        const bool complete = (kp == KS * (uint32_t)G);
+        // the screening pass follows the records' links (the last one's is 0:
+        // the completion test), the exact pass counts
+        if constexpr (LINKED)
+          kp = kp_next;
+        else
+          kp += KS;
+        const bool complete = LINKED ? (kp == 0u) : (kp == KS * (uint32_t)G);
         const bool below = upper < tau;
         // Screening pass: one compare of (upper, tau) serves the drop test and
         // the keep test, !(upper < tau) == (upper >= tau), because neither is
@@ -625,7 +674,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         const bool reach = SCREEN ? !below : (upper >= tau);
 #ifdef CWQ_PRUNE_STATS
         const bool prune = !complete && below;
-        const uint32_t k = kp / KS;
+        const uint32_t k = (LINKED && complete) ? (uint32_t)G : kp / KS;
 #endif
         const bool done = complete || below || !active;
         // the finished lanes' mask from the compares' own masks (SALU).  The
@@ -694,20 +743,44 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         if (active && (complete || prune)) atomicAdd(&s_ps[k], 1u);
         if (active && complete) atomicAdd(&s_ps[65], 1u);
 #endif
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        // a finished lane steps to its next static row.  The empty asm keeps
+        // this a branch on the exec mask (one add and two moves under it):
+        // turned into selects it is an add and three v_cndmask for all lanes
         if (done) {
-          ng = wnext_g + rank * (uint32_t)G;
+          asm volatile("" : "+v"(ng));
+          ng += 64u * (uint32_t)G;
           kp = 0;
           s = 0.0f;
         }
-        wnext_g += (uint32_t)__builtin_popcountll(m) * (uint32_t)G;
         // share tau across the workgroup's waves: it is wave-uniform already,
         // so one returning LDS max by lane 0 and one v_max, no reduce (and no
         // "raised since the last share" flag: both of its arms would be this)
         if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) tau = tau_share_wave(&tau_cell, tau);
-        active = ng < ng_end;
-        m_act = __builtin_amdgcn_ballot_w64(active);
+        // Pool refill, taken by the whole wave when a finished lane has left
+        // its static rows (or was in the pool, or inactive: ng >= ng_stat):
+        // those lanes take pool rows by rank, and the range test, which only a
+        // pool row can fail, is taken here.  Lanes still on a row keep their
+        // ng: static rows are below ng_stat <= ng_end, pool rows in progress
+        // passed the test when they were handed out, inactive lanes are all
+        // finished lanes, so the compare gives every lane's `active` anew.
+        // wnext_g is kept at or below ng_end (rows from there on are out of
+        // range alike), which bounds ng however long lanes stay inactive.
+        const uint64_t m_pool = m & __builtin_amdgcn_uicmp(ng, ng_stat, 35 /* uge */);
+        if (m_pool != 0ull) {
+#ifdef CWQ_PRUNE_STATS
+          if (lane == 0) atomicAdd(&s_ps[70], 1u);
+#endif
+          const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
+              (uint32_t)(m_pool >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_pool, 0u));
+          if (done && ng >= ng_stat) ng = wnext_g + rank * (uint32_t)G;
+          wnext_g += (uint32_t)__builtin_popcountll(m_pool) * (uint32_t)G;
+          wnext_g = wnext_g < ng_end ? wnext_g : ng_end;
+          active = ng < ng_end;
+          m_act = __builtin_amdgcn_ballot_w64(active);
+        }
+#ifdef CWQ_PRUNE_STATS
+        if (lane == 0) atomicAdd(&s_ps[71], 1u);
+#endif
       }
     };
 #ifdef CWQ_PRUNE_STATS

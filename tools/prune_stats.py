@@ -46,6 +46,9 @@ print(f"completed rows {a[65]:.0f} ({a[65] / nb:.2f}/block), survivors pushed {a
       f"({a[66] / nb:.2f}/block), screened tiles {a[67]:.0f}")
 print(f"survivors re-evaluated exactly {a[68]:.0f} ({a[68] / nb:.2f}/block), "
       f"in-loop exact evaluations (list full) {a[69]:.0f}")
+if a[71]:  # builds with the static-stride refill count their loop iterations
+    print(f"wave-iterations {a[71]:.0f}, of them through the pool refill {a[70]:.0f} "
+          f"({a[70] / a[71]:.4f})")
 if "--json" in sys.argv:   # record for bench.py's roofline.valu.evaluated
     import json
     path = sys.argv[sys.argv.index("--json") + 1]
