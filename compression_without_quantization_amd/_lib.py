@@ -140,6 +140,13 @@ SIGNATURES = {
     "cwq_selftest_encode_rows_wave": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                               c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp,
                                               c_size, c_vp]),
+    "cwq_beam_encode_workspace_size": (c_size, [c_i64, c_i64, c_i64, c_int, c_int]),
+    "cwq_beam_encode": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int,
+                                c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_size, c_opts,
+                                c_vp]),
+    "cwq_selftest_beam_encode": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
+                                         c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                         c_size, c_opts, c_vp, c_int]),
     "cwq_pln_posterior": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "cwq_permute_gather": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "cwq_permute_scatter": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
@@ -157,7 +164,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 10
+ABI_VERSION = (0 << 16) | 11
 
 _lib = None
 

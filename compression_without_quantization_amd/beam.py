@@ -1,0 +1,127 @@
+"""The greedy coder with a beam over its steps.
+
+``encode_blocks`` keeps the single best partial sum after every step.  With
+more than one step that is a poor search: the best row of step 1 need not lie
+on the best two-step path.  The calls here keep the ``beam`` best partial sums
+instead (cwq_beam_encode, include/cwq.h states the definition).  Every beam of
+a step is scored against the same candidate rows, so the result is still one
+row index per step: the indices, the bit string and the ``.miracle`` file are
+those of the greedy coder, and every existing decoder reads them.  A beam
+sample has a higher target log-density than the greedy one on average, not
+block by block; ``beam=1`` is the greedy coder bit for bit.
+
+  encode_blocks_beam               encode_blocks with a beam
+  code_grouped_greedy_sample_beam  code_grouped_greedy_sample with a beam
+
+All arithmetic runs in libcwq.so; nothing here computes samples on the CPU.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .binary_io import indices_to_bitcode
+from .coded_greedy_sampler import _device_of, _dist_parts, _f32, _group_starts_array, _ptr
+from .varbits import _nb_of, _offsets, _one_of, _seed32
+
+MAX_BEAM = 16  # CWQ_MAX_BEAM
+
+
+def beam_workspace_bytes(nb, total_dims, max_block_dim, n_steps, beam):
+    """Workspace bytes of encode_blocks_beam (cwq_beam_encode_workspace_size):
+    about ``(3 + 2 beam) * 4`` bytes per dim plus the key lists."""
+    return int(_lib.load().cwq_beam_encode_workspace_size(
+        int(nb), int(total_dims), int(max_block_dim), int(n_steps), int(beam)))
+
+
+def encode_blocks_beam(t_loc, t_scale, p_loc, p_scale, n_bits_per_step, n_steps, seed, beam,
+                       rho=1., block_dim=None, block_off=None, block_id_base=0,
+                       return_value=False, workspace=None, eval_events=None, _path=None):
+    """encode_blocks with the ``beam`` best partial sums kept after each step
+    (1 <= beam <= 16, any value; ``beam * 2**n_bits_per_step <= 2**31``).
+
+    Blocks are uniform (``block_dim``) or ragged (``block_off``, nb + 1
+    offsets); block g is coded with seed ``seed + block_id_base + g``.  Returns
+    (idx int32 [nb, n_steps], sample f32 [D]) as cuda tensors, and with
+    ``return_value`` also the log-density the last step's selection saw for the
+    returned sample (f32 [nb]).  The outputs feed ``decode_blocks`` and
+    ``indices_to_bitcode`` unchanged.  The call is asynchronous on the current
+    stream and can be captured into a graph (pass ``workspace`` then);
+    ``eval_events``: (start, stop) hipEvent_t handles around the scoring launches.
+    """
+    lib = _lib.load()
+    _one_of(block_dim, block_off)
+    dev = _device_of(t_loc, t_scale, p_loc, p_scale)
+    tl = _f32(t_loc, dev, "t_loc")
+    ts = _f32(t_scale, dev, "t_scale")
+    pl = _f32(p_loc, dev, "p_loc")
+    ps = _f32(p_scale, dev, "p_scale")
+    D = tl.numel()
+    if not (ts.numel() == pl.numel() == ps.numel() == D):
+        raise ValueError("t_loc, t_scale, p_loc, p_scale must have the same size")
+    if block_off is not None:
+        offs, nb, longest = _offsets(block_off, D, dev)
+    else:
+        longest, nb = _nb_of(D, block_dim)
+        offs = None
+    n_steps, beam = int(n_steps), int(beam)
+    out_idx = torch.empty((nb, max(n_steps, 0)), dtype=torch.int32, device=dev)
+    out_sample = torch.empty(D, dtype=torch.float32, device=dev)
+    out_value = torch.empty(nb, dtype=torch.float32, device=dev) if return_value else None
+    need = beam_workspace_bytes(nb, D, longest, n_steps, beam)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    opts = _lib.options(None, eval_events)
+    args = (_ptr(tl), _ptr(ts), _ptr(pl), _ptr(ps), offs.data_ptr() if offs is not None else None,
+            nb, D, longest, int(n_bits_per_step), n_steps, beam, _seed32(seed), float(rho),
+            int(block_id_base), _ptr(out_idx), _ptr(out_sample), _ptr(out_value),
+            workspace.data_ptr(), workspace.numel(), opts)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if _path is None:
+            rc = lib.cwq_beam_encode(*args, stream)
+        else:  # the tests' kernel and tiling choice
+            rc = lib.cwq_selftest_beam_encode(*args, stream, int(_path))
+    _lib.check(rc, "cwq_beam_encode")
+    return (out_idx, out_sample, out_value) if return_value else (out_idx, out_sample)
+
+
+def code_grouped_greedy_sample_beam(target, proposal, n_steps, n_bits_per_step, seed, beam,
+                                    max_group_size_bits=12, rho=1.):
+    """code_grouped_greedy_sample with a beam of ``beam`` partial sums per group.
+
+    The standardisation, the per-dim KL and the partition are those of
+    code_grouped_greedy_sample; group g is coded with seed ``seed + g`` on the
+    standard proposal by encode_blocks_beam.  Returns (sample np.float32 [D],
+    bitcode str, group_start_indices list with D appended), the triple of
+    code_grouped_greedy_sample, which ``beam=1`` reproduces;
+    decode_grouped_greedy_sample decodes it.
+    """
+    lib = _lib.load()
+    dev = _device_of(target.loc, target.scale, proposal.loc, proposal.scale)
+    q_loc, q_scale = _dist_parts(target, dev, "Target")
+    p_loc, p_scale = _dist_parts(proposal, dev, "Proposal")
+    D = p_loc.numel()
+    n_steps, n_bits_per_step = int(n_steps), int(n_bits_per_step)
+    t_loc = torch.empty(D, dtype=torch.float32, device=dev)
+    t_scale = torch.empty(D, dtype=torch.float32, device=dev)
+    kl = torch.empty(D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.cwq_standardise(_ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), D,
+                                       _ptr(t_loc), _ptr(t_scale), stream), "cwq_standardise")
+        _lib.check(lib.cwq_kl_normal_normal(_ptr(q_loc), _ptr(q_scale), _ptr(p_loc),
+                                            _ptr(p_scale), D, _ptr(kl), stream),
+                   "cwq_kl_normal_normal")
+    starts = _group_starts_array(kl.cpu().numpy(), n_bits_per_step * n_steps,
+                                 max_group_size_bits)
+    zeros = torch.zeros(D, dtype=torch.float32, device=dev)
+    ones = torch.ones(D, dtype=torch.float32, device=dev)
+    idx, sample = encode_blocks_beam(t_loc, t_scale, zeros, ones, n_bits_per_step, n_steps, seed,
+                                     beam, rho=rho, block_off=starts)
+    out = torch.empty(D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.cwq_destandardise(_ptr(sample), _ptr(p_loc), _ptr(p_scale), D, _ptr(out),
+                                         torch.cuda.current_stream(dev).cuda_stream),
+                   "cwq_destandardise")
+    bitcode = indices_to_bitcode(idx.cpu().numpy(), n_bits_per_step)
+    return out.cpu().numpy(), bitcode, starts.tolist()

@@ -3217,6 +3217,100 @@ int cwq_selftest_encode_rows_wave(const float* t_loc, const float* t_scale, cons
                      nullptr, /*rows_wave=*/true);
 }
 
+namespace {
+int beam_impl(const float* t_loc, const float* t_scale, const float* p_loc, const float* p_scale,
+              const int64_t* block_off, int64_t nb, int64_t total_dims, int64_t max_block_dim,
+              int n_bits, int n_steps, int beam, int32_t seed, float rho, int64_t block_id_base,
+              int32_t* out_idx, float* out_sample, float* out_value, void* workspace,
+              size_t workspace_bytes, const cwq_options* opts, void* stream, int path) {
+  int rc = check_common(n_bits, n_steps, nb);
+  if (rc) return rc;
+  cwq_options o;
+  if ((rc = read_options(opts, &o))) return rc;  // prune_mode: accepted, every row is exact
+  if (beam < 1 || beam > CWQ_MAX_BEAM)
+    return fail(CWQ_ERR_INVALID, "beam=%d outside [1, %d]", beam, CWQ_MAX_BEAM);
+  if (((int64_t)beam << n_bits) > (1LL << 31))
+    return fail(CWQ_ERR_INVALID, "beam * 2^n_bits_per_step = %lld exceeds 2^31",
+                (long long)((int64_t)beam << n_bits));
+  if (total_dims < 0 || max_block_dim < 0)
+    return fail(CWQ_ERR_INVALID, "total_dims and max_block_dim must be >= 0");
+  if (path < -1 || path > 3) return fail(CWQ_ERR_INVALID, "path=%d outside [0, 3]", path);
+  if (!block_off && nb > 0 && (max_block_dim > INT64_MAX / nb || nb * max_block_dim != total_dims))
+    return fail(CWQ_ERR_INVALID, "uniform blocks: total_dims must be nb * max_block_dim");
+  if (nb > 0 && !out_idx) return fail(CWQ_ERR_INVALID, "out_idx is null");
+  if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
+    return fail(CWQ_ERR_INVALID, "null input/output pointer");
+  const cwq::BeamPath plan = cwq::beam_plan(max_block_dim);
+  if (path >= 0 && (path & 1) == 0 && plan != cwq::BeamPath::LanePerRow)
+    return fail(CWQ_ERR_INVALID, "the lane-per-row kernel takes blocks of at most %d dims",
+                CWQ_FUSED_DMAX);
+  const cwq::BeamWs l = cwq::beam_ws_layout(nb, total_dims, n_steps, beam);
+  if (workspace_bytes < l.total || (l.total && !workspace))
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
+                l.total);
+  cwq::BeamArgs a;
+  a.t_loc = t_loc;
+  a.t_scale = t_scale;
+  a.p_loc = p_loc;
+  a.p_scale = p_scale;
+  a.block_off = block_off;
+  a.ud = block_off ? 0 : max_block_dim;
+  a.nb = nb;
+  a.total_dims = total_dims;
+  a.max_d = max_block_dim;
+  a.n_bits = n_bits;
+  a.n_steps = n_steps;
+  a.beam = beam;
+  a.seed = seed;
+  a.rho = rho;
+  a.block_id_base = block_id_base;
+  a.out_idx = out_idx;
+  a.out_sample = out_sample;
+  a.out_value = out_value;
+  a.workspace = workspace;
+  a.ev_start = o.eval_start_event;
+  a.ev_stop = o.eval_stop_event;
+  a.path = path < 0 ? plan
+                    : ((path & 1) ? cwq::BeamPath::WavePerRow : cwq::BeamPath::LanePerRow);
+  a.quarter_tiles = path >= 2;
+  hipError_t e = cwq::launch_beam_encode(a, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_beam_encode");
+  return ok();
+}
+}  // namespace
+
+size_t cwq_beam_encode_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                      int n_steps, int beam) {
+  if (nb < 0 || total_dims < 0 || max_block_dim < 0 || n_steps < 1 || beam < 1 ||
+      beam > CWQ_MAX_BEAM)
+    return 0;
+  return cwq::beam_ws_layout(nb, total_dims, n_steps, beam).total;
+}
+
+int cwq_beam_encode(const float* t_loc, const float* t_scale, const float* p_loc,
+                    const float* p_scale, const int64_t* block_off, int64_t nb,
+                    int64_t total_dims, int64_t max_block_dim, int n_bits_per_step, int n_steps,
+                    int beam, int32_t seed, float rho, int64_t block_id_base, int32_t* out_idx,
+                    float* out_sample, float* out_value, void* workspace, size_t workspace_bytes,
+                    const cwq_options* opts, void* stream) {
+  return beam_impl(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims, max_block_dim,
+                   n_bits_per_step, n_steps, beam, seed, rho, block_id_base, out_idx, out_sample,
+                   out_value, workspace, workspace_bytes, opts, stream, -1);
+}
+
+int cwq_selftest_beam_encode(const float* t_loc, const float* t_scale, const float* p_loc,
+                             const float* p_scale, const int64_t* block_off, int64_t nb,
+                             int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
+                             int n_steps, int beam, int32_t seed, float rho,
+                             int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                             float* out_value, void* workspace, size_t workspace_bytes,
+                             const cwq_options* opts, void* stream, int path) {
+  if (path < 0) return fail(CWQ_ERR_INVALID, "path=%d outside [0, 3]", path);
+  return beam_impl(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims, max_block_dim,
+                   n_bits_per_step, n_steps, beam, seed, rho, block_id_base, out_idx, out_sample,
+                   out_value, workspace, workspace_bytes, opts, stream, path);
+}
+
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream) {
   if (n_waves < 0 || n_waves > (1LL << 31) || (n_waves > 0 && (!x || !out)))
     return fail(CWQ_ERR_INVALID, "cwq_selftest_wave_max: bad arguments");

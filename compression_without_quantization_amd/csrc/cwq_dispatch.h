@@ -120,6 +120,36 @@ inline int encode_fork_parts(const EncodeShape& s, int n_steps) {
   return (int64_t)k < s.nb ? k : (int)s.nb;
 }
 
+// ---- beam search over steps (cwq_beam.hip) -------------------
+// Which scoring kernel a beam encode takes: a lane per candidate row while the
+// longest block fits the lane kernel's LDS row (CWQ_FUSED_DMAX dims), a wave
+// per row otherwise (and when the longest block is unknown).
+enum class BeamPath { LanePerRow, WavePerRow };
+inline BeamPath beam_plan(int64_t max_d) {
+  return max_d >= 0 && max_d <= CWQ_FUSED_DMAX ? BeamPath::LanePerRow : BeamPath::WavePerRow;
+}
+constexpr int64_t kBeamTargetTiles = 2048;  // tiles a scoring launch aims for
+constexpr int64_t kBeamLaneTile = 128;      // smallest tile (rows): a row per lane
+constexpr int64_t kBeamWaveTile = 4;        // ... a row per wave
+// Most tiles one block is ever split into; a function of nb alone, so the
+// workspace (one key list per tile) can be sized without the bit count.  The
+// factor 4 is the tests' quarter-tile knob.
+inline int64_t beam_tiles_cap(int64_t nb) {
+  const int64_t want = nb > 0 ? (kBeamTargetTiles + nb - 1) / nb : 1;
+  int64_t t = 1;
+  while (t < want) t <<= 1;
+  return 4 * t;
+}
+// Tiles per block (a power of two dividing n_cand = 2^b) of one launch.
+inline int64_t beam_tiles_per_block(BeamPath path, int64_t nb, int64_t n_cand, bool quarter) {
+  const int64_t mt = path == BeamPath::LanePerRow ? kBeamLaneTile : kBeamWaveTile;
+  const int64_t most = n_cand > mt ? n_cand / mt : 1;  // tiles of at least mt rows
+  int64_t t = beam_tiles_cap(nb) / 4;
+  t = t < most ? t : most;
+  if (quarter) t = 4 * t < n_cand ? 4 * t : n_cand;
+  return t;
+}
+
 // cwq_greedy_encode_var's bucket rule.  Long rows at few candidates (DESIGN.md
 // 4e): below kCsrPrunedMinCand candidates the other paths walk a row with one
 // lane, so a bucket of `count` blocks at `bits` bits whose mean block reaches

@@ -280,6 +280,52 @@ hipError_t launch_vbc_scatter(const float* sample_s, const int32_t* idx_s, const
                               int n_steps, float* out_sample, int32_t* out_idx,
                               hipStream_t stream);
 
+// ---- beam search over steps (cwq_beam.hip) -------------------
+constexpr int kMaxBeam = 16;  // CWQ_MAX_BEAM
+// Workspace of one beam encode (byte offsets, each a multiple of 256):
+//   loc_s, scale_s, lognorm  [total_dims] f32: the step's shard and normaliser
+//   beams   [2][beam][total_dims] f32: the running sums, ping-pong
+//   tiles   [nb][beam_tiles_cap(nb)][beam] u64: every tile's largest keys
+//   sel     [nb][n_steps][beam] u64: the selected keys, sorted; key j of a step
+//           names beam j's parent and row (candidate parent * 2^b + row)
+struct BeamWs {
+  size_t loc_s, scale_s, lognorm, beams, tiles, sel, total;
+};
+inline BeamWs beam_ws_layout(int64_t nb, int64_t total_dims, int n_steps, int beam) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  BeamWs l;
+  const size_t dims = up((size_t)total_dims * 4);
+  l.loc_s = 0;
+  l.scale_s = dims;
+  l.lognorm = 2 * dims;
+  l.beams = 3 * dims;
+  l.tiles = l.beams + up((size_t)2 * beam * total_dims * 4);
+  l.sel = l.tiles + up((size_t)nb * beam_tiles_cap(nb) * beam * 8);
+  l.total = l.sel + up((size_t)nb * n_steps * beam * 8);
+  return l;
+}
+struct BeamArgs {
+  const float* t_loc;
+  const float* t_scale;
+  const float* p_loc;
+  const float* p_scale;
+  const int64_t* block_off;  // nullptr -> uniform blocks of dimension ud
+  int64_t ud, nb, total_dims, max_d;
+  int n_bits, n_steps, beam;
+  int32_t seed;
+  float rho;
+  int64_t block_id_base;
+  int32_t* out_idx;
+  float* out_sample;
+  float* out_value;  // or nullptr
+  void* workspace;   // beam_ws_layout(nb, total_dims, n_steps, beam).total bytes
+  void* ev_start;    // hipEvent_t around the scoring launches, or nullptr
+  void* ev_stop;
+  BeamPath path;
+  bool quarter_tiles;  // tests: tiles a quarter of the size (same results)
+};
+hipError_t launch_beam_encode(const BeamArgs& a, hipStream_t stream);
+
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);
 hipError_t launch_selftest_screen(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,

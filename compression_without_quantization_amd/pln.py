@@ -51,6 +51,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .beam import code_grouped_greedy_sample_beam
 from .binary_io import _pack_bits, read_bin_code, write_bin_code
 from .coded_greedy_sampler import (Normal, code_grouped_greedy_sample,
                                    decode_grouped_greedy_sample)
@@ -525,7 +526,7 @@ class ProbabilisticLadderNetwork(nn.Module):
                           return_second_level_group_sizes=False,
                           return_second_level_indices=False, verbose=False, *,
                           capture=None, first_level_group_bits=False, first_level_min_bits=0,
-                          first_level_bits_dist_counts=""):
+                          first_level_bits_dist_counts="", beam_width=1):
         """pln.py:213-627.  ``session`` is ignored.  Writes the .miracle file to
         comp_file_path and returns ((sample2, sample1), summaries), or what the
         return_* flags ask for.  Group-size count models are .npy paths or
@@ -542,8 +543,19 @@ class ProbabilisticLadderNetwork(nn.Module):
         the budgets travel as a third variable bit string, arithmetic-coded
         under ``first_level_bits_dist_counts`` (symbol n_bits_per_step - bits + 1;
         uniform over n_bits_per_step + 2 symbols when empty).  The decoder must
-        be given the same flag and count model."""
+        be given the same flag and count model.
+        ``beam_width`` (keyword only, not in the reference): above 1 the greedy
+        level 1 keeps that many partial sums per group and step
+        (code_grouped_greedy_sample_beam) instead of one; the file format and
+        decode_image_greedy are unchanged.  1 is the plain call."""
         del session, backfitting_steps_level_1, backfitting_steps_level_2, use_log_prob
+        beam_width = int(beam_width)
+        if beam_width < 1:
+            raise ValueError(f"beam_width={beam_width} must be >= 1")
+        if beam_width > 1 and (use_importance_sampling or first_level_group_bits):
+            raise ValueError("beam_width > 1 needs use_importance_sampling=False and "
+                             "first_level_group_bits=False: the beam belongs to the plain "
+                             "greedy level-1 coder")
         if first_level_group_bits and use_importance_sampling:
             raise ValueError("first_level_group_bits needs use_importance_sampling=False: the "
                              "budgets belong to the greedy level-1 coder")
@@ -629,6 +641,14 @@ class ProbabilisticLadderNetwork(nn.Module):
                     min_bits=first_level_min_bits)
             code1 = _chars_of(code1_bytes, total_bits)
             keep("level1", q1p, p1p, (sample1, code1, group_indices1, group_bits1), "greedy_var")
+            if return_first_level_group_sizes:
+                return np.asarray(group_indices1)
+            outlier_extras1 = None
+        elif beam_width > 1:
+            sample1, code1, group_indices1 = code_grouped_greedy_sample_beam(
+                q1p, p1p, n_steps, n_bits_per_step, seed, beam_width,
+                max_group_size_bits=greedy_max_group_size_bits, rho=rho)
+            keep("level1", q1p, p1p, (sample1, code1, group_indices1), "greedy_beam")
             if return_first_level_group_sizes:
                 return np.asarray(group_indices1)
             outlier_extras1 = None

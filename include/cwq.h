@@ -25,6 +25,10 @@
  *   cwq_code_grouped_greedy      <- code/coded_greedy_sampler.py:170-296
  *                                   (the whole grouped coder in one call)
  *   cwq_code_grouped_greedy_batch <- the same, once per item of a batch
+ *   cwq_beam_encode              <- code/coded_greedy_sampler.py:29-89 with the B
+ *                                   best partial sums kept after each step
+ *                                   instead of one (not in the reference; its
+ *                                   decoders read the result unchanged)
  *   cwq_decode_grouped_greedy_batch <- code/coded_greedy_sampler.py:299-364
  *                                   decode_grouped_greedy_sample, once per item
  *   cwq_decode_grouped_importance_batch <- code/coded_importance_sampler.py:
@@ -97,8 +101,10 @@ extern "C" {
  *        cwq_greedy_encode_var and its workspace size;
  *   0.10 cwq_selftest_encode_rows_wave; cwq_greedy_encode_var codes buckets of
  *        long blocks below 4,096 candidates with a wave per candidate row
- *        (same results as before). */
-#define CWQ_ABI_VERSION ((0 << 16) | 10)
+ *        (same results as before);
+ *   0.11 beam search over the greedy coder's steps: cwq_beam_encode, its
+ *        workspace size and cwq_selftest_beam_encode (no decoder change). */
+#define CWQ_ABI_VERSION ((0 << 16) | 11)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -649,6 +655,61 @@ int cwq_selftest_encode_rows_wave(const float* t_loc, const float* t_scale, cons
                                   int32_t* out_idx, float* out_sample, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- Beam search over the greedy coder's steps (csrc/cwq_beam.hip) --------
+ * cwq_greedy_encode keeps the one best partial sum after each step; this
+ * encoder keeps the `beam` best.  State after step i: L_i live beams (L_0 = 1,
+ * the all-zero sum; L_{i+1} = min(beam, L_i 2^b)), each a float32 running sum
+ * and its path of i row indices.  Step i scores every live beam k against the
+ * rows r < 2^b of the step's candidate stream (the same rows for every beam,
+ * the stream cwq_greedy_encode draws): candidate c = k 2^b + r has the value
+ * v = sum_j log N(sum_k[j] + row_r[j]; t_loc[j], t_scale[j]) (float32, the
+ * greedy coder's arithmetic and summation order) and the key (v, c), where a
+ * NaN or a value <= -FLT_MAX counts as -FLT_MAX, -0 as +0, and the lower c
+ * wins a tie.  The L_{i+1} candidates with the largest keys, in decreasing
+ * order, become the new beams: sum_k + row_r, path_k followed by r.  After
+ * the last step beam 0 is the result.  The selection is a function of the
+ * candidate set alone; results never depend on the launch geometry.
+ *   beam       1 <= beam <= CWQ_MAX_BEAM, any value; beam * 2^n_bits_per_step
+ *              <= 2^31.  With beam = 1 the outputs are cwq_greedy_encode's.
+ *   block_off  device [nb + 1], or NULL for uniform blocks of max_block_dim
+ *              dims (total_dims = nb * max_block_dim)
+ *   out_idx    [nb * n_steps] int32: beam 0's row index of every step; any
+ *              greedy decoder turns them back into out_sample (the bit string
+ *              and every file format are those of the greedy coder)
+ *   out_sample [total_dims] f32: beam 0's sum
+ *   out_value  [nb] f32 or NULL: beam 0's value v of the last step as its key
+ *              holds it (an empty block: indices 0, value +0)
+ *   opts       prune_mode is accepted and ignored (every row is scored
+ *              exactly); the eval events bracket the scoring launches.
+ * Blocks whose longest has at most 64 dims are scored with a lane per
+ * candidate row, longer ones with a wave per row; a row is drawn once and
+ * scored against all beams.  Asynchronous on `stream`, no host
+ * synchronisation, no other stream: capturable into a graph.
+ * Workspace bytes (each array rounded up to 256): 3 * 4 * total_dims (shard
+ * constants) + 2 * beam * 4 * total_dims (the beams' sums, ping-pong) +
+ * 8 * beam * nb * T(nb) (per-tile key lists, T(nb) = 4 * the power of two at
+ * or above ceil(2048 / nb)) + 8 * beam * nb * n_steps (the selected keys).
+ * It is large: a call whose workspace does not fit is the caller's to split. */
+#define CWQ_MAX_BEAM 16
+size_t cwq_beam_encode_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                      int n_steps, int beam);
+int cwq_beam_encode(const float* t_loc, const float* t_scale, const float* p_loc,
+                    const float* p_scale, const int64_t* block_off, int64_t nb,
+                    int64_t total_dims, int64_t max_block_dim, int n_bits_per_step, int n_steps,
+                    int beam, int32_t seed, float rho, int64_t block_id_base, int32_t* out_idx,
+                    float* out_sample, float* out_value, void* workspace, size_t workspace_bytes,
+                    const cwq_options* opts, void* stream);
+/* The same call on the scoring kernel `path` names instead of the one the
+ * block lengths select: 0 lane per row (max_block_dim <= 64 only), 1 wave per
+ * row; 2 and 3: the same two with tiles a quarter of the size.  The tests hold
+ * all four to the same bits. */
+int cwq_selftest_beam_encode(const float* t_loc, const float* t_scale, const float* p_loc,
+                             const float* p_scale, const int64_t* block_off, int64_t nb,
+                             int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
+                             int n_steps, int beam, int32_t seed, float rho,
+                             int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                             float* out_value, void* workspace, size_t workspace_bytes,
+                             const cwq_options* opts, void* stream, int path);
 
 
 /* ---- PLN image codec plumbing (csrc/cwq_pln.hip) ----
