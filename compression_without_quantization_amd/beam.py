@@ -85,17 +85,11 @@ def encode_blocks_beam(t_loc, t_scale, p_loc, p_scale, n_bits_per_step, n_steps,
     return (out_idx, out_sample, out_value) if return_value else (out_idx, out_sample)
 
 
-def code_grouped_greedy_sample_beam(target, proposal, n_steps, n_bits_per_step, seed, beam,
-                                    max_group_size_bits=12, rho=1.):
-    """code_grouped_greedy_sample with a beam of ``beam`` partial sums per group.
-
-    The standardisation, the per-dim KL and the partition are those of
-    code_grouped_greedy_sample; group g is coded with seed ``seed + g`` on the
-    standard proposal by encode_blocks_beam.  Returns (sample np.float32 [D],
-    bitcode str, group_start_indices list with D appended), the triple of
-    code_grouped_greedy_sample, which ``beam=1`` reproduces;
-    decode_grouped_greedy_sample decodes it.
-    """
+def _code_grouped_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
+                       max_group_size_bits):
+    """code_grouped_greedy_sample's pipeline around a block encoder: standardise,
+    per-dim KL, partition, ``encode(t_loc, t_scale, zeros, ones, starts)`` ->
+    (idx, sample) on the standard proposal, destandardise, bit string."""
     lib = _lib.load()
     dev = _device_of(target.loc, target.scale, proposal.loc, proposal.scale)
     q_loc, q_scale = _dist_parts(target, dev, "Target")
@@ -116,8 +110,7 @@ def code_grouped_greedy_sample_beam(target, proposal, n_steps, n_bits_per_step, 
                                  max_group_size_bits)
     zeros = torch.zeros(D, dtype=torch.float32, device=dev)
     ones = torch.ones(D, dtype=torch.float32, device=dev)
-    idx, sample = encode_blocks_beam(t_loc, t_scale, zeros, ones, n_bits_per_step, n_steps, seed,
-                                     beam, rho=rho, block_off=starts)
+    idx, sample = encode(t_loc, t_scale, zeros, ones, starts)
     out = torch.empty(D, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.cwq_destandardise(_ptr(sample), _ptr(p_loc), _ptr(p_scale), D, _ptr(out),
@@ -125,3 +118,21 @@ def code_grouped_greedy_sample_beam(target, proposal, n_steps, n_bits_per_step, 
                    "cwq_destandardise")
     bitcode = indices_to_bitcode(idx.cpu().numpy(), n_bits_per_step)
     return out.cpu().numpy(), bitcode, starts.tolist()
+
+
+def code_grouped_greedy_sample_beam(target, proposal, n_steps, n_bits_per_step, seed, beam,
+                                    max_group_size_bits=12, rho=1.):
+    """code_grouped_greedy_sample with a beam of ``beam`` partial sums per group.
+
+    The standardisation, the per-dim KL and the partition are those of
+    code_grouped_greedy_sample; group g is coded with seed ``seed + g`` on the
+    standard proposal by encode_blocks_beam.  Returns (sample np.float32 [D],
+    bitcode str, group_start_indices list with D appended), the triple of
+    code_grouped_greedy_sample, which ``beam=1`` reproduces;
+    decode_grouped_greedy_sample decodes it.
+    """
+    def encode(t_loc, t_scale, zeros, ones, starts):
+        return encode_blocks_beam(t_loc, t_scale, zeros, ones, n_bits_per_step, n_steps, seed,
+                                  beam, rho=rho, block_off=starts)
+    return _code_grouped_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
+                              max_group_size_bits)

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcwq.so")
 SOURCES = ["cwq_kernels.hip", "cwq_importance.hip", "cwq_pln.hip", "cwq_partition.hip",
-           "cwq_varbits.hip", "cwq_beam.hip", "cwq_capi.hip", "cwq_ac.cpp"]
+           "cwq_varbits.hip", "cwq_beam.hip", "cwq_backfit.hip", "cwq_capi.hip", "cwq_ac.cpp"]
 HEADERS = ["cwq_math.h", "cwq_screen.h", "cwq_dispatch.h", "cwq_kernels.h", "cwq_device.h",
            "cwq_debug.h", "cwq_refill.h"]
 

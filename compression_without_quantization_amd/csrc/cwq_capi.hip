@@ -344,6 +344,29 @@ int check_common(int n_bits, int n_steps, int64_t nb) {
   return CWQ_OK;
 }
 
+// The encoder's arrays of layout l in the caller's workspace.
+void carve_ws(cwq::EncodeArgs& a, const WsLayout& l, void* workspace) {
+  char* w = (char*)workspace;
+  a.keys = (unsigned long long*)(w + l.keys);
+  a.tq = (uint32_t*)(w + l.tq);
+  a.loc_s = (float*)(w + l.loc_s);
+  a.scale_s = (float*)(w + l.scale_s);
+  a.lognorm = (float*)(w + l.lognorm);
+  a.sab = l.csr ? (float2*)(w + l.sab) : nullptr;
+  a.cdim = l.csr ? (float*)(w + l.cdim) : nullptr;
+  a.bpre = l.csr ? (float*)(w + l.bpre) : nullptr;
+  a.ordu = l.csr ? (uint32_t*)(w + l.ordu) : nullptr;
+  a.grp = l.csr ? (float4*)(w + l.grp) : nullptr;
+  a.gtau = l.csr ? (uint32_t*)(w + l.gtau) : nullptr;
+#ifdef CWQ_NO_RECS
+  a.abp = nullptr;
+#else
+  a.abp = l.recs ? (float4*)(w + l.abp) : nullptr;
+#endif
+  a.slist = l.csr ? (uint2*)(w + l.slist) : nullptr;
+  a.sdmap = l.csr ? (uint32_t*)(w + l.sdmap) : nullptr;
+}
+
 int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
                 const float* p_scale, const int64_t* block_off, int64_t ud, int64_t nb,
                 int64_t total_dims, int64_t max_block_dim, int n_bits, int n_steps, int32_t seed, float rho,
@@ -387,25 +410,7 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
   a.seeds = block_seeds;
   a.out_idx = out_idx;
   a.out_sample = out_sample;
-  char* w = (char*)workspace;
-  a.keys = (unsigned long long*)(w + l.keys);
-  a.tq = (uint32_t*)(w + l.tq);
-  a.loc_s = (float*)(w + l.loc_s);
-  a.scale_s = (float*)(w + l.scale_s);
-  a.lognorm = (float*)(w + l.lognorm);
-  a.sab = l.csr ? (float2*)(w + l.sab) : nullptr;
-  a.cdim = l.csr ? (float*)(w + l.cdim) : nullptr;
-  a.bpre = l.csr ? (float*)(w + l.bpre) : nullptr;
-  a.ordu = l.csr ? (uint32_t*)(w + l.ordu) : nullptr;
-  a.grp = l.csr ? (float4*)(w + l.grp) : nullptr;
-  a.gtau = l.csr ? (uint32_t*)(w + l.gtau) : nullptr;
-#ifdef CWQ_NO_RECS
-  a.abp = nullptr;
-#else
-  a.abp = l.recs ? (float4*)(w + l.abp) : nullptr;
-#endif
-  a.slist = l.csr ? (uint2*)(w + l.slist) : nullptr;
-  a.sdmap = l.csr ? (uint32_t*)(w + l.sdmap) : nullptr;
+  carve_ws(a, l, workspace);
   a.ev_start = o.eval_start_event;
   a.ev_stop = o.eval_stop_event;
   a.ds_out = ds_out;
@@ -3309,6 +3314,80 @@ int cwq_selftest_beam_encode(const float* t_loc, const float* t_scale, const flo
   return beam_impl(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims, max_block_dim,
                    n_bits_per_step, n_steps, beam, seed, rho, block_id_base, out_idx, out_sample,
                    out_value, workspace, workspace_bytes, opts, stream, path);
+}
+
+size_t cwq_greedy_backfit_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                         int n_steps) {
+  if (nb < 0 || total_dims < 0 || max_block_dim < 0 || n_steps < 1) return 0;
+  // sized for either layout of the blocks: ragged needs the most
+  const WsLayout l = ws_layout_csr(nb, total_dims, max_block_dim);
+  return cwq::backfit_ws_layout(l.total, nb, total_dims, n_steps).total;
+}
+
+int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_loc,
+                       const float* p_scale, const int64_t* block_off, int64_t nb,
+                       int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
+                       int n_steps, int sweeps, int32_t seed, float rho, int64_t block_id_base,
+                       int32_t* idx_inout, float* out_sample, float* out_value,
+                       int32_t* out_accepted, void* workspace, size_t workspace_bytes,
+                       const cwq_options* opts, void* stream) {
+  int rc = check_common(n_bits_per_step, n_steps, nb);
+  if (rc) return rc;
+  cwq_options o;
+  if ((rc = read_options(opts, &o))) return rc;
+  if (sweeps < 0 || sweeps > CWQ_MAX_BACKFIT_SWEEPS)
+    return fail(CWQ_ERR_INVALID, "sweeps=%d outside [0, %d]", sweeps, CWQ_MAX_BACKFIT_SWEEPS);
+  if (total_dims < 0 || max_block_dim < 0)
+    return fail(CWQ_ERR_INVALID, "total_dims and max_block_dim must be >= 0");
+  if (!block_off && nb > 0 && (max_block_dim > INT64_MAX / nb || nb * max_block_dim != total_dims))
+    return fail(CWQ_ERR_INVALID, "uniform blocks: total_dims must be nb * max_block_dim");
+  if (nb > 0 && !idx_inout) return fail(CWQ_ERR_INVALID, "idx_inout is null");
+  if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
+    return fail(CWQ_ERR_INVALID, "null input/output pointer");
+  if (nb == 0) return ok();  // no block: nothing to refine, nothing is launched
+  const bool csr = block_off != nullptr;
+  const WsLayout l = csr ? ws_layout_csr(nb, total_dims, max_block_dim)
+                         : ws_layout_uniform(nb, max_block_dim);
+  // the size asked for is the ragged layout's, which no uniform layout exceeds
+  const size_t need = cwq_greedy_backfit_workspace_size(nb, total_dims, max_block_dim, n_steps);
+  if (workspace_bytes < need || (need && !workspace))
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  const cwq::BackfitWs bl = cwq::backfit_ws_layout(l.total, nb, total_dims, n_steps);
+  cwq::BackfitArgs b;
+  cwq::EncodeArgs& a = b.enc;
+  a.t_loc = t_loc;
+  a.t_scale = t_scale;
+  a.p_loc = p_loc;
+  a.p_scale = p_scale;
+  a.block_off = block_off;
+  a.ud = csr ? 0 : max_block_dim;
+  a.nb = nb;
+  a.total_dims = total_dims;
+  a.max_d = max_block_dim;
+  a.n_cand = (int64_t)1 << n_bits_per_step;
+  choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
+  a.n_steps = n_steps;
+  a.prune = o.prune_mode;
+  a.seed = seed;
+  a.rho = rho;
+  a.block_id_base = block_id_base;
+  a.seeds = nullptr;
+  a.out_idx = idx_inout;
+  a.out_sample = out_sample;
+  carve_ws(a, l, workspace);
+  a.ev_start = o.eval_start_event;
+  a.ev_stop = o.eval_stop_event;
+  char* w = (char*)workspace;
+  b.sweeps = sweeps;
+  b.rows = (float*)(w + bl.rows);
+  b.value = (float*)(w + bl.value);
+  b.count = (int32_t*)(w + bl.count);
+  b.out_value = out_value;
+  b.out_accepted = out_accepted;
+  b.path = cwq::backfit_plan(max_block_dim, nb);
+  hipError_t e = cwq::launch_backfit(b, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit");
+  return ok();
 }
 
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream) {

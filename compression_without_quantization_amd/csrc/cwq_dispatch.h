@@ -58,6 +58,10 @@ struct EncodeShape {
   int64_t n_cand;  // 2^n_bits_per_step
   int prune;       // cwq_options.prune_mode
   bool rows_wave;  // the caller forces k_encode_rows_wave (bucket_takes_rows_wave)
+  // the caller wants the step's argmax keys and nothing else (backfitting,
+  // DESIGN.md 4g): the small pipeline writes indices and sample itself, so its
+  // shapes take the three-kernel path
+  bool keys_only = false;
 };
 
 enum class EncodePath { RowsWave, UniformPruned, CsrPruned, SmallPipe, SmallThree, Eval };
@@ -102,8 +106,8 @@ inline EncodePlan encode_plan(const EncodeShape& s) {
   else if (screened && s.n_cand >= kCsrPrunedMinCand)
     path = EncodePath::CsrPruned;
   else if (screened && s.n_cand >= CWQ_SMALL_MIN_CAND)
-    path = CWQ_SMALL_PIPE && CWQ_SMALL_FUSED && s.max_d >= 0 && s.max_d <= CWQ_FUSED_DMAX &&
-                   s.nb < (1LL << 32)
+    path = CWQ_SMALL_PIPE && CWQ_SMALL_FUSED && !s.keys_only && s.max_d >= 0 &&
+                   s.max_d <= CWQ_FUSED_DMAX && s.nb < (1LL << 32)
                ? EncodePath::SmallPipe
                : EncodePath::SmallThree;
   return {path, path == EncodePath::CsrPruned && few_rows(s.nb, s.n_cand),
@@ -148,6 +152,24 @@ inline int64_t beam_tiles_per_block(BeamPath path, int64_t nb, int64_t n_cand, b
   t = t < most ? t : most;
   if (quarter) t = 4 * t < n_cand ? 4 * t : n_cand;
   return t;
+}
+
+// ---- backfitting (cwq_backfit.hip) ---------------------------
+// Who handles one block in k_backfit_accept: a wave, or a lane when no block
+// exceeds CWQ_FUSED_DMAX dims and there are blocks enough for it.  A lane walks
+// its block's dims one after the other (at most CWQ_FUSED_DMAX terms per step
+// row), a wave takes 64 dims at a time but leaves 63 lanes idle on a row of a
+// few dims.  With a wave per block the chip's 6,144 resident waves hold 6,144
+// blocks; from kBackfitLaneMinBlocks blocks on a lane per block keeps as many
+// lanes busy in one round (16,384 lanes = 256 waves) and the launch shrinks 64
+// times.  Below it the waves are too few to matter and the wave kernel, whose
+// latency per block is lower, runs.  An unknown length (-1) takes the wave kernel.
+enum class BackfitPath { WavePerBlock, LanePerBlock };
+constexpr int64_t kBackfitLaneMinBlocks = 16384;
+inline BackfitPath backfit_plan(int64_t max_d, int64_t nb) {
+  return max_d >= 0 && max_d <= CWQ_FUSED_DMAX && nb >= kBackfitLaneMinBlocks
+             ? BackfitPath::LanePerBlock
+             : BackfitPath::WavePerBlock;
 }
 
 // cwq_greedy_encode_var's bucket rule.  Long rows at few candidates (DESIGN.md

@@ -326,6 +326,48 @@ struct BeamArgs {
 };
 hipError_t launch_beam_encode(const BeamArgs& a, hipStream_t stream);
 
+// ---- backfitting (cwq_backfit.hip) ---------------------------
+// k_prep_dims: the shard constants and normalisers of every dim, out_sample = 0
+// and keys = 0 (launch_encode's first launch).
+hipError_t launch_prep_dims(const float* t_scale, const float* p_loc, const float* p_scale,
+                            int64_t n, int n_steps, float rho, float* loc_s, float* scale_s,
+                            float* lognorm, float* out_sample, unsigned long long* keys,
+                            int64_t nb, hipStream_t stream);
+// The scoring launches of step `step` alone, in the form of a step > 0 (every
+// row is scored against a.out_sample, the carried vector) whatever the step's
+// number: the block's best key lands in a.keys, which the caller zeroed; no
+// index or sample is written.  The path is encode_plan's with keys_only set.
+hipError_t launch_score_step(const EncodeArgs& a, int step, hipStream_t stream);
+// What a backfit call has beyond the encoder's arrays (workspace, after the
+// encoder's layout for the shape; each offset a multiple of 256):
+//   rows  [n_steps][total_dims] f32: the selected row of every step
+//   value [nb] f32: v, the value of the block's decoded sample
+//   count [nb] i32: the replacements accepted so far
+struct BackfitWs {
+  size_t rows, value, count, total;
+};
+inline BackfitWs backfit_ws_layout(size_t base, int64_t nb, int64_t total_dims, int n_steps) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  BackfitWs l;
+  l.rows = up(base);
+  l.value = l.rows + up((size_t)n_steps * total_dims * 4);
+  l.count = l.value + up((size_t)nb * 4);
+  l.total = l.count + up((size_t)nb * 4);
+  return l;
+}
+struct BackfitArgs {
+  EncodeArgs enc;      // the encoder's arguments; out_idx is the table (in and out),
+                       // out_sample the carried vector between the launches and the result
+  int sweeps;
+  float* rows;
+  float* value;
+  int32_t* count;
+  float* out_value;       // or nullptr
+  int32_t* out_accepted;  // or nullptr
+  BackfitPath path;
+};
+hipError_t launch_backfit(const BackfitArgs& a, hipStream_t stream);
+
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);
 hipError_t launch_selftest_screen(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,

@@ -3630,6 +3630,26 @@ static void launch_eval_dc(const EncodeArgs& a, const EncodePlan& plan, int step
   }
 }
 
+// One step's scoring launches on their own (backfitting, cwq_backfit.hip).
+// Nothing in the launchers above is tied to the step's number: the tile queue
+// word is zeroed before every launch that uses it, INTER follows the tiling,
+// and the kernels take the step only for the stream's seed.  k_small_prep1<FIRST>
+// is tied to step 0, but the small pipeline is excluded here (keys_only).
+hipError_t launch_score_step(const EncodeArgs& a_in, int step, hipStream_t stream) {
+  if (a_in.nb <= 0) return hipSuccess;
+  EncodeArgs a = a_in;
+  a.pre_ab = a.sab;
+  EncodeShape shape = shape_of(a);
+  shape.keys_only = true;
+  const EncodePlan plan = encode_plan(shape);
+  const bool screened = plan.path == EncodePath::CsrPruned || plan.path == EncodePath::SmallThree;
+  if (plan.self_finalizing ||
+      (screened && !(a.sab && a.cdim && a.bpre && a.ordu && a.grp && a.gtau && a.slist && a.sdmap)))
+    return hipErrorInvalidValue;
+  launch_eval_dc<false>(a, plan, step, stream);
+  return hipGetLastError();
+}
+
 // The step loop of one block range on one stream: reset the argmax keys, score
 // the candidates, finalize (index + best) -- steps are sequential per block.
 static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool events) {

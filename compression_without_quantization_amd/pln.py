@@ -51,6 +51,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .backfit import code_grouped_greedy_sample_backfit
 from .beam import code_grouped_greedy_sample_beam
 from .binary_io import _pack_bits, read_bin_code, write_bin_code
 from .coded_greedy_sampler import (Normal, code_grouped_greedy_sample,
@@ -526,7 +527,8 @@ class ProbabilisticLadderNetwork(nn.Module):
                           return_second_level_group_sizes=False,
                           return_second_level_indices=False, verbose=False, *,
                           capture=None, first_level_group_bits=False, first_level_min_bits=0,
-                          first_level_bits_dist_counts="", beam_width=1):
+                          first_level_bits_dist_counts="", beam_width=1,
+                          backfit_sweeps=0):
         """pln.py:213-627.  ``session`` is ignored.  Writes the .miracle file to
         comp_file_path and returns ((sample2, sample1), summaries), or what the
         return_* flags ask for.  Group-size count models are .npy paths or
@@ -547,8 +549,22 @@ class ProbabilisticLadderNetwork(nn.Module):
         ``beam_width`` (keyword only, not in the reference): above 1 the greedy
         level 1 keeps that many partial sums per group and step
         (code_grouped_greedy_sample_beam) instead of one; the file format and
-        decode_image_greedy are unchanged.  1 is the plain call."""
+        decode_image_greedy are unchanged.  1 is the plain call.
+        ``backfit_sweeps`` (keyword only, not in the reference): above 0 the
+        greedy level 1's code is refined by that many backfitting sweeps
+        (code_grouped_greedy_sample_backfit), after the beam when
+        ``beam_width > 1``; the file format and decode_image_greedy are
+        unchanged.  0 is the present path, untouched.  The reference's own
+        ``backfitting_steps_level_1/2`` stay accepted and ignored, as the
+        reference ignores them."""
         del session, backfitting_steps_level_1, backfitting_steps_level_2, use_log_prob
+        backfit_sweeps = int(backfit_sweeps)
+        if backfit_sweeps < 0:
+            raise ValueError(f"backfit_sweeps={backfit_sweeps} must be >= 0")
+        if backfit_sweeps > 0 and (use_importance_sampling or first_level_group_bits):
+            raise ValueError("backfit_sweeps > 0 needs use_importance_sampling=False and "
+                             "first_level_group_bits=False: backfitting belongs to the plain "
+                             "greedy level-1 coder")
         beam_width = int(beam_width)
         if beam_width < 1:
             raise ValueError(f"beam_width={beam_width} must be >= 1")
@@ -641,6 +657,14 @@ class ProbabilisticLadderNetwork(nn.Module):
                     min_bits=first_level_min_bits)
             code1 = _chars_of(code1_bytes, total_bits)
             keep("level1", q1p, p1p, (sample1, code1, group_indices1, group_bits1), "greedy_var")
+            if return_first_level_group_sizes:
+                return np.asarray(group_indices1)
+            outlier_extras1 = None
+        elif backfit_sweeps > 0:
+            sample1, code1, group_indices1 = code_grouped_greedy_sample_backfit(
+                q1p, p1p, n_steps, n_bits_per_step, seed, backfit_sweeps, beam=beam_width,
+                max_group_size_bits=greedy_max_group_size_bits, rho=rho)
+            keep("level1", q1p, p1p, (sample1, code1, group_indices1), "greedy_backfit")
             if return_first_level_group_sizes:
                 return np.asarray(group_indices1)
             outlier_extras1 = None

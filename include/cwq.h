@@ -103,8 +103,10 @@ extern "C" {
  *        long blocks below 4,096 candidates with a wave per candidate row
  *        (same results as before);
  *   0.11 beam search over the greedy coder's steps: cwq_beam_encode, its
- *        workspace size and cwq_selftest_beam_encode (no decoder change). */
-#define CWQ_ABI_VERSION ((0 << 16) | 11)
+ *        workspace size and cwq_selftest_beam_encode (no decoder change);
+ *   0.12 backfitting: cwq_greedy_backfit and its workspace size (no decoder
+ *        change). */
+#define CWQ_ABI_VERSION ((0 << 16) | 12)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -710,6 +712,71 @@ int cwq_selftest_beam_encode(const float* t_loc, const float* t_scale, const flo
                              int64_t block_id_base, int32_t* out_idx, float* out_sample,
                              float* out_value, void* workspace, size_t workspace_bytes,
                              const cwq_options* opts, void* stream, int path);
+
+/* ---- Backfitting for the greedy coder (csrc/cwq_backfit.hip) ---------------
+ * Coordinate ascent over the steps of a finished code: it refines any index
+ * table (cwq_greedy_encode's, cwq_beam_encode's, the caller's own) and returns
+ * a table of the same form, so every decoder, the bit string and every file
+ * format stay as they are.
+ *
+ * Setup, per block g: the greedy coder's.  Block seed s_g = seed +
+ * block_id_base + g (int32 wrap), step i's stream seed [1000 s_g + i, 42], the
+ * shard constants and normalisers, N = 2^n_bits_per_step rows per step;
+ * row(i, r) is row r of step i's stream; dec(idx) is the decoder's float32
+ * sum in step order, ((+0 + row(0, idx_0)) + row(1, idx_1)) + ...; val(x) is
+ * the value a key holds for x: sum_j log N(x[j]; t_loc[j], t_scale[j]) in
+ * float32 (the greedy coder's arithmetic and summation order), where a NaN or
+ * a value <= -FLT_MAX reads as -FLT_MAX and -0 as +0.
+ *
+ * State: idx[n_steps], initialised from the caller's table, v = val(dec(idx)).
+ * One sweep visits s = 0 .. n_steps - 1 in order:
+ *   1. base_s = the decoder-order sum with step s skipped;
+ *   2. r* = the row with the largest key (val(base_s + row(s, r)), r) over
+ *      r < N; among equal values the lowest r wins;
+ *   3. r* == idx[s]: nothing changes;
+ *   4. otherwise idx' = idx with idx'[s] = r*, v' = val(dec(idx')), and the
+ *      replacement is accepted (idx = idx', v = v') iff v' > v, compared as
+ *      floats.  base_s + row and the decoder's order differ by rounding unless
+ *      s is the last step, hence the test: the output is exactly what the
+ *      decoder rebuilds, and no block ever ends below the code it came with.
+ * After `sweeps` sweeps: idx, out_sample = dec(idx), out_value = v and
+ * out_accepted[g] = the number of accepts of block g.  sweeps = 0 returns the
+ * table with its decoded sample and value.  A code of one step is returned as
+ * given for any `sweeps` (there is no other step to fit it to), as is an empty
+ * block and every block at n_bits_per_step = 0.
+ *   sweeps        0 <= sweeps <= CWQ_MAX_BACKFIT_SWEEPS
+ *   block_off     device [nb + 1], or NULL for uniform blocks of max_block_dim
+ *                 dims (total_dims = nb * max_block_dim)
+ *   idx_inout     [nb * n_steps] int32, device: the table, refined in place.
+ *                 Every entry must lie in [0, N).  The table is device memory
+ *                 and this call does not wait for the device, so the host
+ *                 cannot check it: the bindings check before they call.  An
+ *                 entry outside the range touches no memory it should not
+ *                 (an index only selects a row of the stream) but the block's
+ *                 results are then unspecified.
+ *   out_sample    [total_dims] f32 (also the vector carried between launches)
+ *   out_value     [nb] f32 or NULL
+ *   out_accepted  [nb] int32 or NULL
+ *   opts          prune_mode selects the scoring kernels as in
+ *                 cwq_greedy_encode (results never depend on it); the eval
+ *                 events bracket the scoring launches.
+ * Each step of a sweep is one scoring launch of the greedy encoder in its
+ * step > 0 form against base_s, so a sweep costs about one cwq_greedy_encode.
+ * A block is handled by one wave (or lane) alone: results do not depend on
+ * timing.  Asynchronous on `stream`, no host synchronisation, no other stream:
+ * capturable into a graph.  Workspace: cwq_greedy_encode_workspace_size(nb,
+ * total_dims, max_block_dim) (each array rounded up to 256) + 4 * n_steps *
+ * total_dims (the selected rows) + 2 * 4 * nb (v and the counts). */
+#define CWQ_MAX_BACKFIT_SWEEPS 16
+size_t cwq_greedy_backfit_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                         int n_steps);
+int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_loc,
+                       const float* p_scale, const int64_t* block_off, int64_t nb,
+                       int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
+                       int n_steps, int sweeps, int32_t seed, float rho, int64_t block_id_base,
+                       int32_t* idx_inout, float* out_sample, float* out_value,
+                       int32_t* out_accepted, void* workspace, size_t workspace_bytes,
+                       const cwq_options* opts, void* stream);
 
 
 /* ---- PLN image codec plumbing (csrc/cwq_pln.hip) ----
