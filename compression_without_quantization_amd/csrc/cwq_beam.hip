@@ -353,14 +353,13 @@ __global__ void __launch_bounds__(256) k_beam_final(
 hipError_t launch_beam_encode(const BeamArgs& a, hipStream_t stream) {
   if (a.nb <= 0) return hipSuccess;
   hipError_t e;
-  const BeamWs l = beam_ws_layout(a.nb, a.total_dims, a.n_steps, a.beam);
-  char* w = (char*)a.workspace;
-  float* loc_s = (float*)(w + l.loc_s);
-  float* scale_s = (float*)(w + l.scale_s);
-  float* lognorm = (float*)(w + l.lognorm);
-  float* beams = (float*)(w + l.beams);
-  unsigned long long* tiles = (unsigned long long*)(w + l.tiles);
-  unsigned long long* sel = (unsigned long long*)(w + l.sel);
+  const BeamWs l = beam_ws(a.nb, a.total_dims, a.n_steps, a.beam);
+  float* loc_s = at<float>(a.workspace, l.loc_s);
+  float* scale_s = at<float>(a.workspace, l.scale_s);
+  float* lognorm = at<float>(a.workspace, l.lognorm);
+  float* beams = at<float>(a.workspace, l.beams);
+  unsigned long long* tiles = at<unsigned long long>(a.workspace, l.tiles);
+  unsigned long long* sel = at<unsigned long long>(a.workspace, l.sel);
   const int64_t D = a.total_dims;
   const int64_t half = (int64_t)a.beam * D;
   const float nst = (float)a.n_steps;

@@ -52,69 +52,16 @@ int hip_fail(hipError_t e, const char* where) {
   return fail(CWQ_ERR_HIP, "%s: %s", where, hipGetErrorString(e));
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using cwq::at;
 
-struct WsLayout {
-  size_t keys, tq, loc_s, scale_s, lognorm, sab, cdim, bpre, ordu, grp, gtau, abp, slist;
-  size_t sdmap, total;
-  bool csr;   // has_screen_arrays: the general pruned kernel's and the small paths' arrays
-  bool recs;  // has_long_block_records: visit-order records of blocks > CWQ_CSR_LDS_DIMS
-};
-
-// csr (has_screen_arrays, cwq_dispatch.h): 24 B/dim + 244 B/block; recs
-// (has_long_block_records): 32 B/dim + 384 B per CWQ_CSR_LDS_DIMS + 1 dims
-// (csr_rec_entries: short blocks take no room, so a grouped call sized for
-// D + 1 possible groups does not pay 384 B for each).
-WsLayout ws_layout(int64_t nb, int64_t total_dims, bool csr, bool recs) {
-  WsLayout l;
-  size_t o = 0;
-  l.keys = o;
-  o = align_up(o + (size_t)nb * 8, 256);
-  l.tq = o;  // k_encode_prune's tile queue counters
-  o = align_up(o + (size_t)cwq::kTileQueueSlots * 4, 256);
-  l.loc_s = o;
-  o = align_up(o + (size_t)total_dims * 4, 256);
-  l.scale_s = o;
-  o = align_up(o + (size_t)total_dims * 4, 256);
-  l.lognorm = o;
-  o = align_up(o + (size_t)total_dims * 4, 256);
-  l.csr = csr;
-  l.recs = csr && recs;
-  l.sab = l.cdim = l.bpre = l.ordu = l.grp = l.gtau = l.abp = l.slist = o;
-  l.sdmap = o;
-  if (csr) {
-    l.slist = o;  // the screened small-candidate path's survivor slots (8 B each)
-    o = align_up(o + (size_t)nb * CWQ_SLIST_PER_BLOCK * 8, 256);
-    l.sab = o;
-    o = align_up(o + (size_t)(total_dims + 8 * nb + 4) * 8, 256);  // + 4 zeros (pad unit)
-    l.cdim = o;
-    o = align_up(o + (size_t)total_dims * 4, 256);
-    l.bpre = o;
-    o = align_up(o + (size_t)(total_dims + 12 * nb) * 4, 256);
-    l.ordu = o;
-    o = align_up(o + (size_t)(total_dims + 12 * nb) * 4, 256);
-    l.grp = o;
-    o = align_up(o + (size_t)nb * 16, 256);
-    l.gtau = o;
-    o = align_up(o + (size_t)nb * 4 * CWQ_CSR_GTAU_STRIDE, 256);
-    l.sdmap = o;  // the small-candidate pipeline's dim -> block map
-    o = align_up(o + (size_t)total_dims * 4, 256);
-    if (l.recs) {
-      l.abp = o;
-      o = align_up(o + (size_t)cwq::csr_rec_entries(total_dims) * 32, 256);
-    }
-  }
-  l.total = o;
-  return l;
-}
-// CSR blocks of at most max_block_dim dims
-WsLayout ws_layout_csr(int64_t nb, int64_t total_dims, int64_t max_block_dim) {
-  return ws_layout(nb, total_dims, cwq::has_screen_arrays(true, 0, nb),
-                   cwq::has_long_block_records(true, max_block_dim, nb));
-}
-WsLayout ws_layout_uniform(int64_t nb, int64_t d) {
-  return ws_layout(nb, nb * d, cwq::has_screen_arrays(false, d, nb),
-                   cwq::has_long_block_records(false, d, nb));
+// The one workspace check.  Every entry point wants a workspace of at least its
+// layout's total; they differ in whether a null pointer is an error when that
+// total is 0 (the block coders, whose empty calls need no byte, take it).
+enum class NullWs { Refused, TakenIfEmpty };
+int check_ws(const void* workspace, size_t workspace_bytes, size_t need, NullWs rule) {
+  if (workspace_bytes < need || (!workspace && (need || rule == NullWs::Refused)))
+    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  return CWQ_OK;
 }
 
 #ifndef CWQ_TARGET_TILES
@@ -344,34 +291,62 @@ int check_common(int n_bits, int n_steps, int64_t nb) {
   return CWQ_OK;
 }
 
-// The encoder's arrays of layout l in the caller's workspace.
-void carve_ws(cwq::EncodeArgs& a, const WsLayout& l, void* workspace) {
-  char* w = (char*)workspace;
-  a.keys = (unsigned long long*)(w + l.keys);
-  a.tq = (uint32_t*)(w + l.tq);
-  a.loc_s = (float*)(w + l.loc_s);
-  a.scale_s = (float*)(w + l.scale_s);
-  a.lognorm = (float*)(w + l.lognorm);
-  a.sab = l.csr ? (float2*)(w + l.sab) : nullptr;
-  a.cdim = l.csr ? (float*)(w + l.cdim) : nullptr;
-  a.bpre = l.csr ? (float*)(w + l.bpre) : nullptr;
-  a.ordu = l.csr ? (uint32_t*)(w + l.ordu) : nullptr;
-  a.grp = l.csr ? (float4*)(w + l.grp) : nullptr;
-  a.gtau = l.csr ? (uint32_t*)(w + l.gtau) : nullptr;
+// The block coder's arguments (cwq_greedy_encode*, cwq_greedy_backfit): the
+// shape, the tiling, the options and the encoder's arrays of layout l in the
+// caller's workspace.  What only some callers have (per-block seeds, the fused
+// destandardisation, rows_wave) keeps EncodeArgs' defaults.
+void fill_encode_args(cwq::EncodeArgs& a, const float* t_loc, const float* t_scale,
+                      const float* p_loc, const float* p_scale, const int64_t* block_off,
+                      int64_t ud, int64_t nb, int64_t total_dims, int64_t max_d, int n_bits,
+                      int n_steps, int32_t seed, float rho, int64_t block_id_base,
+                      int32_t* out_idx, float* out_sample, const cwq_options& o,
+                      const cwq::EncWs& l, void* w) {
+  a.t_loc = t_loc;
+  a.t_scale = t_scale;
+  a.p_loc = p_loc;
+  a.p_scale = p_scale;
+  a.block_off = block_off;
+  a.ud = ud;
+  a.nb = nb;
+  a.total_dims = total_dims;
+  a.max_d = max_d;
+  a.n_cand = (int64_t)1 << n_bits;
+  choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
+  a.n_steps = n_steps;
+  a.prune = o.prune_mode;
+  a.seed = seed;
+  a.rho = rho;
+  a.block_id_base = block_id_base;
+  a.seeds = nullptr;
+  a.out_idx = out_idx;
+  a.out_sample = out_sample;
+  a.ev_start = o.eval_start_event;
+  a.ev_stop = o.eval_stop_event;
+  a.keys = at<unsigned long long>(w, l.keys);
+  a.tq = at<uint32_t>(w, l.tq);
+  a.loc_s = at<float>(w, l.loc_s);
+  a.scale_s = at<float>(w, l.scale_s);
+  a.lognorm = at<float>(w, l.lognorm);
+  a.sab = l.screen ? at<float2>(w, l.sab) : nullptr;
+  a.cdim = l.screen ? at<float>(w, l.cdim) : nullptr;
+  a.bpre = l.screen ? at<float>(w, l.bpre) : nullptr;
+  a.ordu = l.screen ? at<uint32_t>(w, l.ordu) : nullptr;
+  a.grp = l.screen ? at<float4>(w, l.grp) : nullptr;
+  a.gtau = l.screen ? at<uint32_t>(w, l.gtau) : nullptr;
 #ifdef CWQ_NO_RECS
   a.abp = nullptr;
 #else
-  a.abp = l.recs ? (float4*)(w + l.abp) : nullptr;
+  a.abp = l.recs ? at<float4>(w, l.abp) : nullptr;
 #endif
-  a.slist = l.csr ? (uint2*)(w + l.slist) : nullptr;
-  a.sdmap = l.csr ? (uint32_t*)(w + l.sdmap) : nullptr;
+  a.slist = l.screen ? at<uint2>(w, l.slist) : nullptr;
+  a.sdmap = l.screen ? at<uint32_t>(w, l.sdmap) : nullptr;
 }
 
 int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
                 const float* p_scale, const int64_t* block_off, int64_t ud, int64_t nb,
-                int64_t total_dims, int64_t max_block_dim, int n_bits, int n_steps, int32_t seed, float rho,
-                int64_t block_id_base, int32_t* out_idx, float* out_sample, void* workspace,
-                size_t workspace_bytes, const cwq_options* opts, void* stream,
+                int64_t total_dims, int64_t max_block_dim, int n_bits, int n_steps, int32_t seed,
+                float rho, int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                void* workspace, size_t workspace_bytes, const cwq_options* opts, void* stream,
                 const int32_t* block_seeds = nullptr, float* ds_out = nullptr,
                 const float* ds_loc = nullptr, const float* ds_scale = nullptr,
                 bool rows_wave = false) {
@@ -385,34 +360,14 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
     return fail(CWQ_ERR_INVALID, "null input/output pointer");
   // required: cwq_greedy_encode_workspace_size (CSR: always the general pruned
   // kernel's arrays) or cwq_greedy_encode_uniform_workspace_size
-  const WsLayout l =
-      block_off ? ws_layout_csr(nb, total_dims, max_block_dim) : ws_layout_uniform(nb, ud);
-  if (workspace_bytes < l.total || (l.total && !workspace))
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
+  const cwq::EncWs l = block_off ? cwq::enc_ws_csr(nb, total_dims, max_block_dim)
+                                 : cwq::enc_ws_uniform(nb, ud);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::TakenIfEmpty))) return rc;
   cwq::EncodeArgs a;
-  a.t_loc = t_loc;
-  a.t_scale = t_scale;
-  a.p_loc = p_loc;
-  a.p_scale = p_scale;
-  a.block_off = block_off;
-  a.ud = ud;
-  a.nb = nb;
-  a.total_dims = total_dims;
-  a.max_d = block_off ? max_block_dim : ud;
-  a.n_cand = (int64_t)1 << n_bits;
-  choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
-  a.n_steps = n_steps;
-  a.prune = o.prune_mode;
-  a.seed = seed;
-  a.rho = rho;
-  a.block_id_base = block_id_base;
+  fill_encode_args(a, t_loc, t_scale, p_loc, p_scale, block_off, ud, nb, total_dims,
+                   block_off ? max_block_dim : ud, n_bits, n_steps, seed, rho, block_id_base,
+                   out_idx, out_sample, o, l, workspace);
   a.seeds = block_seeds;
-  a.out_idx = out_idx;
-  a.out_sample = out_sample;
-  carve_ws(a, l, workspace);
-  a.ev_start = o.eval_start_event;
-  a.ev_stop = o.eval_stop_event;
   a.ds_out = ds_out;
   a.ds_loc = ds_loc;
   a.ds_scale = ds_scale;
@@ -447,12 +402,12 @@ int cwq_stateless_normal_sample(const float* loc, const float* scale, int64_t d,
 
 size_t cwq_greedy_encode_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim) {
   if (nb < 0 || total_dims < 0 || max_block_dim < 0) return 0;
-  return ws_layout_csr(nb, total_dims, max_block_dim).total;
+  return cwq::enc_ws_csr(nb, total_dims, max_block_dim).total;
 }
 
 size_t cwq_greedy_encode_uniform_workspace_size(int64_t nb, int64_t d) {
   if (nb < 0 || d < 0 || (d > 0 && nb > INT64_MAX / d)) return 0;
-  return ws_layout_uniform(nb, d).total;
+  return cwq::enc_ws_uniform(nb, d).total;
 }
 
 int cwq_greedy_encode(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -555,64 +510,6 @@ int cwq_destandardise(const float* sample, const float* p_loc, const float* p_sc
 // sequence with per-block seeds, and the results are scattered back.
 // ---------------------------------------------------------------------------
 namespace {
-struct VarWs {
-  size_t t_loc, t_scale, p_loc, p_scale, sample, seeds, perm, hist, counts, enc, stage, total;
-  size_t enc_bytes;
-};
-// The encoders write the sorted index rows into the caller's out_idx; they are
-// staged for the scatter in the sorted inputs' region (16 nb d bytes, dead by
-// then) when 4 nb n_steps bytes fit there, i.e. n_steps <= 4 d, else in a tail
-// of that size: cwq_greedy_encode_uniform_var_workspace_size is n_steps = 1.
-VarWs var_layout(int64_t nb, int64_t d, int64_t n_steps) {
-  VarWs l;
-  const size_t row = (size_t)nb * (size_t)d * 4;
-  size_t o = 0;
-  l.t_loc = o;
-  o += row;
-  l.t_scale = o;
-  o += row;
-  l.p_loc = o;
-  o += row;
-  l.p_scale = o;
-  o = align_up(o + row, 256);
-  l.sample = o;
-  o = align_up(o + row, 256);
-  l.seeds = o;
-  o = align_up(o + (size_t)nb * 4, 256);
-  l.perm = o;
-  o = align_up(o + (size_t)nb * 4, 256);
-  l.hist = o;
-  o = align_up(o + cwq::vb_sort_scratch_bytes(nb), 256);
-  l.counts = o;
-  o = align_up(o + 32 * 4, 256);
-  l.enc = o;
-  l.enc_bytes = ws_layout_uniform(nb, d).total;
-  o = align_up(o + l.enc_bytes, 256);
-  l.stage = 0;
-  if (n_steps > 4 * d) {
-    l.stage = o;
-    o = align_up(o + (size_t)nb * (size_t)n_steps * 4, 256);
-  }
-  l.total = o;
-  return l;
-}
-
-struct PackWs {
-  size_t off, partial, flag, total;
-};
-PackWs pack_layout(int64_t nb) {
-  PackWs l;
-  size_t o = 0;
-  l.off = o;
-  o = align_up(o + (size_t)(nb + 1) * 8, 256);
-  l.partial = o;
-  o = align_up(o + cwq::vb_offsets_scratch_bytes(nb), 256);
-  l.flag = o;
-  o = align_up(o + 4, 256);
-  l.total = o;
-  return l;
-}
-
 // nb of the variable-budget entries: perm and the bin counts are 32-bit
 int check_var_nb(int64_t nb) {
   if (nb < 0 || nb > INT32_MAX)
@@ -641,7 +538,7 @@ int cwq_block_bits(const float* q_loc, const float* q_scale, const float* p_loc,
 
 size_t cwq_greedy_encode_uniform_var_workspace_size(int64_t nb, int64_t d) {
   if (nb < 0 || nb > INT32_MAX || d < 0 || (d > 0 && nb > INT64_MAX / d / 64)) return 0;
-  return var_layout(nb, d, 1).total;
+  return cwq::var_ws(nb, d, 1).total;
 }
 
 int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -661,21 +558,19 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
   if (!n_bits || !out_idx) return fail(CWQ_ERR_INVALID, "n_bits / out_idx is null");
   if (d > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
     return fail(CWQ_ERR_INVALID, "null input/output pointer");
-  const VarWs l = var_layout(nb, d, n_steps);
-  if (workspace_bytes < l.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
+  const cwq::VarWs l = cwq::var_ws(nb, d, n_steps);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)workspace;
-  float* tl_s = (float*)(w + l.t_loc);
-  float* ts_s = (float*)(w + l.t_scale);
-  float* pl_s = (float*)(w + l.p_loc);
-  float* ps_s = (float*)(w + l.p_scale);
-  float* sample_s = (float*)(w + l.sample);
-  int32_t* seeds_s = (int32_t*)(w + l.seeds);
-  int32_t* perm = (int32_t*)(w + l.perm);
-  uint32_t* counts_dev = (uint32_t*)(w + l.counts);
-  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, (uint32_t*)(w + l.hist), counts_dev, st);
+  void* w = workspace;
+  float* tl_s = at<float>(w, l.t_loc);
+  float* ts_s = at<float>(w, l.t_scale);
+  float* pl_s = at<float>(w, l.p_loc);
+  float* ps_s = at<float>(w, l.p_scale);
+  float* sample_s = at<float>(w, l.sample);
+  int32_t* seeds_s = at<int32_t>(w, l.seeds);
+  int32_t* perm = at<int32_t>(w, l.perm);
+  uint32_t* counts_dev = at<uint32_t>(w, l.counts);
+  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, at<uint32_t>(w, l.hist), counts_dev, st);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (sort)");
   // the one synchronisation: the bucket sizes decide the launches
   uint32_t counts[32];
@@ -705,12 +600,13 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
     end = r0;
     rc = encode_impl(tl_s + r0 * d, ts_s + r0 * d, pl_s + r0 * d, ps_s + r0 * d, nullptr, d, c,
                      c * d, d, b, n_steps, seed, rho, block_id_base, out_idx + r0 * n_steps,
-                     sample_s + r0 * d, w + l.enc, l.enc_bytes, &ob, stream, seeds_s + r0);
+                     sample_s + r0 * d, at<char>(w, l.enc), l.enc.bytes, &ob, stream,
+                     seeds_s + r0);
     if (rc) return rc;
   }
   if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
     return hip_fail(e, "cwq_greedy_encode_uniform_var (event)");
-  int32_t* stage = (int32_t*)(w + l.stage);
+  int32_t* stage = at<int32_t>(w, l.stage);
   e = hipMemcpyAsync(stage, out_idx, (size_t)nb * n_steps * 4, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess)
     e = cwq::launch_vb_scatter(sample_s, stage, perm, nb, d, n_steps, out_sample, out_idx, st);
@@ -728,41 +624,6 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
 // k_prep_dims covers dims [0, total_dims) and clears the sample there.)
 // ---------------------------------------------------------------------------
 namespace {
-struct VarCsrWs {
-  size_t t_loc, t_scale, p_loc, p_scale, sample, seeds, perm, hist, counts, wgfacts, facts, soff,
-      roff, src, partial, stage, enc, total;
-  size_t enc_bytes;
-};
-VarCsrWs var_csr_layout(int64_t nb, int64_t total_dims, int64_t max_block_dim, int64_t n_steps) {
-  VarCsrWs l;
-  const size_t row = (size_t)total_dims * 4;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  l.t_loc = take(row);
-  l.t_scale = take(row);
-  l.p_loc = take(row);
-  l.p_scale = take(row);
-  l.sample = take(row);
-  l.seeds = take((size_t)nb * 4);
-  l.perm = take((size_t)nb * 4);
-  l.hist = take(cwq::vb_sort_scratch_bytes(nb));
-  l.counts = take(32 * 4);
-  l.wgfacts = take(cwq::vbc_facts_scratch_bytes(nb));
-  l.facts = take(sizeof(cwq::VbcFacts));
-  l.soff = take((size_t)(nb + 1) * 8);
-  l.roff = take((size_t)(nb + 33) * 8);
-  l.src = take((size_t)nb * 8);
-  l.partial = take(cwq::vb_offsets_scratch_bytes(nb));
-  l.stage = take((size_t)nb * (size_t)n_steps * 4);
-  l.enc_bytes = ws_layout_csr(nb, total_dims, max_block_dim).total;
-  l.enc = take(l.enc_bytes);
-  l.total = o;
-  return l;
-}
 bool var_csr_sizes_ok(int64_t nb, int64_t total_dims, int64_t max_block_dim, int64_t n_steps) {
   return nb >= 0 && nb <= INT32_MAX && total_dims >= 0 && total_dims <= INT64_MAX / 1024 &&
          max_block_dim >= 0 && n_steps >= 1 && (nb == 0 || n_steps <= INT64_MAX / 1024 / nb);
@@ -792,7 +653,7 @@ int cwq_block_bits_csr(const float* q_loc, const float* q_scale, const float* p_
 size_t cwq_greedy_encode_var_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,
                                             int n_steps) {
   if (!var_csr_sizes_ok(nb, total_dims, max_block_dim, n_steps)) return 0;
-  return var_csr_layout(nb, total_dims, max_block_dim, n_steps).total;
+  return cwq::var_csr_ws(nb, total_dims, max_block_dim, n_steps).total;
 }
 
 int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -813,32 +674,30 @@ int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float*
     return fail(CWQ_ERR_INVALID, "block_off / n_bits / out_idx is null");
   if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
     return fail(CWQ_ERR_INVALID, "null input/output pointer");
-  const VarCsrWs l = var_csr_layout(nb, total_dims, max_block_dim, n_steps);
-  if (workspace_bytes < l.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
+  const cwq::VarCsrWs l = cwq::var_csr_ws(nb, total_dims, max_block_dim, n_steps);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)workspace;
-  float* tl_s = (float*)(w + l.t_loc);
-  float* ts_s = (float*)(w + l.t_scale);
-  float* pl_s = (float*)(w + l.p_loc);
-  float* ps_s = (float*)(w + l.p_scale);
-  float* sample_s = (float*)(w + l.sample);
-  int32_t* seeds_s = (int32_t*)(w + l.seeds);
-  int32_t* perm = (int32_t*)(w + l.perm);
-  uint32_t* counts_dev = (uint32_t*)(w + l.counts);
-  cwq::VbcFacts* facts_dev = (cwq::VbcFacts*)(w + l.facts);
-  int64_t* soff = (int64_t*)(w + l.soff);
-  int64_t* roff = (int64_t*)(w + l.roff);
-  int64_t* src = (int64_t*)(w + l.src);
-  int32_t* stage = (int32_t*)(w + l.stage);
+  void* w = workspace;
+  float* tl_s = at<float>(w, l.t_loc);
+  float* ts_s = at<float>(w, l.t_scale);
+  float* pl_s = at<float>(w, l.p_loc);
+  float* ps_s = at<float>(w, l.p_scale);
+  float* sample_s = at<float>(w, l.sample);
+  int32_t* seeds_s = at<int32_t>(w, l.seeds);
+  int32_t* perm = at<int32_t>(w, l.perm);
+  uint32_t* counts_dev = at<uint32_t>(w, l.counts);
+  cwq::VbcFacts* facts_dev = at<cwq::VbcFacts>(w, l.facts);
+  int64_t* soff = at<int64_t>(w, l.soff);
+  int64_t* roff = at<int64_t>(w, l.roff);
+  int64_t* src = at<int64_t>(w, l.src);
+  int32_t* stage = at<int32_t>(w, l.stage);
   // sort, the buckets' facts, the sorted layout and the sorted copies (all in
   // the workspace) are enqueued before the host waits for the facts
-  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, (uint32_t*)(w + l.hist), counts_dev, st);
+  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, at<uint32_t>(w, l.hist), counts_dev, st);
   if (e == hipSuccess)
     e = cwq::launch_vbc_layout(n_bits, block_off, perm, nb, counts_dev,
-                               (unsigned long long*)(w + l.wgfacts), facts_dev, seed,
-                               block_id_base, soff, roff, src, seeds_s, (int64_t*)(w + l.partial),
+                               at<unsigned long long>(w, l.wgfacts), facts_dev, seed,
+                               block_id_base, soff, roff, src, seeds_s, at<int64_t>(w, l.partial),
                                st);
   if (e == hipSuccess)
     e = cwq::launch_vbc_gather(t_loc, t_scale, p_loc, p_scale, soff, src, nb, total_dims, tl_s,
@@ -882,8 +741,8 @@ int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float*
     // the bucket's own longest block: short blocks stay off the long-block path
     rc = encode_impl(tl_s + d0, ts_s + d0, pl_s + d0, ps_s + d0, roff + r0 + b, 0, c, f.dims[b],
                      f.maxd[b], b, n_steps, seed, rho, block_id_base, stage + r0 * n_steps,
-                     sample_s + d0, w + l.enc, l.enc_bytes, &ob, stream, seeds_s + r0, nullptr,
-                     nullptr, nullptr, rows_wave);
+                     sample_s + d0, at<char>(w, l.enc), l.enc.bytes, &ob, stream, seeds_s + r0,
+                     nullptr, nullptr, nullptr, rows_wave);
     if (rc) return rc;
   }
   if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
@@ -896,7 +755,7 @@ int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float*
 
 size_t cwq_pack_indices_var_workspace_size(int64_t nb) {
   if (nb < 0 || nb > INT32_MAX) return 0;
-  return pack_layout(nb).total;
+  return cwq::pack_ws(nb).total;
 }
 
 int cwq_pack_indices_var(const int32_t* idx, const int32_t* n_bits, int64_t nb, int n_steps,
@@ -911,14 +770,11 @@ int cwq_pack_indices_var(const int32_t* idx, const int32_t* n_bits, int64_t nb, 
     return fail(CWQ_ERR_INVALID, "null pointer");
   hipStream_t st = (hipStream_t)stream;
   hipError_t e;
-  const PackWs l = pack_layout(nb);
-  if (workspace_bytes < l.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
-  char* w = (char*)workspace;
-  int64_t* off = (int64_t*)(w + l.off);
-  e = cwq::launch_vb_offsets(n_bits, nb, n_steps, off, (int64_t*)(w + l.partial),
-                             (uint32_t*)(w + l.flag), total_bits_dev, st);
+  const cwq::PackWs l = cwq::pack_ws(nb);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
+  int64_t* off = at<int64_t>(workspace, l.off);
+  e = cwq::launch_vb_offsets(n_bits, nb, n_steps, off, at<int64_t>(workspace, l.partial),
+                             at<uint32_t>(workspace, l.flag), total_bits_dev, st);
   if (e == hipSuccess) e = cwq::launch_vb_pack(idx, n_bits, off, nb, n_steps, out_bytes, out_cap, st);
   if (e != hipSuccess) return hip_fail(e, "cwq_pack_indices_var");
   return ok();
@@ -933,14 +789,12 @@ int cwq_unpack_indices_var(const uint8_t* bytes, int64_t n_bytes, const int32_t*
   if (n_bytes < 0) return fail(CWQ_ERR_INVALID, "n_bytes must be >= 0");
   if (nb == 0) return ok();
   if (!idx_out || !n_bits || (n_bytes > 0 && !bytes)) return fail(CWQ_ERR_INVALID, "null pointer");
-  const PackWs l = pack_layout(nb);
-  if (workspace_bytes < l.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
-  char* w = (char*)workspace;
-  int64_t* off = (int64_t*)(w + l.off);
-  hipError_t e = cwq::launch_vb_offsets(n_bits, nb, n_steps, off, (int64_t*)(w + l.partial),
-                                        (uint32_t*)(w + l.flag), nullptr, (hipStream_t)stream);
+  const cwq::PackWs l = cwq::pack_ws(nb);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
+  int64_t* off = at<int64_t>(workspace, l.off);
+  hipError_t e =
+      cwq::launch_vb_offsets(n_bits, nb, n_steps, off, at<int64_t>(workspace, l.partial),
+                             at<uint32_t>(workspace, l.flag), nullptr, (hipStream_t)stream);
   if (e == hipSuccess)
     e = cwq::launch_vb_unpack(bytes, n_bytes, n_bits, off, nb, n_steps, idx_out,
                               (hipStream_t)stream);
@@ -955,36 +809,6 @@ int cwq_unpack_indices_var(const uint8_t* bytes, int64_t n_bytes, const int32_t*
 // per call instead of one per Python step.
 // ---------------------------------------------------------------------------
 namespace {
-struct GroupedWs {
-  size_t t_loc, t_scale, kl, zeros, ones, sample, out, offs, idx, part, pinfo, enc, total;
-};
-// D dims in at most max_groups groups (a partition of D dims has at most D + 1:
-// the reference's forced boundary at D - 1 can leave an empty first group)
-GroupedWs grouped_ws(int64_t D, int n_steps, int64_t max_groups) {
-  GroupedWs l;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  const size_t fd = (size_t)(D > 0 ? D : 0) * 4;
-  l.t_loc = take(fd);
-  l.t_scale = take(fd);
-  l.kl = take(fd);
-  l.zeros = take(fd);
-  l.ones = take(fd);
-  l.sample = take(fd);
-  l.out = take(fd);
-  const int64_t G = max_groups > 1 ? max_groups : 1;
-  l.offs = take((size_t)(G + 1) * 8);
-  l.idx = take((size_t)G * (size_t)(n_steps > 0 ? n_steps : 1) * 4);
-  l.part = take(cwq::partition_workspace_size(D > 0 ? D : 0));  // device partition scratch
-  l.pinfo = take(16 * sizeof(unsigned long long));  // partition info[8] + item info[2]
-  l.enc = take(ws_layout_csr(G, D, D).total);
-  l.total = o;
-  return l;
-}
 // Events of one call, created on the stream's device and destroyed with it.
 // Events of one call on the stream's device, from a per-thread pool (creating
 // and destroying a few dozen events per call cost ~0.3 ms on the batch
@@ -1149,7 +973,7 @@ int64_t write_bitcode(const int32_t* idx, int64_t n, int n_bits, char* o) {
 
 size_t cwq_code_grouped_greedy_workspace_size(int64_t D, int n_steps) {
   if (D < 0 || n_steps < 0) return 0;
-  return grouped_ws(D, n_steps, D + 1).total;
+  return cwq::grouped_ws(D, n_steps, D + 1).total;
 }
 
 namespace {
@@ -1173,10 +997,8 @@ int64_t grouped_begin(const float* q_loc, const float* q_scale, const float* p_l
     return fail(CWQ_ERR_INVALID, "%s: null pointer", who);
   if (!starts_host || starts_cap < D + 2)
     return fail(CWQ_ERR_CAPACITY, "%s: starts_cap must be >= D + 2", who);
-  const GroupedWs l = grouped_ws(D, n_steps, D + 1);
-  if (workspace_bytes < l.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
+  const cwq::GroupedWs l = cwq::grouped_ws(D, n_steps, D + 1);
+  if (int wrc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused)) return wrc;
   hipStream_t s = (hipStream_t)stream;
 #ifdef CWQ_PHASE_TIMES  // tuning builds: per-phase host wall times to stderr
   struct timespec ts0, ts1;
@@ -1190,16 +1012,16 @@ int64_t grouped_begin(const float* q_loc, const float* q_scale, const float* p_l
 #else
   auto lap = [](const char*) {};
 #endif
-  char* w = (char*)workspace;
-  float* t_loc = (float*)(w + l.t_loc);
-  float* t_scale = (float*)(w + l.t_scale);
-  float* kl = (float*)(w + l.kl);
-  float* zeros = (float*)(w + l.zeros);
-  float* ones = (float*)(w + l.ones);
-  float* sample = (float*)(w + l.sample);
-  float* out = (float*)(w + l.out);
-  int64_t* offs = (int64_t*)(w + l.offs);
-  int32_t* idx = (int32_t*)(w + l.idx);
+  void* w = workspace;
+  float* t_loc = at<float>(w, l.t_loc);
+  float* t_scale = at<float>(w, l.t_scale);
+  float* kl = at<float>(w, l.kl);
+  float* zeros = at<float>(w, l.zeros);
+  float* ones = at<float>(w, l.ones);
+  float* sample = at<float>(w, l.sample);
+  float* out = at<float>(w, l.out);
+  int64_t* offs = at<int64_t>(w, l.offs);
+  int32_t* idx = at<int32_t>(w, l.idx);
   hipError_t e = hipSuccess;
   int rc;
   // :207-252 the partition: on the device when it applies (cwq_partition.hip,
@@ -1214,13 +1036,13 @@ int64_t grouped_begin(const float* q_loc, const float* q_scale, const float* p_l
     unsigned long long* g_part_info = part_info_host();
     const bool try_dev = device_partition_enabled() && D >= dev_partition_min_dims() &&
                          cwq::partition_applies(D, size_threshold) && g_part_info != nullptr;
-    unsigned long long* info_d = (unsigned long long*)(w + l.pinfo);
+    unsigned long long* info_d = at<unsigned long long>(w, l.pinfo);
     if ((e = cwq::launch_grouped_prep(q_loc, q_scale, p_loc, p_scale, D, t_loc, t_scale, kl, zeros,
                                       ones, info_d, try_dev ? 16 : 0, s)) != hipSuccess)
       return hip_fail(e, "standardise / KL");
     if (try_dev) {
       if ((e = cwq::launch_partition(kl, D, nullptr, 1, size_threshold, group_thr(n_nats, false),
-                                     offs, (int64_t*)(info_d + 8), w + l.part, info_d, s,
+                                     offs, (int64_t*)(info_d + 8), at<char>(w, l.part), info_d, s,
                                      true)) != hipSuccess ||
           (e = hipMemcpyAsync(g_part_info, info_d, 16 * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, s)) != hipSuccess)
@@ -1316,7 +1138,7 @@ int64_t grouped_begin(const float* q_loc, const float* q_scale, const float* p_l
   oe.eval_ms_out = nullptr;
   // (and :292 destandardise into out, folded into the encoder's last launch)
   if ((rc = encode_impl(t_loc, t_scale, zeros, ones, offs, 0, G, D, maxd, n_bits_per_step,
-                        n_steps, seed, rho, 0, idx, sample, w + l.enc, workspace_bytes - l.enc,
+                        n_steps, seed, rho, 0, idx, sample, at<char>(w, l.enc), l.enc.bytes,
                         &oe, stream, nullptr, out, p_loc, p_scale)) < 0)
     return rc;
   if ((e = hipMemcpyAsync(idx_host, idx, (size_t)(G * n_steps) * 4, hipMemcpyDeviceToHost, s)) !=
@@ -1462,52 +1284,6 @@ int64_t cwq_code_grouped_greedy_end(const int32_t* idx_host, int64_t G, int n_st
 // each.
 // ---------------------------------------------------------------------------
 namespace {
-// Device workspace of the batch: the grouped layout for D dims, with the
-// per-chunk regions of the group-indexed arrays (chunk c of a call owns
-// [a_c + i0_c, ...) of them, a_c its first dim and i0_c its first item, so
-// chunks never share a slot however their group counts come out): offsets
-// D + 2 n + 1 entries, indices / seeds D + n.
-struct BatchWs {
-  GroupedWs g;
-  size_t seeds, ioff, dstarts, iinfo, itab, pstarts, total;
-};
-BatchWs batch_ws(int64_t D, int64_t n_items, int n_steps) {
-  BatchWs l;
-  const int64_t n = n_items > 0 ? n_items : 0;
-  l.g = grouped_ws(D, n_steps, D + 2 * n + 1);
-  l.seeds = l.g.total;
-  // the device partition: item offsets, the items' start lists (the host
-  // layout: item i at item_off[i] + 2 i), per-item counts, the layout table
-  l.ioff = align_up(l.seeds + (size_t)(D + n + 1) * 4, 256);
-  l.dstarts = align_up(l.ioff + (size_t)(n + 1) * 8, 256);
-  l.iinfo = align_up(l.dstarts + (size_t)(D + 2 * n + 1) * 8, 256);
-  l.itab = align_up(l.iinfo + (size_t)(4 * n + 4) * 8, 256);
-  // the start lists packed back to back (at most D_i + 2 entries each)
-  l.pstarts = align_up(l.itab + (size_t)(n + 1) * sizeof(cwq::BatchItem), 256);
-  l.total = align_up(l.pstarts + (size_t)(D + 2 * n + 1) * 8, 256);
-  return l;
-}
-// Host staging of the batch (the caller's pinned memory, or thread-local
-// vectors): per-dim KL, then the offsets / seeds / indices regions as above.
-struct BatchHostWs {
-  size_t kl, offs, seeds, idx, total;
-};
-BatchHostWs batch_host_ws(int64_t D, int64_t n_items, int n_steps) {
-  BatchHostWs h;
-  const int64_t n = n_items > 0 ? n_items : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  h.kl = take((size_t)D * 4);
-  h.offs = take((size_t)(D + 2 * n + 1) * 8);
-  h.seeds = take((size_t)(D + n + 1) * 4);
-  h.idx = take((size_t)(D + n + 1) * (size_t)(n_steps > 0 ? n_steps : 1) * 4);
-  h.total = o;
-  return h;
-}
 // Host threads for the per-chunk host phases: CWQ_HOST_THREADS if set, else the
 // CPUs this process may run on, at most 8.  (On the GPU boxes, whose cgroup
 // quota is 16 CPUs, 12 or 16 threads sporadically ran C3 2.5x slower: the
@@ -1720,15 +1496,16 @@ int64_t batch_device_path(int64_t n_items, const int64_t* item_off, int64_t D, i
                           int n_bits_per_step, const int32_t* seeds, float rho,
                           int64_t size_threshold, double n_nats, float* sample_host,
                           char* bits_host, int64_t bits_cap, int64_t* bits_off,
-                          int64_t* starts_host, int64_t* n_starts, char* w, size_t workspace_bytes,
-                          const BatchWs& bl, const cwq_options& o, const std::vector<int64_t>& ci,
+                          int64_t* starts_host, int64_t* n_starts, void* w,
+                          const cwq::BatchWs& bl, const cwq_options& o,
+                          const std::vector<int64_t>& ci,
                           const float* t_loc, const float* t_scale, const float* kl,
                           const float* zeros, const float* ones, float* sample, float* out,
                           int64_t* offs, int32_t* idx, int32_t* bseed, int32_t* idx_h,
                           CallEvents& evs, CallEvents& tev, const float* p_loc,
                           const float* p_scale, hipStream_t s, hipStream_t d2h, hipStream_t h2d,
                           hipEvent_t part_ev, int64_t* pstage) {
-  const GroupedWs& l = bl.g;
+  const cwq::GroupedWs& l = bl.g;
   const int64_t K = (int64_t)ci.size() - 1;
 #ifdef CWQ_PHASE_TIMES  // tuning builds: per-phase host wall times to stderr
   struct timespec ts_start;
@@ -1744,12 +1521,12 @@ int64_t batch_device_path(int64_t n_items, const int64_t* item_off, int64_t D, i
 #else
   auto lap = [](const char*) {};
 #endif
-  int64_t* ioff_d = (int64_t*)(w + bl.ioff);
-  int64_t* dst = (int64_t*)(w + bl.dstarts);
-  int64_t* iinfo_d = (int64_t*)(w + bl.iinfo);
-  cwq::BatchItem* itab_d = (cwq::BatchItem*)(w + bl.itab);
-  int64_t* pst_d = (int64_t*)(w + bl.pstarts);
-  unsigned long long* info_d = (unsigned long long*)(w + l.pinfo);
+  int64_t* ioff_d = at<int64_t>(w, bl.ioff);
+  int64_t* dst = at<int64_t>(w, bl.dstarts);
+  int64_t* iinfo_d = at<int64_t>(w, bl.iinfo);
+  cwq::BatchItem* itab_d = at<cwq::BatchItem>(w, bl.itab);
+  int64_t* pst_d = at<int64_t>(w, bl.pstarts);
+  unsigned long long* info_d = at<unsigned long long>(w, l.pinfo);
   hipEvent_t* done_ev = evs.ev.data() + K;
   // (the host path's per-chunk KL / layout events are free here)
   hipEvent_t layout_ev = evs.ev[0], pst_ev = evs.ev[(size_t)(2 * K)];
@@ -1767,7 +1544,8 @@ int64_t batch_device_path(int64_t n_items, const int64_t* item_off, int64_t D, i
   if ((e = hipMemcpyAsync(ioff_d, item_off, (size_t)(n_items + 1) * 8, hipMemcpyHostToDevice,
                           s)) != hipSuccess ||
       (e = cwq::launch_partition(kl, D, ioff_d, n_items, size_threshold, group_thr(n_nats, false),
-                                 dst, iinfo_d, w + l.part, info_d, s, true)) != hipSuccess ||
+                                 dst, iinfo_d, at<char>(w, l.part), info_d, s, true)) !=
+          hipSuccess ||
       (e = hipMemcpyAsync(hi, info_d, 8 * 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = hipMemcpyAsync(hi + 8, iinfo_d, (size_t)(2 * n_items) * 8, hipMemcpyDeviceToHost, s)) !=
           hipSuccess ||
@@ -1868,7 +1646,7 @@ int64_t batch_device_path(int64_t n_items, const int64_t* item_off, int64_t D, i
       if (rc == CWQ_OK)  // :273-284 the chunk's groups in one launch sequence
         rc = encode_impl(t_loc + a, t_scale + a, zeros + a, ones + a, offs + gb + c, 0, Gc, Dc,
                          cmaxd[(size_t)c], n_bits_per_step, n_steps, 0, rho, 0,
-                         idx + gb * n_steps, sample + a, w + l.enc, workspace_bytes - l.enc, &oc,
+                         idx + gb * n_steps, sample + a, at<char>(w, l.enc), l.enc.bytes, &oc,
                          s, bseed + gb, out + a, p_loc + a, p_scale + a);  // + :292
     } else if (rc == CWQ_OK && Dc > 0 &&
                (e = hipMemsetAsync(out + a, 0, (size_t)Dc * 4, s)) != hipSuccess) {
@@ -1992,13 +1770,13 @@ int64_t batch_device_path(int64_t n_items, const int64_t* item_off, int64_t D, i
 
 size_t cwq_code_grouped_greedy_batch_workspace_size(int64_t D, int64_t n_items, int n_steps) {
   if (D < 0 || n_items < 0 || n_steps < 0) return 0;
-  return batch_ws(D, n_items, n_steps).total;
+  return cwq::batch_ws(D, n_items, n_steps).total;
 }
 
 size_t cwq_code_grouped_greedy_batch_host_workspace_size(int64_t D, int64_t n_items,
                                                          int n_steps) {
   if (D < 0 || n_items < 0 || n_steps < 0) return 0;
-  return batch_host_ws(D, n_items, n_steps).total;
+  return cwq::batch_host_ws(D, n_items, n_steps).total;
 }
 
 int64_t cwq_code_grouped_greedy_batch(
@@ -2027,12 +1805,10 @@ int64_t cwq_code_grouped_greedy_batch(
     return fail(CWQ_ERR_INVALID, "cwq_code_grouped_greedy_batch: null pointer");
   if (!starts_host || starts_cap < D + 2 * n_items)
     return fail(CWQ_ERR_CAPACITY, "starts_cap must be >= D_total + 2 n_items");
-  const BatchWs bl = batch_ws(D, n_items, n_steps);
-  const GroupedWs& l = bl.g;
-  if (workspace_bytes < bl.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                bl.total);
-  const BatchHostWs hl = batch_host_ws(D, n_items, n_steps);
+  const cwq::BatchWs bl = cwq::batch_ws(D, n_items, n_steps);
+  const cwq::GroupedWs& l = bl.g;
+  if (int wrc = check_ws(workspace, workspace_bytes, bl.total, NullWs::Refused)) return wrc;
+  const cwq::BatchHostWs hl = cwq::batch_host_ws(D, n_items, n_steps);
   if (host_workspace && host_workspace_bytes < hl.total)
     return fail(CWQ_ERR_WORKSPACE, "host workspace %zu bytes < required %zu",
                 host_workspace_bytes, hl.total);
@@ -2061,21 +1837,21 @@ int64_t cwq_code_grouped_greedy_batch(
     g_batch_host.resize(hl.total);
     hw = g_batch_host.data();
   }
-  float* kl_h = (float*)(hw + hl.kl);
-  int64_t* offs_h = (int64_t*)(hw + hl.offs);
-  int32_t* seed_h = (int32_t*)(hw + hl.seeds);
-  int32_t* idx_h = (int32_t*)(hw + hl.idx);
-  char* w = (char*)workspace;
-  float* t_loc = (float*)(w + l.t_loc);
-  float* t_scale = (float*)(w + l.t_scale);
-  float* kl = (float*)(w + l.kl);
-  float* zeros = (float*)(w + l.zeros);
-  float* ones = (float*)(w + l.ones);
-  float* sample = (float*)(w + l.sample);
-  float* out = (float*)(w + l.out);
-  int64_t* offs = (int64_t*)(w + l.offs);
-  int32_t* idx = (int32_t*)(w + l.idx);
-  int32_t* bseed = (int32_t*)(w + bl.seeds);
+  float* kl_h = at<float>(hw, hl.kl);
+  int64_t* offs_h = at<int64_t>(hw, hl.offs);
+  int32_t* seed_h = at<int32_t>(hw, hl.seeds);
+  int32_t* idx_h = at<int32_t>(hw, hl.idx);
+  void* w = workspace;
+  float* t_loc = at<float>(w, l.t_loc);
+  float* t_scale = at<float>(w, l.t_scale);
+  float* kl = at<float>(w, l.kl);
+  float* zeros = at<float>(w, l.zeros);
+  float* ones = at<float>(w, l.ones);
+  float* sample = at<float>(w, l.sample);
+  float* out = at<float>(w, l.out);
+  int64_t* offs = at<int64_t>(w, l.offs);
+  int32_t* idx = at<int32_t>(w, l.idx);
+  int32_t* bseed = at<int32_t>(w, bl.seeds);
 
   // chunks of consecutive items (at least one each): the first about a quarter
   // the size of the middle ones, so the device starts after a short first host
@@ -2136,7 +1912,7 @@ int64_t cwq_code_grouped_greedy_batch(
   // (one launch: standardise, KL, the standard prior, the partition's counters)
   const bool try_dev = device_partition_enabled() && cwq::partition_applies(D, size_threshold);
   if ((e = cwq::launch_grouped_prep(q_loc, q_scale, p_loc, p_scale, D, t_loc, t_scale, kl, zeros,
-                                    ones, (unsigned long long*)(w + l.pinfo), try_dev ? 8 : 0,
+                                    ones, at<unsigned long long>(w, l.pinfo), try_dev ? 8 : 0,
                                     s)) != hipSuccess)
     return hip_fail(e, "cwq_code_grouped_greedy_batch: standardise / KL");
   if (try_dev) {
@@ -2147,8 +1923,8 @@ int64_t cwq_code_grouped_greedy_batch(
     lap("to device", 0);
     const int64_t r = batch_device_path(
         n_items, item_off, D, n_steps, n_bits_per_step, seeds, rho, size_threshold, n_nats,
-        sample_host, bits_host, bits_cap, bits_off, starts_host, n_starts, w, workspace_bytes, bl,
-        o, ci, t_loc, t_scale, kl, zeros, ones, sample, out, offs, idx, bseed, idx_h, evs, tev,
+        sample_host, bits_host, bits_cap, bits_off, starts_host, n_starts, w, bl, o, ci, t_loc,
+        t_scale, kl, zeros, ones, sample, out, offs, idx, bseed, idx_h, evs, tev,
         p_loc, p_scale, s, d2h, h2d, kl_ready, offs_h);
     if (r != kBatchFellBack) return r;
   }
@@ -2347,7 +2123,7 @@ int64_t cwq_code_grouped_greedy_batch(
       if (rc == CWQ_OK)
         rc = encode_impl(t_loc + a, t_scale + a, zeros + a, ones + a, offs + gb + c, 0, ch.G, Dc,
                          ch.maxd, n_bits_per_step, n_steps, 0, rho, 0, idx + gb * n_steps,
-                         sample + a, w + l.enc, workspace_bytes - l.enc, &oc, stream, bseed + gb,
+                         sample + a, at<char>(w, l.enc), l.enc.bytes, &oc, stream, bseed + gb,
                          out + a, p_loc + a, p_scale + a);  // + :292 destandardise
     } else if (rc == CWQ_OK && Dc > 0) {  // no groups (empty items only): the sample is zeros
       if ((e = hipMemsetAsync(out + a, 0, (size_t)Dc * 4, s)) != hipSuccess)
@@ -2425,47 +2201,6 @@ int64_t cwq_code_grouped_greedy_batch(
 // caller (host, cheap).
 // ---------------------------------------------------------------------------
 namespace {
-struct GroupedImpWs {
-  size_t t_loc, t_scale, zeros, ones, sample, res, d2h, plan, items, enc, total;
-  size_t a4;  // align_up(4 D, 256): the stride inside the packed regions
-};
-// D dims in I items: at most D + I groups (an item's partition has at most
-// D_i + 1 groups).  What crosses PCIe sits in packed regions, one copy each,
-// laid out identically in the host staging: d2h = [KL | outlier draws | kept
-// flags] (to the host after the preparation launch), res = [sample | indices]
-// (to the host at the end), plan = [counts | offsets | seeds] (to the device;
-// the offsets and seeds start at offsets set by the call's group count, see
-// imp_plan_offsets), items = [item offsets | seeds - 1] (to the device, batches).
-GroupedImpWs grouped_imp_ws(int64_t D, int64_t I) {
-  GroupedImpWs l;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  const size_t n = (size_t)(D > 0 ? D : 0), ni = (size_t)(I > 0 ? I : 0), g = n + ni;
-  l.a4 = align_up(n * 4, 256);
-  l.t_loc = take(n * 4);
-  l.t_scale = take(n * 4);
-  l.zeros = take(n * 4);
-  l.ones = take(n * 4);
-  l.sample = take(n * 4);
-  l.res = take(l.a4 + g * 8);
-  l.d2h = take(2 * l.a4 + n);
-  l.plan = take(align_up(g * 8, 256) + align_up((g + 1) * 8, 256) + g * 4);
-  l.items = take(align_up((ni + 1) * 8, 256) + ni * 4);
-  l.enc = take(cwq::importance_workspace_size((int64_t)g, (int64_t)n));
-  l.total = o;
-  return l;
-}
-// The plan region for G groups: counts at 0, offsets at *po, seeds at *pg;
-// returns the bytes one copy moves (the seeds only with per-item seeds).
-size_t imp_plan_offsets(int64_t G, bool seeds, size_t* po, size_t* pg) {
-  *po = align_up((size_t)G * 8, 256);
-  *pg = *po + align_up((size_t)(G + 1) * 8, 256);
-  return seeds ? *pg + (size_t)G * 4 : *po + (size_t)(G + 1) * 8;
-}
 thread_local PinnedTl tl_imp_pin;             // the grouped importance calls' host staging
 thread_local std::vector<char> tl_imp_pageable;  // ... when page-locked memory is unavailable
 
@@ -2494,9 +2229,8 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
     return fail(CWQ_ERR_INVALID, "%s: null pointer", who);
   if (!starts_host || starts_cap < D + 2 * I)
     return fail(CWQ_ERR_CAPACITY, "%s: starts_cap must be >= D + 2 n_items", who);
-  const GroupedImpWs l = grouped_imp_ws(D, I);
-  if (workspace_bytes < l.total || !workspace)
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, l.total);
+  const cwq::GroupedImpWs l = cwq::grouped_imp_ws(D, I);
+  if (int wrc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused)) return wrc;
   for (int64_t i = 0; i < I; ++i) {
     n_outliers[i] = 0;
     n_starts[i] = 1;
@@ -2518,50 +2252,41 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
 #else
   auto lap = [](const char*) {};
 #endif
-  char* w = (char*)workspace;
-  float* t_loc = (float*)(w + l.t_loc);
-  float* t_scale = (float*)(w + l.t_scale);
-  float* kl2 = (float*)(w + l.d2h);
-  float* tsamp = (float*)(w + l.d2h + l.a4);
-  uint8_t* keep = (uint8_t*)(w + l.d2h + 2 * l.a4);
-  float* zeros = (float*)(w + l.zeros);
-  float* ones = (float*)(w + l.ones);
-  float* sample = (float*)(w + l.sample);
-  float* out = (float*)(w + l.res);
-  int64_t* idx = (int64_t*)(w + l.res + l.a4);
-  int64_t* nsamp = (int64_t*)(w + l.plan);
-  int64_t* items_d = (int64_t*)(w + l.items);
-  int32_t* seed1_d = (int32_t*)(w + l.items + align_up((size_t)(I + 1) * 8, 256));
+  void* w = workspace;
+  float* t_loc = at<float>(w, l.t_loc);
+  float* t_scale = at<float>(w, l.t_scale);
+  float* kl2 = at<float>(w, l.x.kl);
+  float* tsamp = at<float>(w, l.x.tsamp);
+  uint8_t* keep = at<uint8_t>(w, l.x.keep);
+  float* zeros = at<float>(w, l.zeros);
+  float* ones = at<float>(w, l.ones);
+  float* sample = at<float>(w, l.sample);
+  float* out = at<float>(w, l.x.out);
+  int64_t* idx = at<int64_t>(w, l.x.idx);
+  int64_t* nsamp = at<int64_t>(w, l.x.plan);
+  int64_t* items_d = at<int64_t>(w, l.x.item_off);
+  int32_t* seed1_d = at<int32_t>(w, l.x.seed1);
   // the host side's arrays in this thread's page-locked staging (pageable
   // memory is staged by the runtime: I1's 2.9 MB of copies took ~0.5 ms more),
   // waits polled on events (a blocking wait's wake-up cost I2's small calls
   // ~0.1 ms each)
-  const size_t Dz = (size_t)D, Gz = (size_t)(D + I), Iz = (size_t)I;
-  size_t ho = 0;
-  auto htake = [&](size_t b) {
-    const size_t at = ho;
-    ho = align_up(ho + b, 256);
-    return at;
-  };
+  const size_t Dz = (size_t)D, Iz = (size_t)I;
   // the packed regions (same layout as the device's) and the batch's per-item plans
-  const size_t o_d2h = htake(2 * l.a4 + Dz), o_res = htake(l.a4 + Gz * 8),
-               o_plan = htake(align_up(Gz * 8, 256) + align_up((Gz + 1) * 8, 256) + Gz * 4),
-               o_items = htake(align_up((Iz + 1) * 8, 256) + Iz * 4),
-               o_nst = htake(I > 1 ? Gz * 8 : 0);
-  char* hp = (char*)tl_imp_pin.get(ho, ho + ho / 4);
+  const cwq::GroupedImpHostWs hl = cwq::grouped_imp_host_ws(D, I);
+  void* hp = tl_imp_pin.get(hl.total, hl.total + hl.total / 4);
   if (!hp) {  // no page-locked memory: pageable staging (slower copies)
-    tl_imp_pageable.resize(ho);
+    tl_imp_pageable.resize(hl.total);
     hp = tl_imp_pageable.data();
   }
-  float* kl_h = (float*)(hp + o_d2h);
-  float* ts_h = (float*)(hp + o_d2h + l.a4);
-  uint8_t* keep_h = (uint8_t*)(hp + o_d2h + 2 * l.a4);
-  float* out_h = (float*)(hp + o_res);
-  int64_t* idx_h = (int64_t*)(hp + o_res + l.a4);
-  int64_t* ns_h = (int64_t*)(hp + o_plan);
-  int64_t* items_h = (int64_t*)(hp + o_items);
-  int32_t* s1_h = (int32_t*)(hp + o_items + align_up((Iz + 1) * 8, 256));
-  int64_t* nst_h = I > 1 ? (int64_t*)(hp + o_nst) : ns_h;  // item i's plan at item_off[i] + i
+  float* kl_h = at<float>(hp, hl.x.kl);
+  float* ts_h = at<float>(hp, hl.x.tsamp);
+  uint8_t* keep_h = at<uint8_t>(hp, hl.x.keep);
+  float* out_h = at<float>(hp, hl.x.out);
+  int64_t* idx_h = at<int64_t>(hp, hl.x.idx);
+  int64_t* ns_h = at<int64_t>(hp, hl.x.plan);
+  int64_t* items_h = at<int64_t>(hp, hl.x.item_off);
+  int32_t* s1_h = at<int32_t>(hp, hl.x.seed1);
+  int64_t* nst_h = I > 1 ? at<int64_t>(hp, hl.nst) : ns_h;  // item i's plan at item_off[i] + i
   hipError_t e = hipSuccess;
   // every failure after the first copy or launch drains the stream first: the
   // staging buffer may be reused (or reallocated) by this thread's next call
@@ -2584,8 +2309,8 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
   if (I > 1) {
     memcpy(items_h, item_off, (Iz + 1) * 8);
     for (int64_t i = 0; i < I; ++i) s1_h[i] = (int32_t)((uint32_t)seeds[i] - 1u);
-    if ((e = hipMemcpyAsync(items_d, items_h, align_up((Iz + 1) * 8, 256) + Iz * 4,
-                            hipMemcpyHostToDevice, s)) != hipSuccess)
+    if ((e = hipMemcpyAsync(items_d, items_h, l.x.items.bytes, hipMemcpyHostToDevice, s)) !=
+        hipSuccess)
       return drain_fail(e, "items to device");
     items_arg = items_d;
     seed1_arg = seed1_d;
@@ -2595,7 +2320,7 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
                                         (int32_t)((uint32_t)seeds[0] - 1u), t_loc, t_scale, keep,
                                         zeros, ones, kl2, tsamp, s)) != hipSuccess)
     return drain_fail(e, "standardise / KL / outliers");
-  if ((e = hipMemcpyAsync(kl_h, kl2, 2 * l.a4 + Dz, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+  if ((e = hipMemcpyAsync(kl_h, kl2, l.x.d2h.bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = hipEventRecord(hev.ev[0], s)) != hipSuccess)
     return drain_fail(e, "to host");
   lap("prep queued");
@@ -2643,12 +2368,13 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
     return drain_rc(fail((int)item_rc.load(), "%s: item partition / plan failed", who));
   int64_t Gtot = 0;
   for (int64_t i = 0; i < I; ++i) Gtot += n_starts[i] - 1 > 0 ? n_starts[i] - 1 : 0;
-  size_t po = 0, pg = 0;
-  const size_t plan_bytes = imp_plan_offsets(Gtot, I > 1, &po, &pg);
-  int64_t* offs_h = (int64_t*)(hp + o_plan + po);
-  int32_t* gs_h = (int32_t*)(hp + o_plan + pg);
-  int64_t* offs = (int64_t*)(w + l.plan + po);
-  int32_t* gseed = (int32_t*)(w + l.plan + pg);
+  // the plan's offsets and seeds start where this call's group count puts them
+  const cwq::ImpPlan hplan = cwq::imp_plan(hl.x.plan, Gtot, I > 1);
+  const cwq::ImpPlan dplan = cwq::imp_plan(l.x.plan, Gtot, I > 1);
+  int64_t* offs_h = at<int64_t>(hp, hplan.offs);
+  int32_t* gs_h = at<int32_t>(hp, hplan.seeds);
+  int64_t* offs = at<int64_t>(w, dplan.offs);
+  int32_t* gseed = at<int32_t>(w, dplan.seeds);
   Gtot = 0;
   for (int64_t i = 0; i < I; ++i) {
     const int64_t a = item_off[i], G = n_starts[i] - 1;
@@ -2665,7 +2391,7 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
   int64_t tcand = 0;  // the launch's candidates (selects the encoder's instantiation)
   for (int64_t g = 0; g < Gtot; ++g) tcand += ns_h[g] > 1 ? ns_h[g] : 1;
   if (Gtot > 0) {
-    if ((e = hipMemcpyAsync(nsamp, ns_h, plan_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+    if ((e = hipMemcpyAsync(nsamp, ns_h, dplan.copy_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
       return drain_fail(e, "plan to device");
     // :212-245 every group's importance coder; eval_ms_out: its launches timed
     // with events of this call (the call synchronises anyway)
@@ -2675,8 +2401,8 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
     if ((oi.eval_ms_out && (e = hipEventRecord(tev.ev[0], s)) != hipSuccess) ||
         (e = cwq::launch_importance_encode(t_loc, t_scale, zeros, ones, offs, nsamp, Gtot, D,
                                            seeds[0], 0, I > 1 ? gseed : nullptr,
-                                           oi.prune_mode >= 2 ? 1 : 0, idx, nullptr, w + l.enc,
-                                           s, tcand, cwq::importance_tile_count(ns_h, Gtot, tcand),
+                                           oi.prune_mode >= 2 ? 1 : 0, idx, nullptr,
+                                           at<char>(w, l.enc), s, tcand, cwq::importance_tile_count(ns_h, Gtot, tcand),
                                            p_loc, p_scale, out)) != hipSuccess ||
         (oi.eval_ms_out && (e = hipEventRecord(tev.ev[1], s)) != hipSuccess))
       return drain_fail(e, "importance encode");
@@ -2692,8 +2418,8 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
   }
   // :265 rescale: in the encoder's row launch (every dim is in a group);
   // :267 outliers keep their target draw
-  if ((e = hipMemcpyAsync(out_h, out, Gtot > 0 ? l.a4 + (size_t)Gtot * 8 : Dz * 4,
-                          hipMemcpyDeviceToHost, s)) != hipSuccess ||
+  const size_t res_bytes = Gtot > 0 ? l.x.idx.off - l.x.res.off + (size_t)Gtot * 8 : Dz * 4;
+  if ((e = hipMemcpyAsync(out_h, out, res_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = hipEventRecord(hev.ev[1], s)) != hipSuccess)
     return drain_fail(e, "to host");
   lap("enqueued");
@@ -2714,7 +2440,7 @@ int64_t grouped_importance_impl(int64_t I, const int64_t* item_off, const float*
 
 size_t cwq_code_grouped_importance_workspace_size(int64_t D) {
   if (D < 0) return 0;
-  return grouped_imp_ws(D, 1).total;
+  return cwq::grouped_imp_ws(D, 1).total;
 }
 
 int64_t cwq_code_grouped_importance(const float* q_loc, const float* q_scale,
@@ -2738,7 +2464,7 @@ int64_t cwq_code_grouped_importance(const float* q_loc, const float* q_scale,
 
 size_t cwq_code_grouped_importance_batch_workspace_size(int64_t D_total, int64_t n_items) {
   if (D_total < 0 || n_items < 1) return 0;
-  return grouped_imp_ws(D_total, n_items).total;
+  return cwq::grouped_imp_ws(D_total, n_items).total;
 }
 
 int64_t cwq_code_grouped_importance_batch(
@@ -2764,24 +2490,6 @@ int64_t cwq_code_grouped_importance_batch(
 // item's groups; one copy brings the samples back.
 // ---------------------------------------------------------------------------
 namespace {
-// The plan as it lies in the host staging and in the device workspace: group
-// offsets (G + 1), the slot prefix (G + 1; greedy only), seeds (G), indices.
-struct DecPlan {
-  size_t off, slot, seeds, idx, total;
-};
-DecPlan dec_plan(int64_t G, bool slots, size_t idx_bytes_per_group) {
-  const size_t Gz = (size_t)(G > 0 ? G : 0);
-  DecPlan l;
-  l.off = 0;
-  l.slot = align_up((Gz + 1) * 8, 256);
-  l.seeds = l.slot + (slots ? align_up((Gz + 1) * 8, 256) : 0);
-  l.idx = l.seeds + align_up(Gz * 4, 256);
-  l.total = l.idx + align_up(Gz * idx_bytes_per_group, 256);
-  return l;
-}
-size_t dec_ws_bytes(int64_t D, int64_t G, bool slots, size_t idx_bytes_per_group) {
-  return dec_plan(G, slots, idx_bytes_per_group).total + align_up((size_t)D * 4, 256);
-}
 thread_local std::vector<int64_t> tl_dec_items;  // per item: G, first group, first slot, cover
 
 // The arguments the two batch decoders share.  Returns 1 for an empty batch
@@ -2868,13 +2576,13 @@ int64_t dec_finish(const char* who, const cwq_options& oi, const void* plan_h, v
 size_t cwq_decode_grouped_greedy_batch_workspace_size(int64_t D_total, int64_t G_total,
                                                       int n_steps) {
   if (D_total < 0 || G_total < 0 || n_steps < 1) return 0;
-  return dec_ws_bytes(D_total, G_total, true, (size_t)n_steps * 4);
+  return cwq::dec_ws(D_total, G_total, true, (size_t)n_steps * 4).total;
 }
 
 size_t cwq_decode_grouped_greedy_batch_host_workspace_size(int64_t D_total, int64_t G_total,
                                                            int n_steps) {
   if (D_total < 0 || G_total < 0 || n_steps < 1) return 0;
-  return dec_plan(G_total, true, (size_t)n_steps * 4).total;
+  return cwq::dec_plan(G_total, true, (size_t)n_steps * 4).total;
 }
 
 int64_t cwq_decode_grouped_greedy_batch(
@@ -2898,12 +2606,13 @@ int64_t cwq_decode_grouped_greedy_batch(
   const int64_t D = item_off[n_items];
   const int64_t Gcap = starts_off[n_items] - starts_off[0];
   const size_t idx_b = (size_t)n_steps * 4;
-  if (workspace_bytes < dec_ws_bytes(D, Gcap, true, idx_b) || !workspace)
+  const cwq::DecWs wl = cwq::dec_ws(D, Gcap, true, idx_b);  // wl.plan: also the host staging's
+  if (workspace_bytes < wl.total || !workspace)
     return fail(CWQ_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
-                dec_ws_bytes(D, Gcap, true, idx_b));
-  if (host_workspace_bytes < dec_plan(Gcap, true, idx_b).total || !host_workspace)
+                wl.total);
+  if (host_workspace_bytes < wl.plan.total || !host_workspace)
     return fail(CWQ_ERR_WORKSPACE, "%s: host workspace too small (%zu < %zu)", who,
-                host_workspace_bytes, dec_plan(Gcap, true, idx_b).total);
+                host_workspace_bytes, wl.plan.total);
   // :345-347 group g of an item is decoded while its bit slice is non-empty
   const int64_t bpg = (int64_t)n_bits_per_step * n_steps;
   try {
@@ -2940,13 +2649,13 @@ int64_t cwq_decode_grouped_greedy_batch(
     it[4 * i + 2] = Stot;
     Stot += nq;
   }
-  const DecPlan l = dec_plan(Gtot, true, idx_b);
-  char* hp = (char*)host_workspace;
-  char* w = (char*)workspace;
-  int64_t* off_h = (int64_t*)(hp + l.off);
-  int64_t* slot_h = (int64_t*)(hp + l.slot);
-  int32_t* seed_h = (int32_t*)(hp + l.seeds);
-  int32_t* idx_h = (int32_t*)(hp + l.idx);
+  const cwq::DecPlan l = cwq::dec_plan(Gtot, true, idx_b);  // Gtot <= Gcap: it fits both
+  void* hp = host_workspace;
+  void* w = workspace;
+  int64_t* off_h = at<int64_t>(hp, l.off);
+  int64_t* slot_h = at<int64_t>(hp, l.slot);
+  int32_t* seed_h = at<int32_t>(hp, l.seeds);
+  int32_t* idx_h = at<int32_t>(hp, l.idx);
   std::atomic<int> parse_rc{0};
   dec_for_items(n_items, par, [&](int64_t i) {
     const int64_t G = it[4 * i], gb = it[4 * i + 1], a = item_off[i];
@@ -2969,28 +2678,28 @@ int64_t cwq_decode_grouped_greedy_batch(
   if (parse_rc.load()) return fail(CWQ_ERR_INVALID, "%s: bit parse failed", who);
   off_h[Gtot] = D;
   slot_h[Gtot] = Stot;
-  float* out = sample_dev ? sample_dev : (float*)(w + dec_plan(Gcap, true, idx_b).total);
+  float* out = sample_dev ? sample_dev : at<float>(w, wl.out);
   hipStream_t s = (hipStream_t)stream;
   return dec_finish(
       who, oi, hp, w, l.total,
       [&]() {
-        return cwq::launch_decode_csr_q4((const int32_t*)(w + l.idx), (const int64_t*)(w + l.off),
-                                         (const int64_t*)(w + l.slot), Gtot, Stot,
-                                         (const int32_t*)(w + l.seeds), n_bits_per_step, n_steps,
-                                         rho, p_loc, p_scale, out, s);
+        return cwq::launch_decode_csr_q4(at<int32_t>(w, l.idx), at<int64_t>(w, l.off),
+                                         at<int64_t>(w, l.slot), Gtot, Stot,
+                                         at<int32_t>(w, l.seeds), n_bits_per_step, n_steps, rho,
+                                         p_loc, p_scale, out, s);
       },
       out, sample_host, D, Gtot, s);
 }
 
 size_t cwq_decode_grouped_importance_batch_workspace_size(int64_t D_total, int64_t G_total) {
   if (D_total < 0 || G_total < 0) return 0;
-  return dec_ws_bytes(D_total, G_total, false, 8);
+  return cwq::dec_ws(D_total, G_total, false, 8).total;
 }
 
 size_t cwq_decode_grouped_importance_batch_host_workspace_size(int64_t D_total,
                                                                int64_t G_total) {
   if (D_total < 0 || G_total < 0) return 0;
-  return dec_plan(G_total, false, 8).total;
+  return cwq::dec_plan(G_total, false, 8).total;
 }
 
 int64_t cwq_decode_grouped_importance_batch(
@@ -3012,18 +2721,19 @@ int64_t cwq_decode_grouped_importance_batch(
   }
   const int64_t D = item_off[n_items];
   const int64_t Gtot = starts_off[n_items] - starts_off[0];
-  if (workspace_bytes < dec_ws_bytes(D, Gtot, false, 8) || !workspace)
+  const cwq::DecWs wl = cwq::dec_ws(D, Gtot, false, 8);
+  if (workspace_bytes < wl.total || !workspace)
     return fail(CWQ_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
-                dec_ws_bytes(D, Gtot, false, 8));
-  const DecPlan l = dec_plan(Gtot, false, 8);
+                wl.total);
+  const cwq::DecPlan& l = wl.plan;  // in the host staging as in the device workspace
   if (host_workspace_bytes < l.total || !host_workspace)
     return fail(CWQ_ERR_WORKSPACE, "%s: host workspace too small (%zu < %zu)", who,
                 host_workspace_bytes, l.total);
-  char* hp = (char*)host_workspace;
-  char* w = (char*)workspace;
-  int64_t* off_h = (int64_t*)(hp + l.off);
-  int32_t* seed_h = (int32_t*)(hp + l.seeds);
-  int64_t* idx_h = (int64_t*)(hp + l.idx);
+  void* hp = host_workspace;
+  void* w = workspace;
+  int64_t* off_h = at<int64_t>(hp, l.off);
+  int32_t* seed_h = at<int32_t>(hp, l.seeds);
+  int64_t* idx_h = at<int64_t>(hp, l.idx);
   int64_t gb = 0;
   for (int64_t i = 0; i < n_items; ++i) {  // :294 the item's starts, then D_i
     const int64_t G = starts_off[i + 1] - starts_off[i], a = item_off[i];
@@ -3048,7 +2758,7 @@ int64_t cwq_decode_grouped_importance_batch(
     gb += G;
   }
   off_h[Gtot] = D;
-  float* out = sample_dev ? sample_dev : (float*)(w + l.total);
+  float* out = sample_dev ? sample_dev : at<float>(w, wl.out);
   hipStream_t s = (hipStream_t)stream;
   if (Gtot == 0) {  // no dims either (every item is covered)
     ok();
@@ -3057,9 +2767,9 @@ int64_t cwq_decode_grouped_importance_batch(
   return dec_finish(
       who, oi, hp, w, l.total,
       [&]() {
-        return cwq::launch_importance_decode_grouped(
-            (const int64_t*)(w + l.idx), (const int64_t*)(w + l.off), Gtot,
-            (const int32_t*)(w + l.seeds), p_loc, p_scale, out, s);
+        return cwq::launch_importance_decode_grouped(at<int64_t>(w, l.idx), at<int64_t>(w, l.off),
+                                                     Gtot, at<int32_t>(w, l.seeds), p_loc,
+                                                     p_scale, out, s);
       },
       out, sample_host, D, Gtot, s);
 }
@@ -3089,7 +2799,7 @@ int cwq_importance_plan(const float* kl, const int64_t* starts, int64_t ng, int6
 
 size_t cwq_importance_workspace_size(int64_t nb, int64_t total_dims) {
   if (nb < 0 || total_dims < 0) return 0;
-  return cwq::importance_workspace_size(nb, total_dims);
+  return cwq::imp_ws(nb, total_dims).total;
 }
 
 int cwq_importance_encode(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -3106,9 +2816,9 @@ int cwq_importance_encode(const float* t_loc, const float* t_scale, const float*
     return fail(CWQ_ERR_INVALID, "null pointer");
   if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
     return fail(CWQ_ERR_INVALID, "null pointer");
-  const size_t need = cwq::importance_workspace_size(nb, total_dims);
-  if (workspace_bytes < need || (need && !workspace))
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+  if ((rc = check_ws(workspace, workspace_bytes, cwq::imp_ws(nb, total_dims).total,
+                     NullWs::TakenIfEmpty)))
+    return rc;
   hipError_t e = hipSuccess;
   if (o.eval_start_event)  // the caller's timer around the candidate-scoring launches
     e = hipEventRecord((hipEvent_t)o.eval_start_event, (hipStream_t)stream);
@@ -3156,7 +2866,7 @@ int cwq_selftest_screen_tables(uint32_t m0, int64_t count, float* radius, float*
 }
 
 size_t cwq_debug_partition_workspace_size(int64_t D) {
-  return D < 0 ? 0 : cwq::partition_workspace_size(D) + 16 * sizeof(unsigned long long);
+  return D < 0 ? 0 : cwq::part_debug_ws(D).total;
 }
 
 int64_t cwq_debug_group_starts_device(const float* kl, int64_t D, int64_t size_threshold,
@@ -3166,11 +2876,11 @@ int64_t cwq_debug_group_starts_device(const float* kl, int64_t D, int64_t size_t
   if (!kl || !starts || !workspace || !info_host || D < 0)
     return fail(CWQ_ERR_INVALID, "cwq_debug_group_starts_device: bad arguments");
   if (!cwq::partition_applies(D, size_threshold)) return 0;
-  if (workspace_bytes < cwq_debug_partition_workspace_size(D))
+  const cwq::PartDebugWs l = cwq::part_debug_ws(D);
+  if (workspace_bytes < l.total)
     return fail(CWQ_ERR_WORKSPACE, "cwq_debug_group_starts_device: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  unsigned long long* info_d =
-      (unsigned long long*)((char*)workspace + cwq::partition_workspace_size(D));
+  unsigned long long* info_d = at<unsigned long long>(workspace, l.info);
   hipError_t e = cwq::launch_partition(kl, D, nullptr, 1, size_threshold, group_thr(n_nats, false),
                                        starts, (int64_t*)(info_d + 8), workspace, info_d, s);
   unsigned long long h[16];
@@ -3249,10 +2959,9 @@ int beam_impl(const float* t_loc, const float* t_scale, const float* p_loc, cons
   if (path >= 0 && (path & 1) == 0 && plan != cwq::BeamPath::LanePerRow)
     return fail(CWQ_ERR_INVALID, "the lane-per-row kernel takes blocks of at most %d dims",
                 CWQ_FUSED_DMAX);
-  const cwq::BeamWs l = cwq::beam_ws_layout(nb, total_dims, n_steps, beam);
-  if (workspace_bytes < l.total || (l.total && !workspace))
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes,
-                l.total);
+  if ((rc = check_ws(workspace, workspace_bytes,
+                     cwq::beam_ws(nb, total_dims, n_steps, beam).total, NullWs::TakenIfEmpty)))
+    return rc;
   cwq::BeamArgs a;
   a.t_loc = t_loc;
   a.t_scale = t_scale;
@@ -3289,7 +2998,7 @@ size_t cwq_beam_encode_workspace_size(int64_t nb, int64_t total_dims, int64_t ma
   if (nb < 0 || total_dims < 0 || max_block_dim < 0 || n_steps < 1 || beam < 1 ||
       beam > CWQ_MAX_BEAM)
     return 0;
-  return cwq::beam_ws_layout(nb, total_dims, n_steps, beam).total;
+  return cwq::beam_ws(nb, total_dims, n_steps, beam).total;
 }
 
 int cwq_beam_encode(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -3320,8 +3029,7 @@ size_t cwq_greedy_backfit_workspace_size(int64_t nb, int64_t total_dims, int64_t
                                          int n_steps) {
   if (nb < 0 || total_dims < 0 || max_block_dim < 0 || n_steps < 1) return 0;
   // sized for either layout of the blocks: ragged needs the most
-  const WsLayout l = ws_layout_csr(nb, total_dims, max_block_dim);
-  return cwq::backfit_ws_layout(l.total, nb, total_dims, n_steps).total;
+  return cwq::backfit_ws(true, nb, total_dims, max_block_dim, n_steps).total;
 }
 
 int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -3346,42 +3054,18 @@ int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_
     return fail(CWQ_ERR_INVALID, "null input/output pointer");
   if (nb == 0) return ok();  // no block: nothing to refine, nothing is launched
   const bool csr = block_off != nullptr;
-  const WsLayout l = csr ? ws_layout_csr(nb, total_dims, max_block_dim)
-                         : ws_layout_uniform(nb, max_block_dim);
+  const cwq::BackfitWs l = cwq::backfit_ws(csr, nb, total_dims, max_block_dim, n_steps);
   // the size asked for is the ragged layout's, which no uniform layout exceeds
   const size_t need = cwq_greedy_backfit_workspace_size(nb, total_dims, max_block_dim, n_steps);
-  if (workspace_bytes < need || (need && !workspace))
-    return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-  const cwq::BackfitWs bl = cwq::backfit_ws_layout(l.total, nb, total_dims, n_steps);
+  if ((rc = check_ws(workspace, workspace_bytes, need, NullWs::TakenIfEmpty))) return rc;
   cwq::BackfitArgs b;
-  cwq::EncodeArgs& a = b.enc;
-  a.t_loc = t_loc;
-  a.t_scale = t_scale;
-  a.p_loc = p_loc;
-  a.p_scale = p_scale;
-  a.block_off = block_off;
-  a.ud = csr ? 0 : max_block_dim;
-  a.nb = nb;
-  a.total_dims = total_dims;
-  a.max_d = max_block_dim;
-  a.n_cand = (int64_t)1 << n_bits_per_step;
-  choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
-  a.n_steps = n_steps;
-  a.prune = o.prune_mode;
-  a.seed = seed;
-  a.rho = rho;
-  a.block_id_base = block_id_base;
-  a.seeds = nullptr;
-  a.out_idx = idx_inout;
-  a.out_sample = out_sample;
-  carve_ws(a, l, workspace);
-  a.ev_start = o.eval_start_event;
-  a.ev_stop = o.eval_stop_event;
-  char* w = (char*)workspace;
+  fill_encode_args(b.enc, t_loc, t_scale, p_loc, p_scale, block_off, csr ? 0 : max_block_dim, nb,
+                   total_dims, max_block_dim, n_bits_per_step, n_steps, seed, rho, block_id_base,
+                   idx_inout, out_sample, o, l.enc, workspace);
   b.sweeps = sweeps;
-  b.rows = (float*)(w + bl.rows);
-  b.value = (float*)(w + bl.value);
-  b.count = (int32_t*)(w + bl.count);
+  b.rows = at<float>(workspace, l.rows);
+  b.value = at<float>(workspace, l.value);
+  b.count = at<int32_t>(workspace, l.count);
   b.out_value = out_value;
   b.out_accepted = out_accepted;
   b.path = cwq::backfit_plan(max_block_dim, nb);

@@ -686,12 +686,6 @@ hipError_t launch_imp_outliers(const float* kl, int64_t n, float limit, float* t
   return hipGetLastError();
 }
 
-size_t importance_workspace_size(int64_t nb, int64_t total_dims) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  return up((size_t)nb * 8) + up((size_t)(nb + 1) * 8) + 2 * up((size_t)total_dims * 4) +
-         up((size_t)nb * 4) + 256;
-}
-
 // block_seeds: device [nb] per-group seeds (a batch of items, each numbering
 // its groups from 0 with its own seed), or nullptr: seed + block_id_base + g.
 // total_cands: sum over groups of max(n_samples[g], 1) when the host knows it
@@ -706,15 +700,14 @@ hipError_t launch_importance_encode(const float* t_loc, const float* t_scale, co
                                     int64_t total_tiles, const float* dst_loc,
                                     const float* dst_scale, float* dst_out) {
   if (nb <= 0) return hipSuccess;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  char* w = (char*)workspace;
-  unsigned long long* keys = (unsigned long long*)w;
-  int64_t* tprefix = (int64_t*)(w + up((size_t)nb * 8));
-  float* lnt = (float*)(w + up((size_t)nb * 8) + up((size_t)(nb + 1) * 8));
-  float* lnp = lnt + up((size_t)total_dims * 4) / 4;
-  uint32_t* gtau = (uint32_t*)((char*)lnp + up((size_t)total_dims * 4));
-  unsigned long long* next_tile = (unsigned long long*)((char*)gtau + up((size_t)nb * 4));
-  int64_t* cpt = (int64_t*)(next_tile + 1);
+  const ImpWs l = imp_ws(nb, total_dims);
+  unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
+  int64_t* tprefix = at<int64_t>(workspace, l.tprefix);
+  float* lnt = at<float>(workspace, l.lnt);
+  float* lnp = at<float>(workspace, l.lnp);
+  uint32_t* gtau = at<uint32_t>(workspace, l.gtau);
+  unsigned long long* next_tile = at<unsigned long long>(workspace, l.next_tile);
+  int64_t* cpt = at<int64_t>(workspace, l.cpt);
   const SeedSpec ss{seed, block_id_base, block_seeds};
   if (total_dims > 0)
     hipLaunchKernelGGL(k_imp_prep, dim3(grid_for(total_dims, 256, 65536)), dim3(256), 0, stream,

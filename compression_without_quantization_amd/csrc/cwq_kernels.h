@@ -4,29 +4,19 @@
 #include <stdint.h>
 
 #include "cwq_dispatch.h"
+#include "cwq_workspace.h"
 
 namespace cwq {
-
-#ifndef CWQ_CSR_GTAU_STRIDE
-#define CWQ_CSR_GTAU_STRIDE 1  // words between blocks' shared thresholds (tuning builds)
-#endif
 
 // Records `msg` for cwq_last_error() (thread-local) and returns `code`.
 int set_error(int code, const char* msg);
 
 // First entry of a long block's visit-order records (abp, 32 B per entry) for a
-// block at absolute dim offset off.  Only blocks of more than CWQ_CSR_LDS_DIMS
-// dims have records, and two of them start at least CWQ_CSR_LDS_DIMS + 1 dims
-// apart, so each gets a disjoint region of d + 12 entries here and the array
-// needs csr_rec_entries(total_dims) entries however many short blocks there are.
+// block at absolute dim offset off (csr_rec_entries, cwq_workspace.h, sizes the
+// array: each long block gets a disjoint region of d + 12 entries).
 __host__ __device__ inline int64_t csr_rec_base(int64_t off) {
   return off + 12 * (off / (CWQ_CSR_LDS_DIMS + 1));
 }
-__host__ __device__ inline int64_t csr_rec_entries(int64_t total_dims) {
-  return total_dims + 12 * (total_dims / (CWQ_CSR_LDS_DIMS + 1) + 1);
-}
-
-constexpr int kTileQueueSlots = 64;
 
 struct EncodeArgs {
   const float* t_loc;
@@ -91,8 +81,6 @@ struct EncodeArgs {
   bool rows_wave = false;
 };
 
-#define CWQ_SLIST_PER_BLOCK 8
-
 // Library copy streams (which = 0: device to host, 1: host to device) on the
 // device of the caller's stream, created once per host thread; nullptr if they
 // cannot be made.  Used by the pipelined batch coder to overlap its copies with
@@ -148,7 +136,6 @@ hipError_t launch_grouped_prep(const float* q_loc, const float* q_scale, const f
 // item_off[k] + 2 k, iinfo[2k] their count (G + 1), iinfo[2k + 1] its largest
 // group (iinfo holds 4 n_items entries: the rest is scratch).  partition_fell_back(info copied to the host): not covered, the caller
 // runs the host loop (the results never depend on which path ran).
-size_t partition_workspace_size(int64_t D);
 bool partition_applies(int64_t D, int64_t size_threshold);
 // One item of a batch in the device layout of its chunk's encode: its G groups
 // go to offs[go ...] (block offsets relative to the chunk's first dim: rel +
@@ -159,12 +146,13 @@ struct BatchItem {
   int64_t pk, ns;  // the item's start list: packed offset and length (pstarts)
   int32_t seed, pad;
 };
+static_assert(sizeof(BatchItem) == kBatchItemBytes, "batch_ws sizes the layout table by it");
 // pstarts (may be nullptr): every item's start list packed back to back, for
 // one device-to-host copy
 hipError_t launch_batch_layout(const BatchItem* items, int64_t n_items, const int64_t* dstarts,
                                int64_t* offs, int32_t* seeds, int64_t* pstarts,
                                hipStream_t stream);
-// info_zeroed: info[0..7] (and, single item, iinfo[0..1]) were zeroed on the
+// ws: part_ws(D).total bytes.  info_zeroed: info[0..7] (and, single item, iinfo[0..1]) were zeroed on the
 // stream by the caller (launch_grouped_prep); otherwise a memset does it
 hipError_t launch_partition(const float* kl, int64_t D, const int64_t* item_off, int64_t n_items,
                             int64_t size_threshold, float thr, int64_t* starts, int64_t* iinfo,
@@ -172,7 +160,6 @@ hipError_t launch_partition(const float* kl, int64_t D, const int64_t* item_off,
                             bool info_zeroed = false);
 bool partition_fell_back(const unsigned long long* info_host);
 
-size_t importance_workspace_size(int64_t nb, int64_t total_dims);
 hipError_t launch_imp_outliers(const float* kl, int64_t n, float limit, float* t_loc,
                                float* t_scale, uint8_t* keep, hipStream_t stream);
 hipError_t launch_importance_encode(const float* t_loc, const float* t_scale, const float* p_loc,
@@ -180,7 +167,8 @@ hipError_t launch_importance_encode(const float* t_loc, const float* t_scale, co
                                     const int64_t* n_samples, int64_t nb, int64_t total_dims,
                                     int32_t seed, int64_t block_id_base,
                                     const int32_t* block_seeds, int allow_screen,
-                                    int64_t* out_index, float* out_sample, void* workspace,
+                                    int64_t* out_index, float* out_sample,
+                                    void* workspace,  // imp_ws(nb, total_dims).total bytes
                                     hipStream_t stream, int64_t total_cands = -1,
                                     int64_t total_tiles = -1, const float* dst_loc = nullptr,
                                     const float* dst_scale = nullptr, float* dst_out = nullptr);
@@ -208,8 +196,7 @@ hipError_t launch_block_bits(const float* q_loc, const float* q_scale, const flo
                              float* kl_bits_out, hipStream_t stream);
 // Stable counting sort of nb <= 2^31 - 1 blocks by bit count: perm[rank] = g,
 // counts[0..30] the blocks of each count, counts[31] those outside [0, 30]
-// (ranked last).  wg_hist: vb_sort_scratch_bytes(nb) of scratch.
-size_t vb_sort_scratch_bytes(int64_t nb);
+// (ranked last).  wg_hist: vb_tiles(nb) * kVbBins u32 of scratch.
 hipError_t launch_vb_sort(const int32_t* bits, int64_t nb, int32_t* perm, uint32_t* wg_hist,
                           uint32_t* counts, hipStream_t stream);
 // Rows perm[r] of the four inputs to rows r of the sorted copies, and
@@ -225,8 +212,7 @@ hipError_t launch_vb_scatter(const float* sample_s, const int32_t* idx_s, const 
                              int32_t* out_idx, hipStream_t stream);
 // off[0..nb]: exclusive scan of n_steps * bits[g] in block order (a count
 // outside [0, 30] counts as 0 and sets *flag); total_out (or nullptr) receives
-// off[nb], or -1 when the flag is set.  partial: vb_offsets_scratch_bytes(nb).
-size_t vb_offsets_scratch_bytes(int64_t nb);
+// off[nb], or -1 when the flag is set.  partial: vb_tiles(nb) i64 of scratch.
 hipError_t launch_vb_offsets(const int32_t* bits, int64_t nb, int n_steps, int64_t* off,
                              int64_t* partial, uint32_t* flag, int64_t* total_out,
                              hipStream_t stream);
@@ -257,13 +243,13 @@ struct VbcFacts {
   uint32_t counts[32], start[32];
   int64_t bad_len;
 };
+static_assert(sizeof(VbcFacts) == kVbcFactsBytes, "var_csr_ws sizes the facts by it");
 // The sorted layout, from the sort's perm and counts: the facts; soff[0..nb]
 // the exclusive scan of the block lengths in sorted order; roff [nb + 33]:
 // bucket b's own offsets, relative to its first dim, with a terminator of its
 // own, at roff + start[b] + b (counts[b] + 1 entries); src[r] =
 // block_off[perm[r]]; seeds[r] = block_seed(seed, block_id_base + perm[r]).
-// wg: vbc_facts_scratch_bytes(nb); partial: vb_offsets_scratch_bytes(nb).
-size_t vbc_facts_scratch_bytes(int64_t nb);
+// wg: vb_tiles(nb) * kVbcFactsRow u64; partial: vb_tiles(nb) i64.
 hipError_t launch_vbc_layout(const int32_t* bits, const int64_t* block_off, const int32_t* perm,
                              int64_t nb, const uint32_t* counts, unsigned long long* wg,
                              VbcFacts* facts, int32_t seed, int64_t block_id_base, int64_t* soff,
@@ -282,28 +268,6 @@ hipError_t launch_vbc_scatter(const float* sample_s, const int32_t* idx_s, const
 
 // ---- beam search over steps (cwq_beam.hip) -------------------
 constexpr int kMaxBeam = 16;  // CWQ_MAX_BEAM
-// Workspace of one beam encode (byte offsets, each a multiple of 256):
-//   loc_s, scale_s, lognorm  [total_dims] f32: the step's shard and normaliser
-//   beams   [2][beam][total_dims] f32: the running sums, ping-pong
-//   tiles   [nb][beam_tiles_cap(nb)][beam] u64: every tile's largest keys
-//   sel     [nb][n_steps][beam] u64: the selected keys, sorted; key j of a step
-//           names beam j's parent and row (candidate parent * 2^b + row)
-struct BeamWs {
-  size_t loc_s, scale_s, lognorm, beams, tiles, sel, total;
-};
-inline BeamWs beam_ws_layout(int64_t nb, int64_t total_dims, int n_steps, int beam) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  BeamWs l;
-  const size_t dims = up((size_t)total_dims * 4);
-  l.loc_s = 0;
-  l.scale_s = dims;
-  l.lognorm = 2 * dims;
-  l.beams = 3 * dims;
-  l.tiles = l.beams + up((size_t)2 * beam * total_dims * 4);
-  l.sel = l.tiles + up((size_t)nb * beam_tiles_cap(nb) * beam * 8);
-  l.total = l.sel + up((size_t)nb * n_steps * beam * 8);
-  return l;
-}
 struct BeamArgs {
   const float* t_loc;
   const float* t_scale;
@@ -318,7 +282,7 @@ struct BeamArgs {
   int32_t* out_idx;
   float* out_sample;
   float* out_value;  // or nullptr
-  void* workspace;   // beam_ws_layout(nb, total_dims, n_steps, beam).total bytes
+  void* workspace;   // beam_ws(nb, total_dims, n_steps, beam).total bytes
   void* ev_start;    // hipEvent_t around the scoring launches, or nullptr
   void* ev_stop;
   BeamPath path;
@@ -338,23 +302,8 @@ hipError_t launch_prep_dims(const float* t_scale, const float* p_loc, const floa
 // number: the block's best key lands in a.keys, which the caller zeroed; no
 // index or sample is written.  The path is encode_plan's with keys_only set.
 hipError_t launch_score_step(const EncodeArgs& a, int step, hipStream_t stream);
-// What a backfit call has beyond the encoder's arrays (workspace, after the
-// encoder's layout for the shape; each offset a multiple of 256):
-//   rows  [n_steps][total_dims] f32: the selected row of every step
-//   value [nb] f32: v, the value of the block's decoded sample
-//   count [nb] i32: the replacements accepted so far
-struct BackfitWs {
-  size_t rows, value, count, total;
-};
-inline BackfitWs backfit_ws_layout(size_t base, int64_t nb, int64_t total_dims, int n_steps) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  BackfitWs l;
-  l.rows = up(base);
-  l.value = l.rows + up((size_t)n_steps * total_dims * 4);
-  l.count = l.value + up((size_t)nb * 4);
-  l.total = l.count + up((size_t)nb * 4);
-  return l;
-}
+// rows, value, count: what a backfit call has beyond the encoder's arrays
+// (backfit_ws, cwq_workspace.h)
 struct BackfitArgs {
   EncodeArgs enc;      // the encoder's arguments; out_idx is the table (in and out),
                        // out_sample the carried vector between the launches and the result

@@ -52,12 +52,11 @@ namespace cwq {
 #ifndef CWQ_PART_UNROLL
 #define CWQ_PART_UNROLL 4  // k_part_next's dims per threshold test (C3: 51 -> 44.5 us)
 #endif
-constexpr int kPartW = 1024;        // dims per chunk
+// kPartW (dims per chunk), kPartSuper (chunks per superchunk): cwq_workspace.h
 constexpr int kPartMaxJump = 512;   // longest group the device path takes
 constexpr int kPartRun = 8;         // non-converged chunks a walk may cross
 constexpr int kPartThreads = 256;
 constexpr int kPartLdsItems = 1024;  // batches up to this many items search offsets in LDS
-constexpr int kPartSuper = 256;      // chunks per superchunk (k_part_sup's sums)
 // up to this many chunks k_part_emit sums the earlier counts directly (at most
 // 64 loads per thread; C3's 4,660 chunks: 18): an atomic per chunk into the
 // superchunk sums instead cost C3's k_part_mark 33 us (37 -> 70 us)
@@ -515,13 +514,6 @@ hipError_t launch_batch_layout(const BatchItem* items, int64_t n_items, const in
   return hipGetLastError();
 }
 
-size_t partition_workspace_size(int64_t D) {
-  const int64_t nch = (D + kPartW - 1) / kPartW;
-  const int64_t nsup = (nch + kPartSuper - 1) / kPartSuper;
-  const size_t b = (size_t)(4 * (D + 64) + 2 * (nch + 64) + (nsup + 64)) * 4 + 64 * 8;
-  return (b + 255) & ~(size_t)255;  // callers place 8-byte words right after it
-}
-
 bool partition_fell_back(const unsigned long long* info) {
   return info[4] > (unsigned long long)kPartMaxJump || info[2] != 0ull || info[0] == 0ull;
 }
@@ -540,13 +532,14 @@ hipError_t launch_partition(const float* kl, int64_t D, const int64_t* item_off,
   // start list; the kernels now also return past the last chunk)
   if (D < 1 || D >= (1LL << 30) || n_items < 1) return hipErrorInvalidValue;
   const int64_t nch = (D + kPartW - 1) / kPartW;
-  int32_t* nxt = (int32_t*)ws;
-  int32_t* exg = nxt + (D + 64);
-  int32_t* node = exg + (D + 64);
-  int32_t* gnode = node + (D + 64);
-  int32_t* conv = gnode + (D + 64);
-  int32_t* cnt = conv + (nch + 64);
-  int32_t* sup = cnt + (nch + 64);
+  const PartWs l = part_ws(D);
+  int32_t* nxt = at<int32_t>(ws, l.nxt);
+  int32_t* exg = at<int32_t>(ws, l.exg);
+  int32_t* node = at<int32_t>(ws, l.node);
+  int32_t* gnode = at<int32_t>(ws, l.gnode);
+  int32_t* conv = at<int32_t>(ws, l.conv);
+  int32_t* cnt = at<int32_t>(ws, l.cnt);
+  int32_t* sup = at<int32_t>(ws, l.sup);
   const int64_t nsup = (nch + kPartSuper - 1) / kPartSuper;
   const dim3 gch((unsigned)nch), gsup((unsigned)nsup);
   if ((int64_t)gch.x != nch || (int64_t)gsup.x != nsup || nch < 1 || nsup < 1)

@@ -25,10 +25,7 @@
 namespace cwq {
 namespace {
 
-constexpr int kVbThreads = 256;
-constexpr int kVbPerThread = 8;
-constexpr int kVbTile = kVbThreads * kVbPerThread;  // blocks per workgroup (sort, offsets)
-constexpr int kVbBins = 32;                         // bit counts 0..30, 31: out of range
+// kVbThreads, kVbPerThread, kVbTile, kVbBins: cwq_workspace.h (they size the scratch)
 constexpr int kVbMaxBits = 30;                      // CWQ_MAX_BITS_PER_STEP
 
 __device__ __forceinline__ int vb_bin(int32_t b) {
@@ -488,7 +485,6 @@ __global__ void __launch_bounds__(kVbThreads) k_block_bits_csr(
 // kVbTile) and writes wg[w][0..31] (dims by bucket), wg[w][32..63] (longest),
 // wg[w][64] (blocks of negative length) and wg[w][65] (the tile's dims):
 // integer LDS atomics only.
-constexpr int kVbcFactsRow = 2 * kVbBins + 2;
 
 __global__ void __launch_bounds__(kVbThreads) k_vbc_tile(const int32_t* __restrict__ bits,
                                                          const int64_t* __restrict__ block_off,
@@ -649,7 +645,6 @@ bool aligned16_all(const void* a, const void* b, const void* c, const void* d) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) == 0;
 }
 
-int64_t vb_tiles(int64_t nb) { return (nb + kVbTile - 1) / kVbTile; }
 
 }  // namespace
 
@@ -666,7 +661,6 @@ hipError_t launch_block_bits(const float* q_loc, const float* q_scale, const flo
   return hipGetLastError();
 }
 
-size_t vb_sort_scratch_bytes(int64_t nb) { return (size_t)vb_tiles(nb) * kVbBins * 4; }
 
 hipError_t launch_vb_sort(const int32_t* bits, int64_t nb, int32_t* perm, uint32_t* wg_hist,
                           uint32_t* counts, hipStream_t stream) {
@@ -723,7 +717,6 @@ hipError_t launch_vb_scatter(const float* sample_s, const int32_t* idx_s, const 
   return hipGetLastError();
 }
 
-size_t vb_offsets_scratch_bytes(int64_t nb) { return (size_t)vb_tiles(nb) * 8; }
 
 hipError_t launch_vb_offsets(const int32_t* bits, int64_t nb, int n_steps, int64_t* off,
                              int64_t* partial, uint32_t* flag, int64_t* total_out,
@@ -774,7 +767,6 @@ hipError_t launch_block_bits_csr(const float* q_loc, const float* q_scale, const
   return hipGetLastError();
 }
 
-size_t vbc_facts_scratch_bytes(int64_t nb) { return (size_t)vb_tiles(nb) * kVbcFactsRow * 8; }
 
 hipError_t launch_vbc_layout(const int32_t* bits, const int64_t* block_off, const int32_t* perm,
                              int64_t nb, const uint32_t* counts, unsigned long long* wg,

@@ -350,16 +350,20 @@ def test_adversarial(cwq, mode):
 # ---------------------------------------------------------------------------
 # workspace and output buffers: their contents on entry never matter
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("pattern", [0x00, 0xFF, "random"])
+@pytest.mark.parametrize("pattern", [0x00, 0xFF, "random", "guard"])
 def test_poisoned_workspace_and_outputs(cwq, cwqlib, pattern):
+    """The "guard" case: zeros between guard bands (tests/poison.py), which must stay intact."""
+    guard = pattern == "guard"
+    pattern = 0x00 if guard else pattern
     off = _ragged()[0]
     nb, D = len(off) - 1, int(off[-1])
     table = _Fn(_greedy_table, _ragged, 5, 3, 0.7, SEED, BASE)
     want = _reference(_ragged, table, 5, 3, 2, 0.7, SEED, BASE)  # a case of test_vs_reference
     tab = table()
-    with poisoned(pattern) as f:
+    with poisoned(pattern, guard=guard) as f:
         got = _run(cwq, _ragged(), tab, 5, 3, 2, 0.7)
         torch.cuda.synchronize()
+        assert f.assert_guards_intact("backfit") >= int(guard)
     f.assert_workspace(int(cwqlib.cwq_greedy_backfit_workspace_size(nb, D, 4095, 3)), "backfit")
     assert f.count("device", torch.float32, 4 * D) >= 1   # out_sample was poisoned too
     _same(got, want)
@@ -368,9 +372,10 @@ def test_poisoned_workspace_and_outputs(cwq, cwqlib, pattern):
     table_s = _Fn(_greedy_table, layout, n_bits, n_steps, 1.0, SEED, BASE)
     want_s = _reference(layout, table_s, n_bits, n_steps, 2, 1.0, SEED, BASE, None)
     tab = table_s()
-    with poisoned(pattern):
+    with poisoned(pattern, guard=guard) as f:
         got_s = _run(cwq, layout(), tab, n_bits, n_steps, 2, 1.0)
         torch.cuda.synchronize()
+        assert f.assert_guards_intact("backfit, short blocks") >= int(guard)
     _same(got_s, want_s)
 
 

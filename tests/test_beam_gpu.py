@@ -247,24 +247,29 @@ def test_deterministic_and_tiling_independent(cwq):
 # ---------------------------------------------------------------------------
 # workspace and output buffers: their contents on entry never matter
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("pattern", [0x00, 0xFF, "random"])
+@pytest.mark.parametrize("pattern", [0x00, 0xFF, "random", "guard"])
 def test_poisoned_workspace_and_outputs(cwq, cwqlib, pattern):
+    """The "guard" case: zeros between guard bands (tests/poison.py), which must stay intact."""
+    guard = pattern == "guard"
+    pattern = 0x00 if guard else pattern
     off, tl, ts, pl, ps = _ragged()
     want = _reference(_ragged, 3, 4, 16, 0.7, SEED, BASE)  # a case of test_ragged_vs_reference
     nb, D = len(off) - 1, int(off[-1])
-    with poisoned(pattern) as f:
+    with poisoned(pattern, guard=guard) as f:
         got = cwq.encode_blocks_beam(tl, ts, pl, ps, 3, 4, SEED, 16, rho=0.7, block_off=off,
                                      block_id_base=BASE, return_value=True)
         torch.cuda.synchronize()
+        assert f.assert_guards_intact("beam") >= int(guard)
     f.assert_workspace(int(cwqlib.cwq_beam_encode_workspace_size(nb, D, 4095, 4, 16)), "beam")
     assert f.count("device", torch.int32, 4 * nb * 4) >= 1   # out_idx was poisoned too
     _same(got, want)
     s = _short()
     want_s = _reference(_short, 4, 3, 5, 1.0, SEED, BASE)  # a case of test_both_kernels_same_bits
-    with poisoned(pattern):
+    with poisoned(pattern, guard=guard) as f:
         got_s = cwq.encode_blocks_beam(s[1], s[2], s[3], s[4], 4, 3, SEED, 5, block_off=s[0],
                                        block_id_base=BASE, return_value=True)
         torch.cuda.synchronize()
+        assert f.assert_guards_intact("beam, short blocks") >= int(guard)
     _same(got_s, want_s)
 
 

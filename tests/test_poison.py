@@ -70,6 +70,18 @@ def test_originals_restored_also_on_error():
     assert (torch.empty, torch.empty_like, np.empty) == orig
 
 
+def test_guard_mode_leaves_pageable_host_buffers_alone():
+    """Guard bands go around device and page-locked uint8 buffers only (the GPU
+    suite checks those); everything else is filled as without the mode."""
+    with poisoned(0x5A, guard=True) as f:
+        u = torch.empty(100, dtype=torch.uint8)
+        x = torch.empty(7)
+        a = np.empty(9, np.uint8)
+    assert all((_bytes(b) == 0x5A).all() for b in (u, x, a))
+    assert f.guards == [] and f.assert_guards_intact() == 0 and f.count() == 3
+    assert u.untyped_storage().nbytes() == 100
+
+
 def test_workspace_condition():
     with poisoned(0xFF) as f:
         torch.empty(100, dtype=torch.uint8)

@@ -92,10 +92,11 @@ def _drop_wrapper_caches():
 
 
 def _three(run, what, need=None, check=None):
-    """run() under each pattern; the three results must agree.  ``need``: the
-    entry point's workspace size, which a poisoned device uint8 buffer must
-    reach (entry points without a workspace pass ``check(filled)`` instead).
-    Returns the 0x00 result."""
+    """run() under each pattern; the three results must agree, and a fourth
+    run between guard bands (tests/poison.py) must leave them intact and agree
+    too.  ``need``: the entry point's workspace size, which a poisoned device
+    uint8 buffer must reach (entry points without a workspace pass
+    ``check(filled)`` instead).  Returns the 0x00 result."""
     out = {}
     for p in PATTERNS:
         _drop_wrapper_caches()
@@ -109,6 +110,18 @@ def _three(run, what, need=None, check=None):
             assert check(filled), f"{what} ({p!r}): its buffers were not poisoned: {filled.buffers}"
     for p in PATTERNS[1:]:
         _same(out[p], out[0x00], f"{what}: pattern {p!r} against 0x00")
+    # once more between guard bands: the wrappers allocate exactly the bytes
+    # the size functions name, so this is where a store past them shows
+    _drop_wrapper_caches()
+    with poisoned(0x00, guard=True) as filled:
+        res = run()
+        torch.cuda.synchronize()
+        guarded = filled.assert_guards_intact(f"{what} (guarded)")
+        res = _canon(res)
+    if need is not None:
+        filled.assert_workspace(int(need), f"{what} (guarded)")
+        assert guarded >= 1, f"{what}: no buffer was guarded: {filled.buffers}"
+    _same(res, out[0x00], f"{what}: the guarded run against 0x00")
     return out[0x00]
 
 
@@ -129,6 +142,31 @@ def test_poison_reaches_device_and_pinned_memory():
         else:
             assert (db == p).all() and (hb == p).all()
             assert int(s.item()) == (0 if p == 0 else -1)
+    assert (torch.empty, torch.empty_like, np.empty) == _ORIGINALS
+
+
+def test_guard_bands_report_a_store_past_either_end():
+    """The guard mode itself: 256-aligned buffers of exactly the bytes asked
+    for, intact guards pass, one byte past either end of a device or a
+    page-locked buffer is reported.  (The stores land in the test's own larger
+    allocation.)"""
+    from poison import GUARD_BYTE, GUARD_BYTES
+    for pinned in (False, True):
+        kw = dict(pin_memory=True) if pinned else dict(device="cuda")
+        for at in (-1, 1000, -GUARD_BYTES, 1000 + GUARD_BYTES - 1):
+            with poisoned(0xFF, guard=True) as filled:
+                b = torch.empty(1000, dtype=torch.uint8, **kw)
+                f = torch.empty(10, dtype=torch.float32, **kw)  # not a uint8 buffer: no guards
+                z = torch.empty(0, dtype=torch.uint8, **kw)
+            assert b.numel() == 1000 and b.data_ptr() % 256 == 0 and (b == 0xFF).all()
+            assert f.numel() == 10 and z.numel() == 0
+            assert filled.assert_guards_intact() == 1
+            assert filled.count("pinned" if pinned else "device", torch.uint8, 1000) == 1
+            whole, start, n = filled.guards[0]
+            assert n == 1000 and whole.data_ptr() + start == b.data_ptr()
+            whole[start + at] = GUARD_BYTE ^ 1
+            with pytest.raises(AssertionError, match=f"first at byte {at} of the buffer"):
+                filled.assert_guards_intact()
     assert (torch.empty, torch.empty_like, np.empty) == _ORIGINALS
 
 
