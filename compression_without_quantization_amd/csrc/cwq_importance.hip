@@ -15,16 +15,10 @@
 #include <stdint.h>
 
 #include "cwq_device.h"
+#include "cwq_imp_plan.h"  // every constant and rule that selects a path
 #include "cwq_kernels.h"
 
 namespace cwq {
-
-constexpr int64_t kImpCandPerTile = 16384;
-constexpr int kImpScreenMaxD = 256;   // screening pass: per-dim constants live in LDS
-constexpr int64_t kImpPruneMinD = 5;  // rows of >= 5 dims take the pruned screening loop
-#ifndef CWQ_IMP_SURVIVOR_CAP
-#define CWQ_IMP_SURVIVOR_CAP 1024
-#endif
 
 __global__ void __launch_bounds__(256) k_imp_prep(const float* __restrict__ t_scale,
                                                   const float* __restrict__ p_scale, int64_t n,
@@ -37,39 +31,7 @@ __global__ void __launch_bounds__(256) k_imp_prep(const float* __restrict__ t_sc
   }
 }
 
-// Tile size: the launch's candidates cut into about kImpTargetTiles tiles (a
-// few per CU, so one image's ~600 groups do not leave most of a fixed grid
-// idle), a power of two in [kImpMinCandPerTile, kImpCandPerTile].
-#ifndef CWQ_IMP_TARGET_TILES
-#define CWQ_IMP_TARGET_TILES 2048
-#endif
-#ifndef CWQ_IMP_MIN_CPT
-#define CWQ_IMP_MIN_CPT 1024
-#endif
-constexpr int64_t kImpMinCandPerTile = CWQ_IMP_MIN_CPT;
 constexpr int64_t kImpEvalGrid = 256 * 16;  // persistent k_imp_eval workgroups
-
-// The tile-size rule (k_imp_tiles on the device; the launcher on the host
-// when it knows the launch's candidate count T = sum max(N_g, 1)).
-__host__ __device__ inline int64_t imp_cand_per_tile(int64_t T) {
-  int64_t cpt = kImpMinCandPerTile;
-  while (cpt < kImpCandPerTile && cpt * CWQ_IMP_TARGET_TILES < T) cpt <<= 1;
-  return cpt;
-}
-
-// Groups of at most this many candidates are coded by k_imp_small (one wave
-// per group, every row exact) and get no k_imp_eval tile: most groups of a
-// batch of small latents draw a few dozen candidates (I2: 81% of 13,852
-// groups have N <= 128, 1.6% of the candidates), and a tile's fixed cost (its
-// group search, the screening constants, four barriers, the hand-out
-// counter) exceeded their rows' work.  A/B (tools/variants.sh is0..is1024,
-// one box, two rounds): I2's scoring 0.299 -> 0.207 ms, pln_is 0.36 -> 0.18 ms,
-// I1 unchanged (8.39 / 8.41 ms); 128 and 256 tie, 1024 is slower on I1.
-// 0 disables.
-#ifndef CWQ_IMP_SMALL_N
-#define CWQ_IMP_SMALL_N 128
-#endif
-constexpr int64_t kImpSmallN = CWQ_IMP_SMALL_N;
 
 // Exclusive prefix over the 1024 threads of the workgroup (inclusive wave scans
 // by shuffles, then the 16 wave totals).  Returns the prefix and
@@ -114,12 +76,10 @@ __global__ void __launch_bounds__(1024) k_imp_tiles(const int64_t* __restrict__ 
   // 13,852 groups: ~27 us either way -- neither the strided accesses nor the
   // 64-bit divisions of the previous per-thread-run form were the cost)
   const int64_t rounds = (nb + 1023) / 1024;
-  constexpr int kRegs = 16;  // nb <= 16,384: every count held in registers
-  const bool in_regs = rounds <= kRegs;
-  auto count_at = [&](int64_t g) -> int64_t {
-    const int64_t n = n_samples[g];
-    return n > 1 ? n : 1;
-  };
+  constexpr int kRegs = kImpTilesRegRounds;  // nb <= 16,384: every count held in registers
+  static_assert(kImpTilesRound == 1024, "one group per thread and round");
+  const bool in_regs = imp_tiles_in_regs(nb);
+  auto count_at = [&](int64_t g) -> int64_t { return imp_count(n_samples[g]); };
   int64_t nv[kRegs];
   int64_t cand = 0;
   if (in_regs) {
@@ -142,7 +102,7 @@ __global__ void __launch_bounds__(1024) k_imp_tiles(const int64_t* __restrict__ 
   const int64_t cpt = imp_cand_per_tile(T);
   // a group k_imp_small codes takes no tile; cpt is a power of two
   const int lg = __builtin_ctzll((unsigned long long)cpt);
-  auto ntiles = [&](int64_t n) -> int64_t { return n <= kImpSmallN ? 0 : (n + cpt - 1) >> lg; };
+  auto ntiles = [&](int64_t n) -> int64_t { return imp_is_small(n) ? 0 : (n + cpt - 1) >> lg; };
   int64_t carry = 0;
   for (int64_t r = 0; r < rounds; ++r) {
     const int64_t g = r * 1024 + threadIdx.x;
@@ -253,17 +213,6 @@ __device__ __forceinline__ bool imp_screen_dim(float tl, float ts, float pl, flo
          o.B - o.B == 0.0f && o.C - o.C == 0.0f && o.umax - o.umax == 0.0f;
 }
 
-#ifndef CWQ_IMP_DYNAMIC_MIN_GROUPS
-#define CWQ_IMP_DYNAMIC_MIN_GROUPS 4096  // dynamic tile hand-out from this many groups
-#endif
-// ... or, when the host knows the launch's tile count, from this many tiles:
-// below it the one-address hand-out counter (an atomic per tile from every
-// workgroup) cost more than the balance it buys (I2's batch, ~4.4k tiles:
-// 0.206 -> 0.185 ms static; pln_is 0.18 -> 0.13 ms; I1's 99.9k tiles need it:
-// 8.40 -> 9.83 ms static)
-#ifndef CWQ_IMP_DYNAMIC_MIN_TILES
-#define CWQ_IMP_DYNAMIC_MIN_TILES 8192
-#endif
 #ifndef CWQ_IMP_MIN_WAVES
 #define CWQ_IMP_MIN_WAVES 1  // waves/SIMD the register allocator must allow (tools/variants.sh)
 #endif
@@ -314,9 +263,6 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
     tile = s_tile;
     __syncthreads();
   }
-#ifndef CWQ_IMP_PERMUTE
-#define CWQ_IMP_PERMUTE 1
-#endif
 #ifndef CWQ_IMP_GTAU_MASK
 #define CWQ_IMP_GTAU_MASK 63u  // 0: share tau with other tiles only at tile ends
 #endif
@@ -324,8 +270,7 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
   // (a permutation while total < P): a group's tiles go out spread over the
   // launch, so most start after an earlier one has published its tau in
   // gtau[g] instead of all starting from -inf side by side (I1: -6%)
-  const uint64_t pm = (CWQ_IMP_PERMUTE && next_tile && total > 1 && total < 0x7FFFFFFFll)
-                          ? 0x7FFFFFFFull % (uint64_t)total : 1ull;
+  const uint64_t pm = CWQ_IMP_PERM_MULTIPLIER(next_tile, total);
   for (; tile < total;) {
     uint32_t tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
@@ -339,7 +284,7 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
     const int64_t g = lo;
     const int64_t off = block_off[g];
     const int64_t d = block_off[g + 1] - off;
-    const int64_t N = n_samples[g] > 1 ? n_samples[g] : 1;
+    const int64_t N = imp_count(n_samples[g]);
     const int64_t n0 = (tq - tprefix[g]) * cpt;
     const int64_t n1 = (n0 + cpt < N) ? n0 + cpt : N;
     const PhiloxStream st = generate_key(
@@ -363,7 +308,7 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
     };
 
     // screening gate and constants
-    int ok = (allow_screen && d >= 1 && d <= kImpScreenMaxD) ? 1 : 0;
+    int ok = CWQ_IMP_SCREEN_BY_SHAPE(allow_screen, d) ? 1 : 0;
     if (ok && tid < d) {
       ImpScreenDim o;
       ok = imp_screen_dim(tl[tid], ts[tid], pl[tid], ps[tid], ct[tid], cp[tid], o) ? 1 : 0;
@@ -416,7 +361,7 @@ __global__ void __launch_bounds__(256, CWQ_IMP_MIN_WAVES) k_imp_eval(
       };
       // every Philox block index (n d + j) / 4 of the group below 2^32:
       // counter word 1 is 0 (normal4_screen_lo: one multiply less per block)
-      const bool lo32 = (uint64_t)N * (uint64_t)d <= (1ull << 34);
+      const bool lo32 = imp_lo32(N, d);
       auto scan = [&](auto HI0T) __attribute__((always_inline)) {
         constexpr bool HI0 = decltype(HI0T)::value;
         [[maybe_unused]] const PhiloxLo lok = HI0 ? philox_lo_key(st) : PhiloxLo{};
@@ -585,8 +530,8 @@ __global__ void __launch_bounds__(256) k_imp_small(
   const uint32_t wv = wave_id();
   const uint32_t lane = threadIdx.x & 63u;
   for (int64_t g = (int64_t)blockIdx.x * 4 + wv; g < nb; g += (int64_t)gridDim.x * 4) {
-    const int64_t N = n_samples[g] > 1 ? n_samples[g] : 1;
-    if (N > kImpSmallN) continue;  // wave-uniform
+    const int64_t N = imp_count(n_samples[g]);
+    if (!imp_is_small(N)) continue;  // wave-uniform
     const int64_t off = block_off[g];
     const int64_t d = block_off[g + 1] - off;
     const PhiloxStream st = generate_key(seeds.of(g), 42);
@@ -714,16 +659,13 @@ hipError_t launch_importance_encode(const float* t_loc, const float* t_scale, co
                        t_scale, p_scale, total_dims, lnt, lnp);
   hipLaunchKernelGGL(k_imp_tiles, dim3(1), dim3(1024), 0, stream, n_samples, nb, cpt, tprefix,
                      gtau, next_tile, keys);
-  const bool cmax = total_cands >= 0 && imp_cand_per_tile(total_cands) == kImpCandPerTile;
+  const bool cmax = imp_cpt_max(total_cands);
   auto eval = block_seeds ? (cmax ? k_imp_eval<true, true> : k_imp_eval<true, false>)
                           : (cmax ? k_imp_eval<false, true> : k_imp_eval<false, false>);
   hipLaunchKernelGGL(eval, dim3((unsigned)kImpEvalGrid), dim3(256), 0, stream, t_loc, t_scale,
                      p_loc, p_scale, lnt, lnp, block_off, n_samples, nb, (const int64_t*)tprefix,
                      (const int64_t*)cpt, ss, allow_screen, gtau, keys,
-                     (total_tiles >= 0 ? total_tiles >= CWQ_IMP_DYNAMIC_MIN_TILES
-                                       : nb >= CWQ_IMP_DYNAMIC_MIN_GROUPS)
-                         ? next_tile
-                         : nullptr);
+                     imp_dynamic_handout(total_tiles, nb) ? next_tile : nullptr);
   if (kImpSmallN > 0)
     hipLaunchKernelGGL(k_imp_small, dim3(grid_for(nb, 4, 65536)), dim3(256), 0, stream, t_loc,
                        t_scale, p_loc, p_scale, lnt, lnp, block_off, n_samples, nb, ss, keys);
@@ -734,13 +676,7 @@ hipError_t launch_importance_encode(const float* t_loc, const float* t_scale, co
 }
 
 int64_t importance_tile_count(const int64_t* n_samples_host, int64_t nb, int64_t total_cands) {
-  const int64_t cpt = imp_cand_per_tile(total_cands);  // k_imp_tiles' rule
-  int64_t tiles = 0;
-  for (int64_t g = 0; g < nb; ++g) {
-    const int64_t n = n_samples_host[g] > 1 ? n_samples_host[g] : 1;
-    tiles += n <= kImpSmallN ? 0 : (n + cpt - 1) / cpt;
-  }
-  return tiles;
+  return imp_tile_count(n_samples_host, nb, total_cands);
 }
 
 hipError_t launch_importance_decode(const int64_t* index, const float* p_loc,

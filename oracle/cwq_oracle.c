@@ -968,6 +968,41 @@ CWQO_API int cwqo_importance_encode_block(const float* t_loc, const float* t_sca
   return 0;
 }
 
+/* The importance weights (:58-61) of chosen rows of ONE block's candidate stream:
+ * out[i] = the score cwqo_importance_encode_block gives row rows[i] (any order,
+ * any 0 <= row < 2^63 / d).  For tests whose group is too large to scan. */
+CWQO_API int cwqo_importance_scores(const float* t_loc, const float* t_scale,
+                                    const float* p_loc, const float* p_scale, int64_t d,
+                                    int32_t seed, const int64_t* rows, int64_t n_rows,
+                                    float* out) {
+  if (d < 0 || n_rows < 0) return -1;
+  size_t db = (size_t)(d > 0 ? d : 1) * sizeof(float);
+  float* ct = (float*)malloc(db);
+  float* cp = (float*)malloc(db);
+  float* row = (float*)malloc(db);
+  if (!ct || !cp || !row) { free(ct); free(cp); free(row); return -2; }
+  for (int64_t j = 0; j < d; ++j) {
+    ct[j] = cwqo_log_normalization(t_scale[j]);
+    cp[j] = cwqo_log_normalization(p_scale[j]);
+  }
+  normal_stream st;
+  memset(&st, 0, sizeof(st));
+  cwqo_generate_key(seed, 42, st.key, st.ctr);
+  for (int64_t i = 0; i < n_rows; ++i) {
+    for (int64_t j = 0; j < d; ++j) {
+      float z = stream_normal(&st, (uint64_t)rows[i] * (uint64_t)d + (uint64_t)j);
+      float x = p_scale[j] * z;
+      x = p_loc[j] + x;
+      float lt = log_prob_c(x, t_loc[j], t_scale[j], ct[j]);
+      float lp = log_prob_c(x, p_loc[j], p_scale[j], cp[j]);
+      row[j] = lt - lp;
+    }
+    out[i] = cwqo_eigen_rowsum(row, d);
+  }
+  free(ct); free(cp); free(row);
+  return 0;
+}
+
 /* decode_importance_sample (:82-109): the last of index+1 samples = row index. */
 CWQO_API void cwqo_importance_decode_block(int64_t index, const float* p_loc,
                                            const float* p_scale, int64_t d, int32_t seed,

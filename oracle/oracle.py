@@ -69,6 +69,7 @@ def lib():
             "cwqo_importance_encode_block": (ci, [vp, vp, vp, vp, i64, i32, i64, vp, vp]),
             "cwqo_importance_decode_block": (None, [i64, vp, vp, i64, i32, vp]),
             "cwqo_importance_encode": (ci, [vp, vp, vp, vp, vp, i64, vp, i32, i64, vp, vp, ci]),
+            "cwqo_importance_scores": (ci, [vp, vp, vp, vp, i64, i32, vp, i64, vp]),
             "cwqo_quantize_quint16": (None, [vp, i64, f32, f32, vp]),
             "cwqo_dequantize_quint16": (None, [vp, i64, f32, f32, vp]),
         }
@@ -361,6 +362,18 @@ def importance_decode_block(index, p_loc, p_scale, seed):
     out = np.zeros(pl.size, dtype=np.float32)
     lib().cwqo_importance_decode_block(int(index), _p(pl), _p(ps), pl.size, int(seed), _p(out))
     return out
+
+
+def importance_scores(t_loc, t_scale, p_loc, p_scale, seed, rows):
+    """The importance weights of the given rows of one block's candidate stream
+    (the values importance_encode's argmax runs over), float32 [len(rows)]."""
+    tl, ts, pl, ps = map(_f32, (t_loc, t_scale, p_loc, p_scale))
+    r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+    out = np.zeros(max(r.size, 1), dtype=np.float32)
+    rc = lib().cwqo_importance_scores(_p(tl), _p(ts), _p(pl), _p(ps), tl.size, int(seed), _p(r),
+                                      r.size, _p(out))
+    assert rc == 0, rc
+    return out[:r.size]
 
 
 def quantize_quint16(x, mn=-30.0, mx=30.0):

@@ -1,13 +1,16 @@
 // Host build of the product's device-math restatement (csrc/cwq_math.h) and of
-// the screening bound (csrc/cwq_screen.h), and of the encode dispatch
-// (csrc/cwq_dispatch.h).  tests/test_math_exhaustive.py compares the first
+// the screening bound (csrc/cwq_screen.h), of the encode dispatch
+// (csrc/cwq_dispatch.h) and of the importance coder's launch plan
+// (csrc/cwq_imp_plan.h).  tests/test_math_exhaustive.py compares the first
 // with the host glibc over the full Box-Muller input domains;
-// tests/test_screen_bound.py checks the second's inequalities and
-// tests/test_encode_plan.py the third's table of shapes.
+// tests/test_screen_bound.py checks the second's inequalities,
+// tests/test_encode_plan.py the third's table of shapes and
+// tests/test_importance_plan.py the fourth's.
 // Test-only shim; not part of the product.
 #include <stdint.h>
 #include <vector>
 #include "../../compression_without_quantization_amd/csrc/cwq_dispatch.h"
+#include "../../compression_without_quantization_amd/csrc/cwq_imp_plan.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_math.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_screen.h"
 
@@ -127,5 +130,35 @@ void mc_dispatch_consts(int64_t* out) {
   out[0] = (int64_t)CWQ_CSR_COOP_ROWS_PER_LANE * cwq::kChipLanes;
   out[1] = CWQ_CSR_COOP_MIN_D;
   out[2] = CWQ_CSR_LDS_DIMS;
+}
+
+// The importance coder's launch plan (csrc/cwq_imp_plan.h).
+// out = (T, tile size, tiles, small groups, dynamic, permuted, multiplier,
+// PER_BLOCK, CPT_MAX, k_imp_tiles in registers); forms[g] (may be null) =
+// ImpRowForm | 0x80 when the group's screening counters are 32-bit (HI0).
+void mc_importance_plan(const int64_t* n_samples, const int64_t* block_off, int64_t nb,
+                        int total_known, int per_block_seeds, int allow_screen, int64_t* out,
+                        uint8_t* forms) {
+  const cwq::ImpLaunchPlan p = cwq::imp_launch_plan(n_samples, block_off, nb, total_known != 0,
+                                                    per_block_seeds != 0, allow_screen, forms);
+  out[0] = p.total_cands; out[1] = p.cpt; out[2] = p.tiles; out[3] = p.small_groups;
+  out[4] = p.dynamic; out[5] = p.permuted; out[6] = (int64_t)p.multiplier;
+  out[7] = p.per_block; out[8] = p.cpt_max; out[9] = p.tiles_in_regs;
+}
+// importance_tile_count's definition (the launcher's hand-out argument)
+int64_t mc_importance_tile_count(const int64_t* n_samples, int64_t nb, int64_t total_cands) {
+  return cwq::imp_tile_count(n_samples, nb, total_cands);
+}
+int64_t mc_importance_cand_per_tile(int64_t T) { return cwq::imp_cand_per_tile(T); }
+// (kImpSmallN, kImpMinCandPerTile, kImpCandPerTile, CWQ_IMP_TARGET_TILES,
+//  CWQ_IMP_DYNAMIC_MIN_GROUPS, CWQ_IMP_DYNAMIC_MIN_TILES, register rounds of
+//  k_imp_tiles x groups per round, kImpPruneMinD, kImpScreenMaxD,
+//  CWQ_IMP_SURVIVOR_CAP)
+void mc_importance_consts(int64_t* out) {
+  out[0] = cwq::kImpSmallN; out[1] = cwq::kImpMinCandPerTile; out[2] = cwq::kImpCandPerTile;
+  out[3] = CWQ_IMP_TARGET_TILES; out[4] = CWQ_IMP_DYNAMIC_MIN_GROUPS;
+  out[5] = CWQ_IMP_DYNAMIC_MIN_TILES;
+  out[6] = (int64_t)cwq::kImpTilesRegRounds * cwq::kImpTilesRound;
+  out[7] = cwq::kImpPruneMinD; out[8] = cwq::kImpScreenMaxD; out[9] = CWQ_IMP_SURVIVOR_CAP;
 }
 }
