@@ -4,8 +4,9 @@ Public surface mirrors the reference's code/coded_greedy_sampler.py,
 code/misc.py and code/binary_io.py (bit-string helpers); every sample is
 computed by the gfx950 kernels in libcwq.so (see include/cwq.h).
 """
-from .backfit import (backfit_blocks, code_grouped_greedy_sample_backfit,
-                      encode_blocks_backfit)
+from .backfit import (backfit_blocks, backfit_blocks_var, code_grouped_greedy_sample_backfit,
+                      code_grouped_greedy_sample_var_backfit, encode_blocks_backfit,
+                      encode_blocks_var_backfit)
 from .beam import code_grouped_greedy_sample_beam, encode_blocks_beam
 from .binary_io import (bitcode_to_indices, elias_delta_code, elias_delta_decode,
                         elias_delta_code_many, elias_delta_decode_many,
@@ -51,4 +52,5 @@ __all__ = [
     "code_grouped_greedy_sample_var", "decode_grouped_greedy_sample_var",
     "encode_blocks_beam", "code_grouped_greedy_sample_beam",
     "backfit_blocks", "encode_blocks_backfit", "code_grouped_greedy_sample_backfit",
+    "backfit_blocks_var", "encode_blocks_var_backfit", "code_grouped_greedy_sample_var_backfit",
 ]

@@ -18,6 +18,12 @@
 //     the count are stored.  One wave (or one lane) handles a block alone.
 // k_backfit_init fills the cache and v before the first sweep, k_backfit_final
 // writes the sample and the value after the last.
+//
+// Under per-block bit budgets (cwq_greedy_backfit_var) the blocks
+// arrive sorted by budget and only the scoring differs: one launch sequence per
+// budget bucket on that bucket's slice of the shared arrays (BackfitBucket),
+// between the same k_backfit_base and accept launch over all blocks.  None of
+// the kernels here reads a bit count: they read indices and keys.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -309,6 +315,40 @@ hipError_t launch_backfit(const BackfitArgs& b, hipStream_t stream) {
   a.count = b.count;
   a.idx = e.out_idx;
   a.keys = e.keys;
+  // step s's scoring launches: the call's own, or one sequence per budget
+  // bucket on that bucket's slice of the shared arrays.  The
+  // screening arrays are not shifted: the buckets use them in stream order and
+  // each sequence initialises what it reads.
+  auto score = [&](int s) -> hipError_t {
+    if (!b.buckets) return launch_score_step(e, s, stream);
+    for (int i = 0; i < b.n_buckets; ++i) {
+      const BackfitBucket& k = b.buckets[i];
+      EncodeArgs p = e;
+      p.t_loc = e.t_loc + k.d0;
+      p.t_scale = e.t_scale + k.d0;
+      p.p_loc = e.p_loc + k.d0;
+      p.p_scale = e.p_scale + k.d0;
+      p.loc_s = e.loc_s + k.d0;
+      p.scale_s = e.scale_s + k.d0;
+      p.lognorm = e.lognorm + k.d0;
+      p.out_sample = e.out_sample + k.d0;
+      p.keys = e.keys + k.r0;
+      p.out_idx = e.out_idx + k.r0 * e.n_steps;
+      p.block_id_base = e.block_id_base + k.r0;
+      if (e.seeds) p.seeds = e.seeds + k.r0;
+      p.block_off = k.block_off;
+      p.nb = k.count;
+      p.total_dims = k.dims;
+      p.max_d = k.maxd;
+      p.n_cand = (int64_t)1 << k.bits;
+      p.tiles_per_block = k.tiles_per_block;
+      p.cand_per_tile = k.cand_per_tile;
+      p.rows_wave = k.rows_wave;
+      const hipError_t se = launch_score_step(p, s, stream);
+      if (se != hipSuccess) return se;
+    }
+    return hipSuccess;
+  };
   const unsigned wgrid = grid_for(e.nb, 4, 1u << 16);
   const unsigned dgrid = grid_for(D > e.nb ? D : e.nb, 256, 1u << 16);
   hipLaunchKernelGGL(k_backfit_init, dim3(wgrid), dim3(256), 0, stream, a);
@@ -324,7 +364,7 @@ hipError_t launch_backfit(const BackfitArgs& b, hipStream_t stream) {
       if (k == 0 && s == 0 && e.ev_start &&
           (err = hipEventRecord((hipEvent_t)e.ev_start, stream)) != hipSuccess)
         return err;
-      if ((err = launch_score_step(e, s, stream)) != hipSuccess) return err;
+      if ((err = score(s)) != hipSuccess) return err;
       if (k == sweeps - 1 && s == e.n_steps - 1 && e.ev_stop &&
           (err = hipEventRecord((hipEvent_t)e.ev_stop, stream)) != hipSuccess)
         return err;

@@ -3074,6 +3074,161 @@ int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_
   return ok();
 }
 
+// Backfitting under per-block budgets: the budget call's sort,
+// sorted layout and gather, the table's rows gathered with their range check,
+// one wait for the buckets' facts and the check's count, then launch_backfit
+// over all sorted blocks with a scoring launch sequence per bucket, and the
+// scatter back.  The caller's arrays are written by that scatter alone.
+int cwq_greedy_backfit_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                           const float* p_scale, const int64_t* block_off, int64_t nb,
+                           int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                           int n_steps, int sweeps, int32_t seed, float rho,
+                           int64_t block_id_base, int32_t* idx_inout, float* out_sample,
+                           float* out_value, int32_t* out_accepted, void* workspace,
+                           size_t workspace_bytes, const cwq_options* opts, void* stream) {
+  int rc;
+  if ((rc = check_var_nb(nb))) return rc;
+  if (n_steps < 1) return fail(CWQ_ERR_INVALID, "n_steps=%d must be >= 1", n_steps);
+  if (sweeps < 0 || sweeps > CWQ_MAX_BACKFIT_SWEEPS)
+    return fail(CWQ_ERR_INVALID, "sweeps=%d outside [0, %d]", sweeps, CWQ_MAX_BACKFIT_SWEEPS);
+  if (!var_csr_sizes_ok(nb, total_dims, max_block_dim, n_steps))
+    return fail(CWQ_ERR_INVALID, "bad total_dims / max_block_dim / n_steps");
+  const bool csr = block_off != nullptr;
+  const int64_t d = max_block_dim;
+  if (!csr && nb > 0 && (d > INT64_MAX / 64 / nb || nb * d != total_dims))
+    return fail(CWQ_ERR_INVALID, "uniform blocks: total_dims must be nb * max_block_dim");
+  cwq_options o;
+  if ((rc = read_options(opts, &o))) return rc;
+  if (nb == 0) return ok();  // no block: nothing to refine, nothing is launched
+  if (!n_bits || !idx_inout) return fail(CWQ_ERR_INVALID, "n_bits / idx_inout is null");
+  if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
+    return fail(CWQ_ERR_INVALID, "null input/output pointer");
+  const cwq::BackfitVarWs l = cwq::backfit_var_ws(csr, nb, total_dims, max_block_dim, n_steps);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  void* w = workspace;
+  float* tl_s = at<float>(w, l.t_loc);
+  float* ts_s = at<float>(w, l.t_scale);
+  float* pl_s = at<float>(w, l.p_loc);
+  float* ps_s = at<float>(w, l.p_scale);
+  float* sample_s = at<float>(w, l.sample);
+  int32_t* seeds_s = at<int32_t>(w, l.seeds);
+  int32_t* perm = at<int32_t>(w, l.perm);
+  uint32_t* counts_dev = at<uint32_t>(w, l.counts);  // 32 counts, then `bad`
+  uint32_t* bad_dev = at<uint32_t>(w, l.bad);
+  int32_t* table = at<int32_t>(w, l.table);
+  cwq::VbcFacts* facts_dev = at<cwq::VbcFacts>(w, l.facts);
+  int64_t* soff = at<int64_t>(w, l.soff);
+  int64_t* roff = at<int64_t>(w, l.roff);
+  int64_t* src = at<int64_t>(w, l.src);
+  // everything up to the sorted copies lies in the workspace and is enqueued
+  // before the host waits; nothing here depends on the values being valid
+  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, at<uint32_t>(w, l.hist), counts_dev, st);
+  if (e == hipSuccess && csr) {
+    e = cwq::launch_vbc_layout(n_bits, block_off, perm, nb, counts_dev,
+                               at<unsigned long long>(w, l.wgfacts), facts_dev, seed,
+                               block_id_base, soff, roff, src, seeds_s, at<int64_t>(w, l.partial),
+                               st);
+    if (e == hipSuccess)
+      e = cwq::launch_vbc_gather(t_loc, t_scale, p_loc, p_scale, soff, src, nb, total_dims, tl_s,
+                                 ts_s, pl_s, ps_s, st);
+  } else if (e == hipSuccess) {
+    e = cwq::launch_vb_gather(t_loc, t_scale, p_loc, p_scale, perm, nb, d, seed, block_id_base,
+                              tl_s, ts_s, pl_s, ps_s, seeds_s, st);
+  }
+  if (e == hipSuccess)
+    e = cwq::launch_vb_gather_table(idx_inout, n_bits, perm, nb, n_steps, table, bad_dev, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var (sort / gather)");
+  // the one synchronisation: the buckets' sizes decide the launches, and the
+  // table's check comes with them
+  cwq::VbcFacts f;
+  uint32_t cb[33];  // uniform blocks: the counts and the check's word in one copy
+  if (csr) {
+    e = hipMemcpyAsync(&f, facts_dev, sizeof(f), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&cb[32], bad_dev, 4, hipMemcpyDeviceToHost, st);
+  } else {
+    e = hipMemcpyAsync(cb, counts_dev, sizeof(cb), hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var (facts)");
+  if (!csr) {  // the facts of uniform blocks follow from the counts
+    int64_t row = 0;
+    f.bad_len = 0;
+    for (int b = 0; b < 32; ++b) {
+      f.counts[b] = cb[b];
+      f.start[b] = (uint32_t)row;
+      f.pre[b] = row * d;
+      f.dims[b] = (int64_t)cb[b] * d;
+      f.maxd[b] = cb[b] ? d : 0;
+      row += cb[b];
+    }
+  }
+  if (f.counts[31] != 0)
+    return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", f.counts[31],
+                (long long)nb, CWQ_MAX_BITS_PER_STEP);
+  if (f.bad_len != 0)
+    return fail(CWQ_ERR_INVALID, "block_off decreases at %lld blocks", (long long)f.bad_len);
+  int64_t sum_dims = 0, longest = 0;
+  for (int b = 0; b <= CWQ_MAX_BITS_PER_STEP; ++b) {
+    sum_dims += f.dims[b];
+    longest = std::max(longest, f.maxd[b]);
+  }
+  if (sum_dims > total_dims)
+    return fail(CWQ_ERR_INVALID, "the blocks hold %lld dims, total_dims=%lld", (long long)sum_dims,
+                (long long)total_dims);
+  if (longest > max_block_dim)
+    return fail(CWQ_ERR_INVALID, "a block holds %lld dims, max_block_dim=%lld",
+                (long long)longest, (long long)max_block_dim);
+  if (cb[32] != 0)
+    return fail(CWQ_ERR_INVALID, "%u of %lld entries of idx_inout lie outside [0, 2^n_bits[g])",
+                cb[32], (long long)nb * n_steps);
+  // the buckets that score: at least one bit and one block, from the top as
+  // cwq_greedy_encode_var walks them
+  cwq::BackfitBucket buckets[CWQ_MAX_BITS_PER_STEP];
+  int n_buckets = 0, top = 0;
+  for (int b = CWQ_MAX_BITS_PER_STEP; b >= 1; --b) {
+    const int64_t c = f.counts[b];
+    if (c == 0) continue;
+    top = std::max(top, b);
+    cwq::BackfitBucket& k = buckets[n_buckets++];
+    k.bits = b;
+    k.r0 = f.start[b];
+    k.d0 = f.pre[b];
+    k.count = c;
+    k.dims = f.dims[b];
+    k.maxd = f.maxd[b];  // its own longest block: short blocks stay off the long-block path
+    k.block_off = csr ? roff + k.r0 + b : nullptr;
+    choose_tiling(c, (int64_t)1 << b, &k.tiles_per_block, &k.cand_per_tile);
+    k.rows_wave = csr && cwq::bucket_takes_rows_wave(b, f.dims[b], c, o.prune_mode);
+  }
+  char* encw = at<char>(w, l.enc);
+  cwq::BackfitArgs a;
+  fill_encode_args(a.enc, tl_s, ts_s, pl_s, ps_s, csr ? soff : nullptr, csr ? 0 : d, nb, sum_dims,
+                   longest, top, n_steps, seed, rho, block_id_base, table, sample_s, o, l.encl,
+                   encw);
+  a.enc.seeds = seeds_s;
+  a.sweeps = sweeps;
+  a.rows = at<float>(w, l.rows);
+  a.value = at<float>(w, l.value);
+  a.count = at<int32_t>(w, l.count);
+  a.out_value = nullptr;  // the scatter below writes the caller's arrays
+  a.out_accepted = nullptr;
+  a.path = cwq::backfit_plan(longest, nb);
+  a.buckets = buckets;
+  a.n_buckets = n_buckets;
+  e = cwq::launch_backfit(a, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var");
+  if (csr)
+    e = cwq::launch_vbc_scatter(sample_s, table, soff, src, perm, nb, total_dims, n_steps,
+                                out_sample, idx_inout, st);
+  else
+    e = cwq::launch_vb_scatter(sample_s, table, perm, nb, d, n_steps, out_sample, idx_inout, st);
+  if (e == hipSuccess)
+    e = cwq::launch_vb_scatter_blocks(a.value, a.count, perm, nb, out_value, out_accepted, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var (scatter)");
+  return ok();
+}
+
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream) {
   if (n_waves < 0 || n_waves > (1LL << 31) || (n_waves > 0 && (!x || !out)))
     return fail(CWQ_ERR_INVALID, "cwq_selftest_wave_max: bad arguments");

@@ -266,6 +266,18 @@ hipError_t launch_vbc_scatter(const float* sample_s, const int32_t* idx_s, const
                               int n_steps, float* out_sample, int32_t* out_idx,
                               hipStream_t stream);
 
+// Backfitting under budgets.  Row r of idx_s = row perm[r] of
+// the table idx [nb, n_steps]; *bad = the entries outside [0, 2^bits[g]) of
+// their block g (blocks whose count is itself outside [0, 30] are not tested).
+hipError_t launch_vb_gather_table(const int32_t* idx, const int32_t* bits, const int32_t* perm,
+                                  int64_t nb, int n_steps, int32_t* idx_s, uint32_t* bad,
+                                  hipStream_t stream);
+// out_value[perm[r]] = value_s[r], out_count[perm[r]] = count_s[r] (either
+// output may be nullptr).
+hipError_t launch_vb_scatter_blocks(const float* value_s, const int32_t* count_s,
+                                    const int32_t* perm, int64_t nb, float* out_value,
+                                    int32_t* out_count, hipStream_t stream);
+
 // ---- beam search over steps (cwq_beam.hip) -------------------
 constexpr int kMaxBeam = 16;  // CWQ_MAX_BEAM
 struct BeamArgs {
@@ -304,6 +316,18 @@ hipError_t launch_prep_dims(const float* t_scale, const float* p_loc, const floa
 hipError_t launch_score_step(const EncodeArgs& a, int step, hipStream_t stream);
 // rows, value, count: what a backfit call has beyond the encoder's arrays
 // (backfit_ws, cwq_workspace.h)
+// One budget's slice of a call whose blocks are sorted by budget (DESIGN.md
+// 4h): rows [r0, r0 + count) and dims [d0, d0 + dims) of the call's arrays, none
+// of its blocks longer than maxd.  Its scoring launches get the call's arrays
+// shifted to r0 / d0, the offsets block_off (relative to d0; nullptr: uniform)
+// and the shape's own candidate count, tiling and path.
+struct BackfitBucket {
+  int bits;
+  int64_t r0, d0, count, dims, maxd;
+  const int64_t* block_off;
+  int64_t tiles_per_block, cand_per_tile;
+  bool rows_wave;
+};
 struct BackfitArgs {
   EncodeArgs enc;      // the encoder's arguments; out_idx is the table (in and out),
                        // out_sample the carried vector between the launches and the result
@@ -314,6 +338,12 @@ struct BackfitArgs {
   float* out_value;       // or nullptr
   int32_t* out_accepted;  // or nullptr
   BackfitPath path;
+  // nullptr: one budget (enc.n_cand) for every block, one scoring launch
+  // sequence per step.  Otherwise the call's buckets (each of at least one bit
+  // and one block): a scoring launch sequence per step and bucket; blocks in no
+  // bucket keep key 0, i.e. row 0.  Everything else covers all blocks at once.
+  const BackfitBucket* buckets = nullptr;
+  int n_buckets = 0;
 };
 hipError_t launch_backfit(const BackfitArgs& a, hipStream_t stream);
 

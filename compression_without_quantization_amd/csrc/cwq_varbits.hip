@@ -14,8 +14,13 @@
 // k_vbc_soff_final) and a segmented gather and scatter (k_vbc_gather,
 // k_vbc_scatter).
 //
-// Every result is reproducible: the only atomics are integer LDS adds of a
-// histogram, all global writes are plain vector stores.
+// Backfitting under budgets adds the gather of an index table
+// into sorted order with its range check (k_vb_gather_table) and the scatter
+// of the per-block results (k_vb_scatter_blocks).
+//
+// Every result is reproducible: the only atomics are integer adds (a histogram
+// in LDS, the range check's count of failures), all other global writes are
+// plain vector stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -641,6 +646,50 @@ __global__ void __launch_bounds__(kVbThreads) k_vbc_scatter(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Backfitting under budgets: an index table's rows into sorted
+// order with the range check folded in, and a block's value and accept count
+// back to caller order.  An entry of block g fails when it lies outside
+// [0, 2^bits[g]); a block whose count is itself out of range is not tested (the
+// sort reports it).  The failures are summed in LDS and reach *bad, which the
+// launcher zeroed, by one integer add per workgroup that saw any.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kVbThreads) k_vb_gather_table(
+    const int32_t* __restrict__ idx, const int32_t* __restrict__ bits,
+    const int32_t* __restrict__ perm, int64_t nb, int64_t n_steps, int32_t* __restrict__ idx_s,
+    uint32_t* __restrict__ bad) {
+  __shared__ uint32_t fails;
+  if (threadIdx.x == 0) fails = 0;
+  __syncthreads();
+  const int64_t ni = nb * n_steps;
+  uint32_t mine = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ni;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t r, s;
+    vb_row_of(i, n_steps, r, s);
+    const int64_t g = perm[r];
+    const int32_t v = idx[g * n_steps + s];
+    const int32_t b = bits[g];
+    if (b >= 0 && b <= kVbMaxBits && (v < 0 || v >= ((int32_t)1 << b))) ++mine;
+    idx_s[i] = v;
+  }
+  if (mine) atomicAdd(&fails, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && fails) atomicAdd(bad, fails);
+}
+
+__global__ void __launch_bounds__(kVbThreads) k_vb_scatter_blocks(
+    const float* __restrict__ value_s, const int32_t* __restrict__ count_s,
+    const int32_t* __restrict__ perm, int64_t nb, float* __restrict__ out_value,
+    int32_t* __restrict__ out_count) {
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nb;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t g = perm[r];
+    if (out_value) out_value[g] = value_s[r];
+    if (out_count) out_count[g] = count_s[r];
+  }
+}
+
 bool aligned16_all(const void* a, const void* b, const void* c, const void* d) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) == 0;
 }
@@ -806,6 +855,28 @@ hipError_t launch_vbc_scatter(const float* sample_s, const int32_t* idx_s, const
   hipLaunchKernelGGL(k_vbc_scatter, dim3(grid_for(work, kVbThreads, 1u << 20)), dim3(kVbThreads),
                      0, stream, sample_s, idx_s, soff, src, perm, nb, cap, (int64_t)n_steps,
                      out_sample, out_idx);
+  return hipGetLastError();
+}
+
+hipError_t launch_vb_gather_table(const int32_t* idx, const int32_t* bits, const int32_t* perm,
+                                  int64_t nb, int n_steps, int32_t* idx_s, uint32_t* bad,
+                                  hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(bad, 0, 4, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_vb_gather_table, dim3(grid_for(nb * n_steps, kVbThreads, 1u << 16)),
+                     dim3(kVbThreads), 0, stream, idx, bits, perm, nb, (int64_t)n_steps, idx_s,
+                     bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_vb_scatter_blocks(const float* value_s, const int32_t* count_s,
+                                    const int32_t* perm, int64_t nb, float* out_value,
+                                    int32_t* out_count, hipStream_t stream) {
+  if (nb <= 0 || (!out_value && !out_count)) return hipSuccess;
+  hipLaunchKernelGGL(k_vb_scatter_blocks, dim3(grid_for(nb, kVbThreads, 1u << 16)),
+                     dim3(kVbThreads), 0, stream, value_s, count_s, perm, nb, out_value,
+                     out_count);
   return hipGetLastError();
 }
 

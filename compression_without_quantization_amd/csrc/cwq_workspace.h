@@ -504,4 +504,63 @@ inline BackfitWs backfit_ws(bool csr, int64_t nb, int64_t total_dims, int64_t ma
   return l;
 }
 
+// ---- backfitting under per-block budgets (cwq_greedy_backfit_var) --
+// The budget call's layout for the shape (var_csr_ws, or var_ws at n_steps = 1),
+// then backfit's rows, value and count, all over the sorted blocks.  What the
+// call uses of the budget layout:
+//   t_loc .. p_scale  the sorted inputs, live through the sweeps
+//   sample            the vector the scoring launches carry; the sorted result
+//   table             the sorted copy of the caller's table, refined in place:
+//                     ragged blocks take the budget call's `stage`; uniform
+//                     blocks a region of their own behind that layout (its
+//                     stage lies on the sorted inputs, which stay live here)
+//   bad               one word right behind the 32 bucket counts: the table's
+//                     entries outside [0, 2^n_bits[g]) (uniform blocks: the host
+//                     reads the 33 words in one copy)
+//   enc               every bucket's scoring launches (enc_ws_* is monotone);
+//                     keys, loc_s, scale_s and lognorm are the call's, shared
+// Regions the blocks' form does not have are empty.  Totals, which include/cwq.h
+// states in terms of the size functions:
+//   ragged   var_csr_ws(nb, D, maxd, n_steps) + backfit_ws(csr, nb, D, maxd, n_steps)
+//            - enc_ws_csr(nb, D, maxd)
+//   uniform  var_ws(nb, d, 1) + up(4 nb n_steps) + the same difference at
+//            (nb, nb d, d, n_steps)
+struct BackfitVarWs {
+  Region t_loc, t_scale, p_loc, p_scale, sorted_in, sample, seeds, perm, hist, counts, bad,
+      wgfacts, facts, soff, roff, src, partial, table, enc, rows, value, count;
+  size_t total;
+  bool csr;
+  EncWs encl;  // the arrays inside `enc` (offsets relative to it)
+};
+inline BackfitVarWs backfit_var_ws(bool csr, int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                   int n_steps) {
+  BackfitVarWs l{};
+  l.csr = csr;
+  const size_t n = (size_t)nb;
+  Arena a;
+  if (csr) {
+    const VarCsrWs v = var_csr_ws(nb, total_dims, max_block_dim, n_steps);
+    l.t_loc = v.t_loc, l.t_scale = v.t_scale, l.p_loc = v.p_loc, l.p_scale = v.p_scale;
+    l.sample = v.sample, l.seeds = v.seeds, l.perm = v.perm, l.hist = v.hist, l.counts = v.counts;
+    l.wgfacts = v.wgfacts, l.facts = v.facts, l.soff = v.soff, l.roff = v.roff, l.src = v.src;
+    l.partial = v.partial, l.table = v.stage, l.enc = v.enc;
+    l.encl = enc_ws_csr(nb, total_dims, max_block_dim);
+    a.o = v.total;
+  } else {
+    const VarWs v = var_ws(nb, max_block_dim, 1);
+    l.t_loc = v.t_loc, l.t_scale = v.t_scale, l.p_loc = v.p_loc, l.p_scale = v.p_scale;
+    l.sorted_in = v.sorted_in, l.sample = v.sample, l.seeds = v.seeds, l.perm = v.perm;
+    l.hist = v.hist, l.counts = v.counts, l.enc = v.enc;
+    l.encl = enc_ws_uniform(nb, max_block_dim);
+    a.o = v.total;
+    l.table = a.take(n * (size_t)n_steps * 4);
+  }
+  l.bad = Region{l.counts.off + l.counts.bytes, 4};  // in the counts' rounding room
+  l.rows = a.take((size_t)n_steps * total_dims * 4);
+  l.value = a.take(n * 4);
+  l.count = a.take(n * 4);
+  l.total = a.o;
+  return l;
+}
+
 }  // namespace cwq

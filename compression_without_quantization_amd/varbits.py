@@ -320,26 +320,12 @@ def decode_blocks_var(code_or_idx, n_bits, p_loc, p_scale, n_steps, seed, rho=1.
 # ---------------------------------------------------------------------------
 # the grouped coder with a budget per group (composed from the calls above)
 # ---------------------------------------------------------------------------
-def code_grouped_greedy_sample_var(target, proposal, n_steps, n_bits_per_step, seed,
-                                   max_group_size_bits=12, rho=1.,
-                                   extra_bits=1.0 / math.log(2.0), min_bits=0, prune_mode=None):
-    """code_grouped_greedy_sample with a bit count per group.
-
-    The standardisation, the per-dim KL and the partition are those of
-    code_grouped_greedy_sample (``n_bits_per_step * n_steps`` decides where a
-    group closes); group g is then coded with seed ``seed + g`` at
-    ``block_bits(block_off=starts, n_steps=n_steps, min_bits=min_bits,
-    max_bits=n_bits_per_step)[g]`` bits per step instead of ``n_bits_per_step``,
-    so no group spends more than the reference call, and
-    ``min_bits = n_bits_per_step`` gives its sample and indices exactly.
-    Returns (sample np.float32 [D], code bytes (pack_indices), total_bits,
-    group_start_indices list with D appended, group_bits np.int32 [G]); the
-    decoder needs the last two next to the code.  ``prune_mode``: the encoder's
-    cwq_options.prune_mode; results never depend on it.  Leave it at the
-    default: buckets of long groups at fewer than 12 bits are then scored with a
-    wave per candidate row (c2low: 18.7 ms against 82-88 ms with
-    ``prune_mode=0``, DESIGN.md 4e).
-    """
+def _code_grouped_var_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
+                           max_group_size_bits, extra_bits, min_bits):
+    """code_grouped_greedy_sample_var's pipeline around a block encoder:
+    standardise, per-dim KL, partition, budgets, ``encode(t_loc, t_scale, zeros,
+    ones, bits, starts)`` -> (idx, sample) on the standard proposal,
+    destandardise, pack_indices."""
     lib = _lib.load()
     dev = _device_of(target.loc, target.scale, proposal.loc, proposal.scale)
     q_loc, q_scale = _dist_parts(target, dev, "Target")
@@ -363,8 +349,7 @@ def code_grouped_greedy_sample_var(target, proposal, n_steps, n_bits_per_step, s
                       n_steps=n_steps, min_bits=min_bits, max_bits=n_bits_per_step)
     zeros = torch.zeros(D, dtype=torch.float32, device=dev)
     ones = torch.ones(D, dtype=torch.float32, device=dev)
-    idx, sample = encode_blocks_var(t_loc, t_scale, zeros, ones, bits, n_steps, seed, rho=rho,
-                                    block_off=starts, prune_mode=prune_mode)
+    idx, sample = encode(t_loc, t_scale, zeros, ones, bits, starts)
     out = torch.empty(D, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.cwq_destandardise(_ptr(sample), _ptr(p_loc), _ptr(p_scale), D, _ptr(out),
@@ -373,6 +358,33 @@ def code_grouped_greedy_sample_var(target, proposal, n_steps, n_bits_per_step, s
     code, total_bits = pack_indices(idx, bits)
     return (out.cpu().numpy(), code.cpu().numpy().tobytes(), total_bits, starts.tolist(),
             bits.cpu().numpy())
+
+
+def code_grouped_greedy_sample_var(target, proposal, n_steps, n_bits_per_step, seed,
+                                   max_group_size_bits=12, rho=1.,
+                                   extra_bits=1.0 / math.log(2.0), min_bits=0, prune_mode=None):
+    """code_grouped_greedy_sample with a bit count per group.
+
+    The standardisation, the per-dim KL and the partition are those of
+    code_grouped_greedy_sample (``n_bits_per_step * n_steps`` decides where a
+    group closes); group g is then coded with seed ``seed + g`` at
+    ``block_bits(block_off=starts, n_steps=n_steps, min_bits=min_bits,
+    max_bits=n_bits_per_step)[g]`` bits per step instead of ``n_bits_per_step``,
+    so no group spends more than the reference call, and
+    ``min_bits = n_bits_per_step`` gives its sample and indices exactly.
+    Returns (sample np.float32 [D], code bytes (pack_indices), total_bits,
+    group_start_indices list with D appended, group_bits np.int32 [G]); the
+    decoder needs the last two next to the code.  ``prune_mode``: the encoder's
+    cwq_options.prune_mode; results never depend on it.  Leave it at the
+    default: buckets of long groups at fewer than 12 bits are then scored with a
+    wave per candidate row (c2low: 18.7 ms against 82-88 ms with
+    ``prune_mode=0``, DESIGN.md 4e).
+    """
+    def encode(t_loc, t_scale, zeros, ones, bits, starts):
+        return encode_blocks_var(t_loc, t_scale, zeros, ones, bits, n_steps, seed, rho=rho,
+                                 block_off=starts, prune_mode=prune_mode)
+    return _code_grouped_var_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
+                                  max_group_size_bits, extra_bits, min_bits)
 
 
 def decode_grouped_greedy_sample_var(code, group_start_indices, group_bits, proposal, n_steps,

@@ -105,8 +105,10 @@ extern "C" {
  *   0.11 beam search over the greedy coder's steps: cwq_beam_encode, its
  *        workspace size and cwq_selftest_beam_encode (no decoder change);
  *   0.12 backfitting: cwq_greedy_backfit and its workspace size (no decoder
- *        change). */
-#define CWQ_ABI_VERSION ((0 << 16) | 12)
+ *        change);
+ *   0.13 backfitting under per-block bit budgets: cwq_greedy_backfit_var (no
+ *        new size function, no decoder change). */
+#define CWQ_ABI_VERSION ((0 << 16) | 13)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -777,6 +779,52 @@ int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_
                        int32_t* idx_inout, float* out_sample, float* out_value,
                        int32_t* out_accepted, void* workspace, size_t workspace_bytes,
                        const cwq_options* opts, void* stream);
+
+/* Backfitting under per-block bit budgets.  Block g is refined exactly as
+ * cwq_greedy_backfit refines it in a call of its own with n_bits_per_step =
+ * n_bits[g] and block seed seed + block_id_base + g: N_g = 2^n_bits[g] rows per
+ * step, the same sweeps, the same accept test.  A block at n_bits[g] = 0, an
+ * empty block and a code of one step are returned as given; sweeps = 0 returns
+ * the table with its decoded sample and value.  The table is that of
+ * cwq_greedy_encode_var / cwq_greedy_encode_uniform_var (or any other whose row
+ * g lies in [0, N_g)), the result goes to the same decoders and
+ * cwq_pack_indices_var.
+ *   block_off     device [nb + 1], or NULL for uniform blocks of max_block_dim
+ *                 dims (total_dims = nb * max_block_dim)
+ *   n_bits        device [nb] int32, each in [0, CWQ_MAX_BITS_PER_STEP]
+ *   idx_inout, out_sample, out_value, out_accepted, sweeps, opts: as above; the
+ *                 eval events bracket the first to the last scoring launch of
+ *                 the call (an empty bracket when there is none).
+ * The blocks are sorted by budget as in cwq_greedy_encode_var; a step of a
+ * sweep is one scoring launch sequence per budget in use (none for budget 0)
+ * between two launches over all blocks, all on `stream`.  Results never depend
+ * on prune_mode, launch geometry or timing.
+ * The call waits for the device once, as cwq_greedy_encode_var does, because
+ * the bucket sizes decide the launches: it cannot be captured into a graph.
+ * In that one wait it also validates what lives on the device, so unlike
+ * cwq_greedy_backfit it refuses an out-of-range table itself: CWQ_ERR_INVALID
+ * with the number of entries outside [0, N_g), and likewise for n_bits outside
+ * [0, 30] and a decreasing block_off.  On every refusal idx_inout, out_sample,
+ * out_value and out_accepted have not been written: the call works on a sorted
+ * copy of the table in the workspace and writes the caller's arrays only in its
+ * last launches.
+ * Workspace (no size function of its own; less returns CWQ_ERR_WORKSPACE):
+ *   ragged   cwq_greedy_encode_var_workspace_size(nb, total_dims, max_block_dim,
+ *            n_steps) + cwq_greedy_backfit_workspace_size(nb, total_dims,
+ *            max_block_dim, n_steps) - cwq_greedy_encode_workspace_size(nb,
+ *            total_dims, max_block_dim)
+ *   uniform  cwq_greedy_encode_uniform_var_workspace_size(nb, d) +
+ *            round256(4 * nb * n_steps) + cwq_greedy_backfit_workspace_size(nb,
+ *            nb * d, d, n_steps) - cwq_greedy_encode_workspace_size(nb, nb * d, d)
+ * with d = max_block_dim and round256 the next multiple of 256. */
+int cwq_greedy_backfit_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                           const float* p_scale, const int64_t* block_off /* NULL: uniform */,
+                           int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                           const int32_t* n_bits /* device [nb], each in [0, 30] */,
+                           int n_steps, int sweeps, int32_t seed, float rho,
+                           int64_t block_id_base, int32_t* idx_inout, float* out_sample,
+                           float* out_value, int32_t* out_accepted, void* workspace,
+                           size_t workspace_bytes, const cwq_options* opts, void* stream);
 
 
 /* ---- PLN image codec plumbing (csrc/cwq_pln.hip) ----
