@@ -140,6 +140,9 @@ SIGNATURES = {
     "cwq_selftest_encode_rows_wave": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                               c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp,
                                               c_size, c_vp]),
+    "cwq_selftest_encode_uniform_tau_guess": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int,
+                                                      c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp,
+                                                      c_size, c_opts, c_vp, c_int]),
     "cwq_beam_encode_workspace_size": (c_size, [c_i64, c_i64, c_i64, c_int, c_int]),
     "cwq_beam_encode": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int,
                                 c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_size, c_opts,
@@ -171,7 +174,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 13
+ABI_VERSION = (0 << 16) | 14
 
 _lib = None
 

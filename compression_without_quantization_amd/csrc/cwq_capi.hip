@@ -349,7 +349,7 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
                 void* workspace, size_t workspace_bytes, const cwq_options* opts, void* stream,
                 const int32_t* block_seeds = nullptr, float* ds_out = nullptr,
                 const float* ds_loc = nullptr, const float* ds_scale = nullptr,
-                bool rows_wave = false) {
+                bool rows_wave = false, int tau_guess = -1) {
   int rc = check_common(n_bits, n_steps, nb);
   if (rc) return rc;
   cwq_options o;
@@ -372,6 +372,7 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
   a.ds_loc = ds_loc;
   a.ds_scale = ds_scale;
   a.rows_wave = rows_wave;
+  a.tau_guess = tau_guess;
   hipError_t e = cwq::launch_encode(a, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode");
   return ok();
@@ -2930,6 +2931,23 @@ int cwq_selftest_encode_rows_wave(const float* t_loc, const float* t_scale, cons
                      n_bits_per_step, n_steps, seed, rho, block_id_base, out_idx, out_sample,
                      workspace, workspace_bytes, nullptr, stream, nullptr, nullptr, nullptr,
                      nullptr, /*rows_wave=*/true);
+}
+
+int cwq_selftest_encode_uniform_tau_guess(const float* t_loc, const float* t_scale,
+                                          const float* p_loc, const float* p_scale, int64_t nb,
+                                          int64_t d, int n_bits_per_step, int n_steps,
+                                          int32_t seed, float rho, int64_t block_id_base,
+                                          int32_t* out_idx, float* out_sample, void* workspace,
+                                          size_t workspace_bytes, const cwq_options* opts,
+                                          void* stream, int guess_mode) {
+  if (d < 0) return fail(CWQ_ERR_INVALID, "d must be >= 0");
+  if (nb < 0 || (d > 0 && nb > INT64_MAX / d)) return fail(CWQ_ERR_INVALID, "bad nb");
+  if (guess_mode < 0 || guess_mode > 2)
+    return fail(CWQ_ERR_INVALID, "guess_mode=%d outside [0, 2]", guess_mode);
+  return encode_impl(t_loc, t_scale, p_loc, p_scale, nullptr, d, nb, nb * d, d, n_bits_per_step,
+                     n_steps, seed, rho, block_id_base, out_idx, out_sample, workspace,
+                     workspace_bytes, opts, stream, nullptr, nullptr, nullptr, nullptr,
+                     /*rows_wave=*/false, guess_mode);
 }
 
 namespace {

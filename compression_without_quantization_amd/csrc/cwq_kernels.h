@@ -33,6 +33,7 @@ struct EncodeArgs {
   int64_t cand_per_tile;     // multiple of 256
   int n_steps;
   int prune;                 // 1: use the pruned kernel where it applies
+  int tau_guess = -1;        // k_encode_prune's tau guess: -1 = on where prune >= 2; 0, 1, 2
   int32_t seed;
   float rho;
   int64_t block_id_base;

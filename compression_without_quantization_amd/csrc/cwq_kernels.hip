@@ -24,6 +24,7 @@
 #include "cwq_device.h"
 #include "cwq_kernels.h"
 #include "cwq_refill.h"
+#include "cwq_tau_guess.h"
 
 namespace cwq {
 
@@ -268,7 +269,8 @@ __device__ unsigned int g_tile_wg[kTileTimes];
 #ifdef CWQ_PRUNE_STATS
 // tuning builds only (tools/prune_stats.py): [0..64] candidates finished after
 // k units, [65] completed rows, [66] survivors pushed, [67] screened tiles,
-// [70] wave-iterations that took the pool refill, [71] wave-iterations;
+// [70] wave-iterations that took the pool refill, [71] wave-iterations,
+// [50] tiles started from a tau guess, [51] tiles run again without it;
 // general kernel (tools/csr_stats.py): [40]/[41] screened/exact tiles, [42] rows
 // finished, [43] dims screened, [44] rows completed, [45] survivors pushed,
 // [46] list-full exact rows, [47] survivors re-evaluated, [48] lane-iterations
@@ -279,6 +281,37 @@ constexpr int kDbgBlocks = 1 << 20;
 __device__ unsigned long long g_dbg_best[kDbgBlocks];
 __device__ int g_seed_tau;
 #endif
+
+// cwq_tau_guess.h's Dims on the device: a dim per lane (w = b2 = 0 in the
+// other lanes), summed by a butterfly that leaves the same bits in every lane.
+// Full exec mask.
+struct TauGuessWaveDims {
+  float w, b2;
+  int d;
+  __device__ __forceinline__ int count() const { return d; }
+  template <class F>
+  __device__ __forceinline__ cwq::TauGuessSums sum(F f) const {
+    cwq::TauGuessSums o = f(w, b2);
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) {
+      o.k += __shfl_xor(o.k, sh, 64);
+      o.k1 += __shfl_xor(o.k1, sh, 64);
+      o.k2 += __shfl_xor(o.k2, sh, 64);
+    }
+    return o;
+  }
+};
+// qm_cell's test value (allow_screen bits 1-2 == 2): tau_g = FLT_MAX, which no
+// row reaches, so every screened tile takes the retry
+constexpr float kTauForceRetry = -2.0f;
+// tau_g from the cell: the lower bound of a completed row whose screened sum
+// is -q_m; -inf without a guess (never NaN)
+__device__ __forceinline__ float tau_guess_of(float qm, float As, float Pq) {
+  if (qm == kTauForceRetry) return 3.402823466e+38f;
+  if (!(qm >= 0.0f)) return -__builtin_inff();
+  const float tg = cwq::screen_row_lower(-qm, cwq::kScreenC2, As, Pq);
+  return tg == tg ? tg : -__builtin_inff();
+}
 
 template <int D, bool STEP0, bool INTER>
 __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
@@ -307,6 +340,8 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
   __shared__ float lowc;             // L: lower-end constant of a completed row
   __shared__ float scr_a, scr_pq;    // screening: As, Pq
   __shared__ float tau_cell;         // the workgroup's tau (a float, never NaN: LDS float max)
+  __shared__ float tau_seed_cell;    // what the tile really starts from: -inf or keys[g]'s value
+  __shared__ float qm_cell;          // tau guess: q_m, kTauNoGuess or kTauForceRetry (tau_guess_of)
   __shared__ uint32_t sq_cnt;
   __shared__ uint32_t sq_n[CWQ_SURVIVOR_CAP];
   __shared__ float sq_ub[CWQ_SURVIVOR_CAP];
@@ -446,7 +481,27 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     const bool scr_all = __syncthreads_and(scr_ok) != 0;
     // (e) drop bounds: thread k computes B_k for the first k visited groups
     //     (exact or screening form); thread G + 1 the screening constants
-    const bool screen = allow_screen && scr_all;
+    const bool screen = (allow_screen & 1) && scr_all;
+    // tau guess (cwq_tau_guess.h): while wave 0 sums the bounds below, wave 1
+    // solves for q_m, a dim per lane, from the records (d) has just written
+    if (wv == 1u) {
+      const int gmode = (allow_screen >> 1) & 3;
+      float qm = cwq::kTauNoGuess;
+      if (screen && gmode == 1) {
+        float w = 0.0f, b2 = 0.0f;
+        if (lane < (uint32_t)D) {
+          const float* sc = reinterpret_cast<const float*>(&vrec[lane >> 2]);
+          const float al = sc[lane & 3u] * (float)(1.0 / cwq::kSqrt2Ln2);
+          const float be = sc[4u + (lane & 3u)];
+          w = al * al;
+          b2 = be * be;
+        }
+        qm = cwq::tau_guess_q(TauGuessWaveDims{w, b2, D}, n1 - n0, cwq::kTauGuessM);
+      } else if (screen && gmode == 2) {
+        qm = kTauForceRetry;
+      }
+      if (lane == 0) qm_cell = qm;
+    }
     if (tid <= G + 1) {
       const int kb = tid;
       const float* c = reinterpret_cast<const float*>(cst);
@@ -499,6 +554,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           t0 = unord_f32((uint32_t)(g_dbg_best[g] >> 32));
 #endif
         tau_cell = t0;
+        tau_seed_cell = t0;
         sq_cnt = 0u;
       }
     }
@@ -559,10 +615,19 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
 #endif
     // tau is wave-uniform from here to the end of the tile: it starts so, and
     // the keep branch and the share below both leave the same value in every lane
+    //
+    // Tau guess.  The screening pass starts tau at the larger of the tile's
+    // real start (-inf, or the keys[g] value in INTER: the seed) and tau_g,
+    // the lower bound of a row at the predicted level q_m; it is not written to
+    // the cell, which the first share raises.  tau_g is no row's bound, so the
+    // arguments at the drop tests below hold only once a real row has passed
+    // it, which is checked after the pass: see "the guess held" there.
     float tau = (INTER && CWQ_TAU_FROM_KEYS) ? tau_cell : -__builtin_inff();
 #ifdef CWQ_PRUNE_STATS
     tau = tau_seed;
+    if (tid == 0 && qm_cell >= 0.0f) atomicAdd(&g_prune_stats[50], 1ull);
 #endif
+    tau = max_f32_quiet(tau, tau_guess_of(qm_cell, sA, sPq));
     uint64_t bestk = 0;
 
     const PhiloxLo lok = philox_lo_key(st);  // block indices < 2^32 (launch_prune_t)
@@ -666,8 +731,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // is finite with |z'| < 5 for every Philox word (u1 is clamped to
         // [1e-7, 1], sin and cos take an angle in [1, 2)), so |a| < 2^54 and s,
         // a sum of at most 64 terms -a^2, is finite; B_k is finite or +inf,
-        // never NaN (round_up_f32).  tau starts at -inf or at a clamped key's
-        // value and only ever takes a max with a lower bound that is not NaN
+        // never NaN (round_up_f32).  tau starts at -inf, at a clamped key's
+        // value or at tau_g (tau_guess_of: never NaN) and only ever takes a
+        // max with a lower bound that is not NaN
         // (tau_raise_wave leaves a NaN out) or with the workgroup's cell, which
         // holds such values only.  The exact pass, whose s may be NaN, keeps
         // both compares: a NaN row is neither dropped early nor kept.
@@ -786,15 +852,54 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
 #ifdef CWQ_PRUNE_STATS
     if (screen && tid == 0) atomicAdd(&g_prune_stats[67], 1ull);
 #endif
-    if (screen)
-      pass(std::true_type{});
-    else
+    // The pass, and once more with the guess off where the guess did not hold
+    // (one loop around the one inlined screening pass; the branch is taken by
+    // the whole workgroup on values read from LDS, made scalar).
+    //
+    // The guess held iff tau_final > tau_g or seed >= tau_g.  Then tau_final
+    // is a lower bound of a real row's exact value (a completed row of this
+    // tile, or the row behind keys[g]): only such bounds and tau_g enter the
+    // maxima that make it, and it exceeds tau_g (or the seed alone is one).
+    // Every drop of the pass was taken against a tau <= tau_final (tau only
+    // rises, and the final share puts every wave's tau into the cell), so a
+    // dropped row's exact value is below that of a real row: it is neither
+    // the argmax nor a tie.  A row whose exact value equals the best row's
+    // has upper >= that value >= tau_final >= every tau of the pass, so it
+    // was kept and its upper end reaches tau_final below.  If the guess did
+    // not hold, rows may have been dropped against a tau no real row backs:
+    // the survivor list and the cell are reset to the seed and the pass runs
+    // again from there, as it would have without a guess.  bestk keeps the
+    // exact keys it has (list-full rows): they belong to real rows.
+    float tau_final;
+    if (screen) {
+      for (;;) {
+        pass(std::true_type{});
+        tau_share_wave(&tau_cell, tau);
+        __syncthreads();
+        tau_final = tau_cell;
+        const float tg = tau_guess_of(qm_cell, sA, sPq);
+        const float seed = INTER ? tau_seed_cell : -__builtin_inff();
+        const bool held = tau_final > tg || seed >= tg;
+        if (__builtin_amdgcn_readfirstlane(held ? 1 : 0) != 0) break;
+        __syncthreads();  // every thread has read the cells
+        if (tid == 0) {
+          tau_cell = seed;
+          sq_cnt = 0u;
+          qm_cell = cwq::kTauNoGuess;
+#ifdef CWQ_PRUNE_STATS
+          atomicAdd(&g_prune_stats[51], 1ull);
+#endif
+        }
+        __syncthreads();
+        tau = (INTER && CWQ_TAU_FROM_KEYS) ? seed : -__builtin_inff();
+      }
+    } else {  // the exact pass takes no guess (qm_cell: kTauNoGuess)
       pass(std::false_type{});
-
+      tau_share_wave(&tau_cell, tau);
+      __syncthreads();
+      tau_final = tau_cell;
+    }
     // exact evaluation of the survivors that can still reach the final tau
-    tau_share_wave(&tau_cell, tau);
-    __syncthreads();
-    const float tau_final = tau_cell;
     const uint32_t nsurv = sq_cnt < CWQ_SURVIVOR_CAP ? sq_cnt : CWQ_SURVIVOR_CAP;
     // A wave takes the list 64 entries at a time, packs those that reach
     // tau_final to the front of its 64 (in place: every lane has read its
@@ -3380,6 +3485,14 @@ static void launch_eval_t(const EncodeArgs& a, int step, hipStream_t stream) {
                      step, a.keys);
 }
 
+// k_encode_prune's allow_screen: bit 0 the screening pass, bits 1-2 the tau
+// guess (0 off, 1 on, 2 every screened tile retried: tests)
+static int prune_screen_arg(const EncodeArgs& a) {
+  const int scr = a.prune >= 2 ? 1 : 0;
+  const int gm = a.tau_guess >= 0 ? (a.tau_guess & 3) : scr;
+  return scr | (gm << 1);
+}
+
 template <int D, bool STEP0>
 static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
   // grid of 256 CUs x 6 resident workgroups x 256; each workgroup loops over
@@ -3421,7 +3534,7 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                        dim3((unsigned)(nt_s < kPruneGrid ? nt_s : kPruneGrid)), dim3(256), 0,
                        stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                        nt_s, seed_n / cpt_s, cpt_s, seed_n, seeds_of(a), step,
-                       a.prune >= 2 ? 1 : 0, a.keys, seed_n / cpt_s, 1, nullptr);
+                       prune_screen_arg(a), a.keys, seed_n / cpt_s, 1, nullptr);
   }
   // tile queue (k_encode_prune): a persistent grid of CWQ_QUEUE_GRID workgroups
   // draws tiles from a counter in the workspace, zeroed here before the launch
@@ -3466,12 +3579,12 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                        dim3(qgrid(nt2)), dim3(256), 0,
                        stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                        nt2, tpb2, a.cand_per_tile, a.n_cand, seeds_of(a), step,
-                       a.prune >= 2 ? 1 : 0, a.keys, from, (int)div, tq);
+                       prune_screen_arg(a), a.keys, from, (int)div, tq);
   } else {
     hipLaunchKernelGGL((k_encode_prune<D, STEP0, false>), dim3(qgrid(ntiles)), dim3(256), 0,
                        stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                        ntiles, a.tiles_per_block, a.cand_per_tile, a.n_cand, seeds_of(a), step,
-                       a.prune >= 2 ? 1 : 0, a.keys, a.tiles_per_block, 1, tq);
+                       prune_screen_arg(a), a.keys, a.tiles_per_block, 1, tq);
   }
 }
 

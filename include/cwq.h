@@ -107,8 +107,10 @@ extern "C" {
  *   0.12 backfitting: cwq_greedy_backfit and its workspace size (no decoder
  *        change);
  *   0.13 backfitting under per-block bit budgets: cwq_greedy_backfit_var (no
- *        new size function, no decoder change). */
-#define CWQ_ABI_VERSION ((0 << 16) | 13)
+ *        new size function, no decoder change);
+ *   0.14 cwq_selftest_encode_uniform_tau_guess (the pruned uniform encoder
+ *        starts its threshold from a predicted level; same results). */
+#define CWQ_ABI_VERSION ((0 << 16) | 14)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -658,6 +660,21 @@ int cwq_selftest_encode_rows_wave(const float* t_loc, const float* t_scale, cons
                                   int n_steps, int32_t seed, float rho, int64_t block_id_base,
                                   int32_t* out_idx, float* out_sample, void* workspace,
                                   size_t workspace_bytes, void* stream);
+/* cwq_greedy_encode_uniform (same arguments, validation, workspace and
+ * results) with the pruned kernel's tau guess set by guess_mode instead of by
+ * opts->prune_mode: 0 = off (the threshold of a tile starts at -inf or at the
+ * block's best so far), 1 = on (it starts at the lower bound of a row at the
+ * level that CWQ_TAU_GUESS_M of the tile's candidates are expected to fall
+ * below; the default where prune_mode is 2), 2 = every screened tile's guess
+ * replaced by FLT_MAX, so that each is run again without it.  The guess only
+ * has an effect where the screening pass runs (prune_mode 2). */
+int cwq_selftest_encode_uniform_tau_guess(const float* t_loc, const float* t_scale,
+                                          const float* p_loc, const float* p_scale, int64_t nb,
+                                          int64_t d, int n_bits_per_step, int n_steps,
+                                          int32_t seed, float rho, int64_t block_id_base,
+                                          int32_t* out_idx, float* out_sample, void* workspace,
+                                          size_t workspace_bytes, const cwq_options* opts,
+                                          void* stream, int guess_mode);
 
 /* ---- Beam search over the greedy coder's steps (csrc/cwq_beam.hip) --------
  * cwq_greedy_encode keeps the one best partial sum after each step; this
