@@ -7,7 +7,8 @@ computed by the gfx950 kernels in libcwq.so (see include/cwq.h).
 from .backfit import (backfit_blocks, backfit_blocks_var, code_grouped_greedy_sample_backfit,
                       code_grouped_greedy_sample_var_backfit, encode_blocks_backfit,
                       encode_blocks_var_backfit)
-from .beam import code_grouped_greedy_sample_beam, encode_blocks_beam
+from .beam import (code_grouped_greedy_sample_beam, code_grouped_greedy_sample_var_beam,
+                   encode_blocks_beam, encode_blocks_var_beam)
 from .binary_io import (bitcode_to_indices, elias_delta_code, elias_delta_decode,
                         elias_delta_code_many, elias_delta_decode_many,
                         from_bit_string, indices_to_bitcode, read_bin_code, to_bit_string,
@@ -51,6 +52,7 @@ __all__ = [
     "block_bits", "encode_blocks_var", "decode_blocks_var", "pack_indices", "unpack_indices",
     "code_grouped_greedy_sample_var", "decode_grouped_greedy_sample_var",
     "encode_blocks_beam", "code_grouped_greedy_sample_beam",
+    "encode_blocks_var_beam", "code_grouped_greedy_sample_var_beam",
     "backfit_blocks", "encode_blocks_backfit", "code_grouped_greedy_sample_backfit",
     "backfit_blocks_var", "encode_blocks_var_backfit", "code_grouped_greedy_sample_var_backfit",
 ]

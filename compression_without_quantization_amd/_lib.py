@@ -150,6 +150,12 @@ SIGNATURES = {
     "cwq_selftest_beam_encode": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
                                          c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp,
                                          c_size, c_opts, c_vp, c_int]),
+    "cwq_beam_encode_var": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int,
+                                    c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                    c_size, c_opts, c_vp]),
+    "cwq_selftest_beam_encode_var": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                             c_vp, c_int, c_int, c_int, c_i32, c_f32, c_i64, c_vp,
+                                             c_vp, c_vp, c_vp, c_size, c_opts, c_vp, c_int]),
     "cwq_greedy_backfit_workspace_size": (c_size, [c_i64, c_i64, c_i64, c_int]),
     "cwq_greedy_backfit": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int,
                                    c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_size,
@@ -174,7 +180,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 14
+ABI_VERSION = (0 << 16) | 15
 
 _lib = None
 

@@ -19,7 +19,7 @@ and with a bit budget per block (cwq_greedy_backfit_var: block g is refined as
 backfit_blocks refines it at ``n_bits[g]``, all blocks in one call):
 
   backfit_blocks_var                      refine encode_blocks_var's table
-  encode_blocks_var_backfit               encode_blocks_var, then refine
+  encode_blocks_var_backfit               encode_blocks_var (or a beam), then refine
   code_grouped_greedy_sample_var_backfit  code_grouped_greedy_sample_var, refined
 
 All arithmetic runs in libcwq.so; nothing here computes samples on the CPU.
@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .beam import _code_grouped_with, encode_blocks_beam
+from .beam import _code_grouped_with, encode_blocks_beam, encode_blocks_var_beam
 from .coded_greedy_sampler import _device_of, _f32, _ptr, encode_blocks
 from .varbits import (_bits_tensor, _code_grouped_var_with, _nb_of, _offsets, _one_of, _seed32,
                       encode_blocks_var)
@@ -232,14 +232,20 @@ def backfit_blocks_var(idx, t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, see
 
 def encode_blocks_var_backfit(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, sweeps,
                               rho=1., block_dim=None, block_off=None, block_id_base=0,
-                              return_value=False, return_accepted=False, prune_mode=None):
-    """encode_blocks_var, then ``sweeps`` backfitting sweeps over its table.
-    Returns what backfit_blocks_var returns; with ``sweeps=0`` that is
-    encode_blocks_var's own result."""
+                              return_value=False, return_accepted=False, prune_mode=None, beam=1):
+    """encode_blocks_var (``beam=1``) or encode_blocks_var_beam (``beam > 1``),
+    then ``sweeps`` backfitting sweeps over its table.  Returns what
+    backfit_blocks_var returns; with ``sweeps=0`` that is the encoder's own
+    result."""
     _one_of(block_dim, block_off)
     kw = dict(rho=rho, block_dim=block_dim, block_off=block_off, block_id_base=block_id_base,
               prune_mode=prune_mode)
-    idx, _ = encode_blocks_var(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, **kw)
+    if int(beam) > 1:
+        idx, _ = encode_blocks_var_beam(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed,
+                                        beam, rho=rho, block_dim=block_dim, block_off=block_off,
+                                        block_id_base=block_id_base)
+    else:
+        idx, _ = encode_blocks_var(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, **kw)
     return backfit_blocks_var(idx, t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, sweeps,
                               return_value=return_value, return_accepted=return_accepted, **kw)
 
@@ -247,20 +253,22 @@ def encode_blocks_var_backfit(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, s
 def code_grouped_greedy_sample_var_backfit(target, proposal, n_steps, n_bits_per_step, seed,
                                            sweeps, max_group_size_bits=12, rho=1.,
                                            extra_bits=1.0 / math.log(2.0), min_bits=0,
-                                           prune_mode=None):
+                                           prune_mode=None, beam=1):
     """code_grouped_greedy_sample_var with ``sweeps`` backfitting sweeps per
-    group, each group at its own budget.
+    group (after a beam of ``beam`` partial sums when ``beam > 1``), each group
+    at its own budget.
 
     The standardisation, the per-dim KL, the partition and the budgets are
     those of code_grouped_greedy_sample_var; group g is coded with seed ``seed
     + g`` on the standard proposal by encode_blocks_var_backfit.  Returns the
     5-tuple of code_grouped_greedy_sample_var (sample, code bytes, total_bits,
-    group starts, group_bits), which ``sweeps=0`` reproduces byte for byte;
-    the budgets, hence total_bits, do not depend on ``sweeps``, and
+    group starts, group_bits), which ``sweeps=0, beam=1`` reproduces byte for
+    byte; the budgets, hence total_bits, depend on neither, and
     decode_grouped_greedy_sample_var decodes the result.
     """
     def encode(t_loc, t_scale, zeros, ones, bits, starts):
         return encode_blocks_var_backfit(t_loc, t_scale, zeros, ones, bits, n_steps, seed, sweeps,
-                                         rho=rho, block_off=starts, prune_mode=prune_mode)
+                                         rho=rho, block_off=starts, prune_mode=prune_mode,
+                                         beam=beam)
     return _code_grouped_var_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
                                   max_group_size_bits, extra_bits, min_bits)

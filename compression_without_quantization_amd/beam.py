@@ -13,15 +13,25 @@ block by block; ``beam=1`` is the greedy coder bit for bit.
   encode_blocks_beam               encode_blocks with a beam
   code_grouped_greedy_sample_beam  code_grouped_greedy_sample with a beam
 
+and with a bit budget per block (cwq_beam_encode_var: block g is coded as
+encode_blocks_beam codes it at ``n_bits[g]``, all blocks in one launch
+sequence, no sort and no wait):
+
+  encode_blocks_var_beam               encode_blocks_var with a beam
+  code_grouped_greedy_sample_var_beam  code_grouped_greedy_sample_var with a beam
+
 All arithmetic runs in libcwq.so; nothing here computes samples on the CPU.
 """
+import math
+
 import numpy as np
 import torch
 
 from . import _lib
 from .binary_io import indices_to_bitcode
 from .coded_greedy_sampler import _device_of, _dist_parts, _f32, _group_starts_array, _ptr
-from .varbits import _nb_of, _offsets, _one_of, _seed32
+from .varbits import (MAX_BITS, _bits_tensor, _code_grouped_var_with, _nb_of, _offsets, _one_of,
+                      _seed32)
 
 MAX_BEAM = 16  # CWQ_MAX_BEAM
 
@@ -136,3 +146,100 @@ def code_grouped_greedy_sample_beam(target, proposal, n_steps, n_bits_per_step, 
                                   beam, rho=rho, block_off=starts)
     return _code_grouped_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
                               max_group_size_bits)
+
+
+# ---------------------------------------------------------------------------
+# a bit budget per block
+# ---------------------------------------------------------------------------
+def encode_blocks_var_beam(t_loc, t_scale, p_loc, p_scale, n_bits, n_steps, seed, beam, rho=1.,
+                           block_dim=None, block_off=None, block_id_base=0, return_value=False,
+                           workspace=None, eval_events=None, max_bits=None, check=True,
+                           _path=None):
+    """encode_blocks_beam with a bit count per block: block g is coded exactly
+    as ``encode_blocks_beam(..., n_bits[g], ...)`` codes it in a call of its own
+    (seed ``seed + block_id_base + g``), all blocks in one launch sequence.
+    ``n_bits``: int tensor, array or list of nb counts in [0, 30];
+    ``beam * 2**max(n_bits) <= 2**31``.  Returns what encode_blocks_beam
+    returns; row g of the indices lies in ``[0, 2**n_bits[g])``, the table
+    decode_blocks_var, pack_indices and backfit_blocks_var read.  ``beam=1`` is
+    encode_blocks_var bit for bit.
+
+    ``check=True`` reads the counts' smallest and largest (one wait for the
+    device) and raises ValueError for a count outside [0, 30] or above a given
+    ``max_bits``; without ``max_bits`` the largest count is taken.  With
+    ``check=False`` ``max_bits`` is required, nothing waits, and a count outside
+    ``[0, max_bits]`` is read as clamped to it (cwq_beam_encode_var): pass a
+    ``workspace`` (beam_workspace_bytes) as well and the call can be captured
+    into a graph.
+    """
+    lib = _lib.load()
+    _one_of(block_dim, block_off)
+    dev = _device_of(t_loc, t_scale, p_loc, p_scale)
+    tl = _f32(t_loc, dev, "t_loc")
+    ts = _f32(t_scale, dev, "t_scale")
+    pl = _f32(p_loc, dev, "p_loc")
+    ps = _f32(p_scale, dev, "p_scale")
+    D = tl.numel()
+    if not (ts.numel() == pl.numel() == ps.numel() == D):
+        raise ValueError("t_loc, t_scale, p_loc, p_scale must have the same size")
+    if block_off is not None:
+        offs, nb, longest = _offsets(block_off, D, dev)
+    else:
+        longest, nb = _nb_of(D, block_dim)
+        offs = None
+    bits = _bits_tensor(n_bits, nb, dev)
+    if max_bits is not None:
+        max_bits = int(max_bits)
+        if not 0 <= max_bits <= MAX_BITS:
+            raise ValueError(f"max_bits={max_bits} outside [0, {MAX_BITS}]")
+    if check:
+        lo, hi = (int(v) for v in torch.aminmax(bits)) if nb else (0, 0)
+        top = MAX_BITS if max_bits is None else max_bits
+        if lo < 0 or hi > top:
+            raise ValueError(f"n_bits holds a count outside [0, {top}]")
+        if max_bits is None:
+            max_bits = hi
+    elif max_bits is None:
+        raise ValueError("check=False needs max_bits, the bound the counts are read under")
+    n_steps, beam = int(n_steps), int(beam)
+    out_idx = torch.empty((nb, max(n_steps, 0)), dtype=torch.int32, device=dev)
+    out_sample = torch.empty(D, dtype=torch.float32, device=dev)
+    out_value = torch.empty(nb, dtype=torch.float32, device=dev) if return_value else None
+    if workspace is None:
+        need = beam_workspace_bytes(nb, D, longest, n_steps, beam)
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    opts = _lib.options(None, eval_events)
+    args = (_ptr(tl), _ptr(ts), _ptr(pl), _ptr(ps), offs.data_ptr() if offs is not None else None,
+            nb, D, longest, _ptr(bits), max_bits, n_steps, beam, _seed32(seed), float(rho),
+            int(block_id_base), _ptr(out_idx), _ptr(out_sample), _ptr(out_value),
+            workspace.data_ptr(), workspace.numel(), opts)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if _path is None:
+            rc = lib.cwq_beam_encode_var(*args, stream)
+        else:  # the tests' kernel and tiling choice
+            rc = lib.cwq_selftest_beam_encode_var(*args, stream, int(_path))
+    _lib.check(rc, "cwq_beam_encode_var")
+    return (out_idx, out_sample, out_value) if return_value else (out_idx, out_sample)
+
+
+def code_grouped_greedy_sample_var_beam(target, proposal, n_steps, n_bits_per_step, seed, beam,
+                                        max_group_size_bits=12, rho=1.,
+                                        extra_bits=1.0 / math.log(2.0), min_bits=0):
+    """code_grouped_greedy_sample_var with a beam of ``beam`` partial sums per
+    group, each group at its own budget.
+
+    The standardisation, the per-dim KL, the partition and the budgets are
+    those of code_grouped_greedy_sample_var; group g is coded with seed ``seed
+    + g`` on the standard proposal by encode_blocks_var_beam with ``max_bits =
+    n_bits_per_step`` (the budgets' own upper clamp).  Returns the 5-tuple of
+    code_grouped_greedy_sample_var (sample, code bytes, total_bits, group
+    starts, group_bits), which ``beam=1`` reproduces byte for byte; the budgets,
+    hence total_bits, do not depend on ``beam``, and
+    decode_grouped_greedy_sample_var decodes the result.
+    """
+    def encode(t_loc, t_scale, zeros, ones, bits, starts):
+        return encode_blocks_var_beam(t_loc, t_scale, zeros, ones, bits, n_steps, seed, beam,
+                                      rho=rho, block_off=starts, max_bits=n_bits_per_step)
+    return _code_grouped_var_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
+                                  max_group_size_bits, extra_bits, min_bits)

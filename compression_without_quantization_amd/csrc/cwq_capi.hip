@@ -2955,7 +2955,11 @@ int beam_impl(const float* t_loc, const float* t_scale, const float* p_loc, cons
               const int64_t* block_off, int64_t nb, int64_t total_dims, int64_t max_block_dim,
               int n_bits, int n_steps, int beam, int32_t seed, float rho, int64_t block_id_base,
               int32_t* out_idx, float* out_sample, float* out_value, void* workspace,
-              size_t workspace_bytes, const cwq_options* opts, void* stream, int path) {
+              size_t workspace_bytes, const cwq_options* opts, void* stream, int path,
+              const int32_t* n_bits_dev = nullptr, bool var = false) {
+  // var (cwq_beam_encode_var): n_bits is max_bits, the bound on n_bits_dev's counts
+  if (var && (n_bits < 0 || n_bits > CWQ_MAX_BITS_PER_STEP))
+    return fail(CWQ_ERR_INVALID, "max_bits=%d outside [0, %d]", n_bits, CWQ_MAX_BITS_PER_STEP);
   int rc = check_common(n_bits, n_steps, nb);
   if (rc) return rc;
   cwq_options o;
@@ -2963,8 +2967,9 @@ int beam_impl(const float* t_loc, const float* t_scale, const float* p_loc, cons
   if (beam < 1 || beam > CWQ_MAX_BEAM)
     return fail(CWQ_ERR_INVALID, "beam=%d outside [1, %d]", beam, CWQ_MAX_BEAM);
   if (((int64_t)beam << n_bits) > (1LL << 31))
-    return fail(CWQ_ERR_INVALID, "beam * 2^n_bits_per_step = %lld exceeds 2^31",
-                (long long)((int64_t)beam << n_bits));
+    return fail(CWQ_ERR_INVALID, "beam * 2^%s = %lld exceeds 2^31",
+                var ? "max_bits" : "n_bits_per_step", (long long)((int64_t)beam << n_bits));
+  if (var && nb > 0 && !n_bits_dev) return fail(CWQ_ERR_INVALID, "n_bits is null");
   if (total_dims < 0 || max_block_dim < 0)
     return fail(CWQ_ERR_INVALID, "total_dims and max_block_dim must be >= 0");
   if (path < -1 || path > 3) return fail(CWQ_ERR_INVALID, "path=%d outside [0, 3]", path);
@@ -3005,8 +3010,9 @@ int beam_impl(const float* t_loc, const float* t_scale, const float* p_loc, cons
   a.path = path < 0 ? plan
                     : ((path & 1) ? cwq::BeamPath::WavePerRow : cwq::BeamPath::LanePerRow);
   a.quarter_tiles = path >= 2;
+  a.n_bits_dev = var ? n_bits_dev : nullptr;
   hipError_t e = cwq::launch_beam_encode(a, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "cwq_beam_encode");
+  if (e != hipSuccess) return hip_fail(e, var ? "cwq_beam_encode_var" : "cwq_beam_encode");
   return ok();
 }
 }  // namespace
@@ -3041,6 +3047,31 @@ int cwq_selftest_beam_encode(const float* t_loc, const float* t_scale, const flo
   return beam_impl(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims, max_block_dim,
                    n_bits_per_step, n_steps, beam, seed, rho, block_id_base, out_idx, out_sample,
                    out_value, workspace, workspace_bytes, opts, stream, path);
+}
+
+int cwq_beam_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                        const float* p_scale, const int64_t* block_off, int64_t nb,
+                        int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                        int max_bits, int n_steps, int beam, int32_t seed, float rho,
+                        int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                        float* out_value, void* workspace, size_t workspace_bytes,
+                        const cwq_options* opts, void* stream) {
+  return beam_impl(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims, max_block_dim,
+                   max_bits, n_steps, beam, seed, rho, block_id_base, out_idx, out_sample,
+                   out_value, workspace, workspace_bytes, opts, stream, -1, n_bits, true);
+}
+
+int cwq_selftest_beam_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                                 const float* p_scale, const int64_t* block_off, int64_t nb,
+                                 int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                                 int max_bits, int n_steps, int beam, int32_t seed, float rho,
+                                 int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                                 float* out_value, void* workspace, size_t workspace_bytes,
+                                 const cwq_options* opts, void* stream, int path) {
+  if (path < 0) return fail(CWQ_ERR_INVALID, "path=%d outside [0, 3]", path);
+  return beam_impl(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims, max_block_dim,
+                   max_bits, n_steps, beam, seed, rho, block_id_base, out_idx, out_sample,
+                   out_value, workspace, workspace_bytes, opts, stream, path, n_bits, true);
 }
 
 size_t cwq_greedy_backfit_workspace_size(int64_t nb, int64_t total_dims, int64_t max_block_dim,

@@ -300,6 +300,10 @@ struct BeamArgs {
   void* ev_stop;
   BeamPath path;
   bool quarter_tiles;  // tests: tiles a quarter of the size (same results)
+  // cwq_beam_encode_var: the blocks' bit counts, device [nb];
+  // n_bits is then max_bits, the bound the counts are read as clamped to.
+  // nullptr: every block at n_bits.
+  const int32_t* n_bits_dev = nullptr;
 };
 hipError_t launch_beam_encode(const BeamArgs& a, hipStream_t stream);
 

@@ -463,6 +463,13 @@ inline DecWs dec_ws(int64_t D, int64_t G, bool slots, size_t idx_bytes_per_group
 //   tiles   [nb][beam_tiles_cap(nb)][beam] u64: every tile's largest keys
 //   sel     [nb][n_steps][beam] u64: the selected keys, sorted; key j of a step
 //           names beam j's parent and row (candidate parent * 2^b + row)
+// cwq_beam_encode_var takes this layout as it is: the size does
+// not depend on the bit counts, and there is no layout or size function of its
+// own.  It addresses `tiles` as [nb][stride][beam] with stride =
+// beam_tiles_per_block at 2^max_bits <= beam_tiles_cap(nb) (the rule is
+// monotone in the candidate count); block g uses the first tpb[b_g] of its
+// slots.  Slots [L'_g, beam) of a block's beams are never read later, because
+// L_g of the next step is L'_g.
 struct BeamWs {
   Region loc_s, scale_s, lognorm, beams, tiles, sel;
   size_t total;

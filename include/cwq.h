@@ -109,8 +109,11 @@ extern "C" {
  *   0.13 backfitting under per-block bit budgets: cwq_greedy_backfit_var (no
  *        new size function, no decoder change);
  *   0.14 cwq_selftest_encode_uniform_tau_guess (the pruned uniform encoder
- *        starts its threshold from a predicted level; same results). */
-#define CWQ_ABI_VERSION ((0 << 16) | 14)
+ *        starts its threshold from a predicted level; same results);
+ *   0.15 beam search under per-block bit budgets: cwq_beam_encode_var and
+ *        cwq_selftest_beam_encode_var (no new size function, no decoder
+ *        change; cwq_beam_encode's results are unchanged). */
+#define CWQ_ABI_VERSION ((0 << 16) | 15)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -731,6 +734,55 @@ int cwq_selftest_beam_encode(const float* t_loc, const float* t_scale, const flo
                              int64_t block_id_base, int32_t* out_idx, float* out_sample,
                              float* out_value, void* workspace, size_t workspace_bytes,
                              const cwq_options* opts, void* stream, int path);
+
+/* ---- Beam search under per-block bit budgets (csrc/cwq_beam.hip) -----------
+ * cwq_beam_encode with a bit count per block.  Block g is coded exactly as
+ * cwq_beam_encode codes it in a call of its own with n_bits_per_step = b_g and
+ * block seed seed + block_id_base + g (int32 wrap), where
+ *   b_g = clamp(n_bits[g], 0, max_bits),
+ *   L_0 = 1, L_{i+1} = min(beam, L_i 2^b_g), i.e. L_i = min(beam, 2^(b_g i)),
+ *   candidate c = k 2^b_g + r for live beam k and row r < 2^b_g;
+ * the keys, the tie rule, the handling of NaN, values <= -FLT_MAX and -0,
+ * out_idx, out_sample and out_value are those of cwq_beam_encode.  A block at 0
+ * bits has one row per step: indices 0, one beam for ever.  An empty block
+ * gives indices 0 and value +0.  Row g of out_idx lies in [0, 2^b_g): it is the
+ * table cwq_greedy_decode_var, cwq_pack_indices_var and cwq_greedy_backfit_var
+ * read; there is no new decoder and no new format.
+ *   n_bits     device [nb] int32, the blocks' bit counts
+ *   max_bits   the bound on them the caller vouches for: 0 <= max_bits <=
+ *              CWQ_MAX_BITS_PER_STEP and beam * 2^max_bits <= 2^31 (these take
+ *              the place of cwq_beam_encode's checks on n_bits_per_step)
+ * The counts live on the device and the call does not wait for the device, so
+ * it cannot check them: a count outside [0, max_bits] is READ AS CLAMPED to
+ * that range.  This is deterministic and memory-safe (every loop bound and
+ * every index derived from a count uses the clamped value), but such a block's
+ * indices then need the clamped count to decode.  Check the counts first where
+ * they are not known to be in range; the Python binding does.
+ * Every other argument is cwq_beam_encode's.  The workspace is that of
+ * cwq_beam_encode_workspace_size(nb, total_dims, max_block_dim, n_steps,
+ * beam): the size does not depend on the bit counts, the layout is the same,
+ * and there is no size function of its own.  One launch sequence serves every
+ * budget (3 launches per step, one before and one after, whatever the number
+ * of distinct budgets): one stream, no fork, no host synchronisation, no
+ * allocation; capturable into a graph.  nb == 0 returns CWQ_OK without
+ * touching the device.  prune_mode is accepted and ignored; the eval events
+ * bracket the scoring launches. */
+int cwq_beam_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                        const float* p_scale, const int64_t* block_off, int64_t nb,
+                        int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                        int max_bits, int n_steps, int beam, int32_t seed, float rho,
+                        int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                        float* out_value, void* workspace, size_t workspace_bytes,
+                        const cwq_options* opts, void* stream);
+/* The same call with the kernel and tiling forced: paths 0-3 as in
+ * cwq_selftest_beam_encode. */
+int cwq_selftest_beam_encode_var(const float* t_loc, const float* t_scale, const float* p_loc,
+                                 const float* p_scale, const int64_t* block_off, int64_t nb,
+                                 int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
+                                 int max_bits, int n_steps, int beam, int32_t seed, float rho,
+                                 int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                                 float* out_value, void* workspace, size_t workspace_bytes,
+                                 const cwq_options* opts, void* stream, int path);
 
 /* ---- Backfitting for the greedy coder (csrc/cwq_backfit.hip) ---------------
  * Coordinate ascent over the steps of a finished code: it refines any index
