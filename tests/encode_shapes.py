@@ -53,3 +53,86 @@ WS_CSR_LANE = ([5, 12, 100, 72, 33, 0, 255], 12, 2)
 WS_CSR_ALL = CSR_COOP[4][:3]               # cooperative rows, records, the 1,024-dim boundary
 WS_SMALL = {"pipeline": (SMALL_PATH_SIZES["pipeline"], 8, 2),
             "three_kernel": (SMALL_PATH_SIZES["three_kernel"], 8, 2)}
+
+# ---------------------------------------------------------------------------
+# test_near_ties.py / test_near_ties_gpu.py: one case per scoring path of the
+# greedy family, on tests/near_ties.py's inputs.  A block-length list above is
+# repeated until the case has at least 16 non-empty blocks.  Each case:
+#   group       the GPU test that runs it
+#   d           uniform block length, or None: ragged blocks of ``sizes`` dims
+#   bits        bits per step: one count, or one per block (a budget call)
+#   input_seed  near_ties.inputs' seed;  level: its t_scale level
+#   path        the path the case is there for (test_encode_plan.py checks it)
+# and what forces the path: ``prune`` (the prune_modes to run), ``guess`` (the
+# tau-guess selftest's modes), ``oracle_stride`` (the oracle on every n-th
+# block, the whole against prune_mode 0), ``ref_stride`` (the backfitting
+# restatement on every n-th block).
+# ---------------------------------------------------------------------------
+NEAR_TIE_MIN_BLOCKS = 16
+
+
+def _case(group, sizes, bits, n_steps, input_seed, d=None, level=300.0, **how):
+    return dict(group=group, d=d, sizes=list(sizes), bits=bits, n_steps=n_steps,
+                input_seed=input_seed, level=level, **how)
+
+
+def _uni(group, d, bits, nb, n_steps, input_seed, **how):
+    return _case(group, [d] * nb, bits, n_steps, input_seed, d=d, **how)
+
+
+VAR_SHORT_SIZES = SMALL_PATH_SIZES["pipeline"] * 2 + SMALL_PATH_SIZES["three_kernel"]
+# the last block (130 dims) at 8 bits: a bucket on the three-kernel path
+VAR_SHORT_BITS = ([4, 7, 9, 12, 6, 11, 0, 8, 5, 10, 12] * 4)[:len(VAR_SHORT_SIZES) - 1] + [8]
+BACKFIT_LANE = (8, 6, 16384, 3)  # (d, bits, nb, n_steps): a lane per block from 16,384 blocks on
+
+NEAR_TIE_CASES = {
+    # the exact kernel
+    "exact_uniform": _uni("encode", 16, 12, 64, 1, 1, path="eval", prune=(0,)),
+    "exact_ragged": _case("encode", WS_EVAL_RAGGED[0] * 6, WS_EVAL_RAGGED[1], WS_EVAL_RAGGED[2], 5,
+                          level=1000.0, path="eval", prune=(None,)),
+    # k_encode_prune
+    "prune_d8": _uni("encode", 8, 6, 64, 3, 3, path="uniform_pruned", prune=(1, 2)),
+    "prune_d16": _uni("encode", 16, 12, 64, 1, 4, path="uniform_pruned", prune=(1, 2)),
+    "prune_d32": _uni("encode", 32, 12, 64, 1, 5, path="uniform_pruned", prune=(1, 2)),
+    "prune_d64": _uni("encode", 64, 14, 64, 1, 6, path="uniform_pruned", prune=(1, 2)),
+    "tau_guess": _uni("tau_guess", 32, 12, 64, 1, 7, path="uniform_pruned", guess=(0, 1, 2)),
+    "tile_queue": _uni("encode", *WS_TILE_QUEUE, 8, path="uniform_pruned", prune=(None,),
+                       oracle_stride=16),
+    # the general pruned kernel on uniform blocks
+    "general_d5": _uni("encode", 5, 13, 64, 2, 9, path="csr_pruned", prune=(None,)),
+    "general_d100": _uni("encode", 100, 14, 32, 2, 10, path="csr_pruned", prune=(None,)),
+    # k_encode_prune_csr: per-lane rows (forked), cooperative rows and records
+    "csr_lane": _case("encode", WS_CSR_LANE[0] * 3, WS_CSR_LANE[1], WS_CSR_LANE[2], 11,
+                      path="csr_pruned", prune=(0, 2)),
+    "csr_coop": _case("encode", CSR_COOP[4][0] * 2, CSR_COOP[4][1], CSR_COOP[4][2], 12,
+                      path="csr_pruned", prune=(0, 2)),
+    # the small-candidate paths
+    "small_pipe_b8": _case("encode", SMALL_PATH_SIZES["pipeline"] * 4, 8, 2, 13,
+                           path="small_pipe", prune=(None,)),
+    "small_pipe_b11": _case("encode", SMALL_PATH_SIZES["pipeline"] * 4, 11, 1, 14,
+                            path="small_pipe", prune=(None,)),
+    "small_three_b8": _case("encode", SMALL_PATH_SIZES["three_kernel"] * 4, 8, 2, 15,
+                            path="small_three", prune=(None,)),
+    "small_three_b11": _case("encode", SMALL_PATH_SIZES["three_kernel"] * 4, 11, 1, 16,
+                             path="small_three", prune=(None,)),
+    # k_encode_rows_wave, forced
+    "rows_wave_b9": _case("rows_wave", ROWS_WAVE_LENGTHS * 2, 9, 2, 17, path="rows_wave"),
+    "rows_wave_b11": _case("rows_wave", ROWS_WAVE_LENGTHS * 2, 11, 1, 18, path="rows_wave"),
+    # encode_blocks_var: block g at bits[g]
+    "var_uniform": _uni("var", 32, [4 + g % 9 for g in range(64)], 64, 2, 19,
+                        path="uniform_pruned"),
+    "var_long": _case("var", LONG_LENS * 3, LONG_BITS * 3, 2, 20, path="rows_wave"),
+    "var_short": _case("var", VAR_SHORT_SIZES, VAR_SHORT_BITS, 2, 21, path="mixed"),
+    # the beam encoder: blocks of at most 64 dims, so every selftest path takes them
+    "beam": _case("beam", SMALL_PATH_SIZES["pipeline"] * 2, 6, 2, 22, path="beam_lane"),
+    "beam_var": _case("beam_var", VAR_SHORT_SIZES[:26], [min(b, 8) for b in VAR_SHORT_BITS[:26]],
+                      2, 23, path="beam_lane"),
+    # backfitting: a wave per block (short and long ragged blocks), a lane per
+    # block, and under budgets
+    "backfit_short": _case("backfit", SMALL_PATH_SIZES["three_kernel"] * 3, 6, 3, 21,
+                           path="backfit_wave"),
+    "backfit_ragged": _case("backfit", ROWS_WAVE_LENGTHS, 5, 3, 25, path="backfit_wave"),
+    "backfit_lane": _uni("backfit", *BACKFIT_LANE, 26, path="backfit_lane", ref_stride=64),
+    "backfit_var": _case("backfit_var", VAR_SHORT_SIZES, [min(b, 8) for b in VAR_SHORT_BITS], 2,
+                         27, path="backfit_wave"),
+}

@@ -317,3 +317,107 @@ def test_workspace_state_ragged_shapes(mc):
         whole, ranges = csr_paths(mc, sizes, bits, n_steps)
         assert whole[0] == path and whole[2] == (path == SMALL_PIPE) and whole[3] == 3
         assert {r[:3] for r in ranges} == {(path, False, path == SMALL_PIPE)}
+
+
+# ---------------------------------------------------------------------------
+# test_near_ties_gpu.py: each near-tie case takes the path it names
+# ---------------------------------------------------------------------------
+ENCODE_PATHS = {"rows_wave": ROWS_WAVE, "uniform_pruned": UNIFORM_PRUNED, "csr_pruned": CSR_PRUNED,
+                "small_pipe": SMALL_PIPE, "small_three": SMALL_THREE, "eval": EVAL}
+
+
+@pytest.fixture(scope="module")
+def search_plans(tmp_path_factory):
+    """beam_plan and backfit_plan (csrc/cwq_dispatch.h) compiled for the host."""
+    import os
+    import subprocess
+    from conftest import REPO
+    out = []
+    for name in ("beam_plan", "backfit_plan"):
+        so = tmp_path_factory.mktemp(name) / f"lib{name}.so"
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-o", str(so),
+                               os.path.join(REPO, "tests", "native", name + ".cpp")])
+        out.append(ctypes.CDLL(str(so)))
+    out[0].bp_path.argtypes, out[0].bp_path.restype = [I64], ctypes.c_int
+    out[1].bf_path.argtypes, out[1].bf_path.restype = [I64, I64], ctypes.c_int
+    return out
+
+
+def _bucket_plans(mc, c):
+    """A budget call's buckets as cwq_greedy_encode_var and
+    cwq_greedy_encode_uniform_var run them: the blocks of one bit count as a
+    call of their own, with their own longest block; {bits: (path, rows_wave rule)}."""
+    out = {}
+    for b in sorted(set(c["bits"])):
+        mine = [n for n, bb in zip(c["sizes"], c["bits"]) if bb == b]
+        if c["d"] is not None:
+            out[b] = (plan(mc, csr=False, ud=c["d"], bits=b, prune=2, nb=len(mine),
+                           n_steps=c["n_steps"])[0], False)
+        else:
+            rule = bool(mc.mc_bucket_takes_rows_wave(b, sum(mine), len(mine), 2))
+            out[b] = (plan(mc, csr=True, bits=b, prune=2, nb=len(mine), max_d=max(mine),
+                           rows_wave=rule, n_steps=c["n_steps"])[0], rule)
+    return out
+
+
+@pytest.mark.parametrize("name", list(S.NEAR_TIE_CASES))
+def test_near_tie_case_takes_its_path(mc, search_plans, name):
+    c = S.NEAR_TIE_CASES[name]
+    sizes, n_steps, nb = c["sizes"], c["n_steps"], len(c["sizes"])
+    assert sum(1 for n in sizes if n > 0) >= S.NEAR_TIE_MIN_BLOCKS
+    consts = (I64 * 3)()
+    mc.mc_dispatch_consts(consts)
+    coop_min_d, lds = consts[1], consts[2]
+    if c["group"] in ("encode", "tau_guess"):
+        want = ENCODE_PATHS[c["path"]]
+        for prune in c.get("prune", (2,)):
+            p = 2 if prune is None else prune
+            if c["d"] is not None:
+                whole = plan(mc, csr=False, ud=c["d"], bits=c["bits"], prune=p, nb=nb,
+                             n_steps=n_steps)
+                ranges = [whole]
+                assert whole[3] == 1
+            else:
+                whole, ranges = csr_paths(mc, sizes, c["bits"], n_steps, prune=p)
+            # prune_mode 0 is the exact kernel whatever the shape
+            assert {r[0] for r in ranges + [whole]} == {EVAL if p == 0 else want}, (name, prune)
+    if name == "tile_queue":
+        assert (1 << c["bits"]) >= 4096 and nb > 1536 and c["oracle_stride"] == 16
+    elif c["path"] == "uniform_pruned" and c["group"] != "var":
+        assert nb <= 1536  # no tile queue
+    if name == "csr_lane":
+        assert max(sizes) < coop_min_d and 0 in sizes
+        assert csr_paths(mc, sizes, c["bits"], n_steps)[0][3] == 3  # forked
+    if name == "csr_coop":
+        whole, ranges = csr_paths(mc, sizes, c["bits"], n_steps)
+        assert whole[1] and all(r[1] for r in ranges)
+        assert lds in sizes and any(n > lds for n in sizes) and any(n < coop_min_d for n in sizes)
+        assert mc.mc_has_long_block_records(1, max(sizes), nb)
+    if name.startswith("general"):
+        assert mc.mc_has_screen_arrays(0, c["d"], nb)
+    if c["group"] == "rows_wave":  # forced by the selftest entry, in every part
+        whole = plan(mc, csr=True, bits=c["bits"], prune=2, nb=nb, max_d=max(sizes),
+                     rows_wave=True, n_steps=n_steps)
+        assert whole[0] == ROWS_WAVE
+        for n in part_sizes(nb, whole[3]):
+            assert plan(mc, csr=True, bits=c["bits"], prune=2, nb=n, max_d=max(sizes),
+                        rows_wave=True, n_steps=n_steps)[0] == ROWS_WAVE
+        assert 0 in sizes and max(sizes) == 4095
+    if c["group"] == "var":
+        assert len(c["bits"]) == nb
+        buckets = _bucket_plans(mc, c)
+        if c["path"] == "mixed":  # one call, every other path, no long bucket
+            assert not any(rule for _, rule in buckets.values())
+            assert {p for p, _ in buckets.values()} >= {EVAL, SMALL_PIPE, SMALL_THREE, CSR_PRUNED}
+            assert 0 in c["bits"] and 0 in sizes
+        else:
+            assert {p for p, _ in buckets.values()} == {ENCODE_PATHS[c["path"]]}
+            assert len(buckets) >= 4
+        if c["path"] == "rows_wave":
+            assert all(rule for _, rule in buckets.values())
+    beam, backfit = search_plans
+    if c["group"] in ("beam", "beam_var"):
+        assert c["path"] == "beam_lane" and beam.bp_path(max(sizes)) == 0 and max(sizes) == 64
+    if c["group"] in ("backfit", "backfit_var"):
+        assert n_steps >= 2  # a code of one step is returned as given
+        assert backfit.bf_path(max(sizes), nb) == (1 if c["path"] == "backfit_lane" else 0)
