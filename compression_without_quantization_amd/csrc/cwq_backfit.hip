@@ -21,7 +21,7 @@
 //
 // Under per-block bit budgets (cwq_greedy_backfit_var) the blocks
 // arrive sorted by budget and only the scoring differs: one launch sequence per
-// budget bucket on that bucket's slice of the shared arrays (BackfitBucket),
+// budget bucket on that bucket's slice of the shared arrays (BudgetBucket),
 // between the same k_backfit_base and accept launch over all blocks.  None of
 // the kernels here reads a bit count: they read indices and keys.
 #include <hip/hip_runtime.h>
@@ -322,7 +322,7 @@ hipError_t launch_backfit(const BackfitArgs& b, hipStream_t stream) {
   auto score = [&](int s) -> hipError_t {
     if (!b.buckets) return launch_score_step(e, s, stream);
     for (int i = 0; i < b.n_buckets; ++i) {
-      const BackfitBucket& k = b.buckets[i];
+      const BudgetBucket& k = b.buckets[i];
       EncodeArgs p = e;
       p.t_loc = e.t_loc + k.d0;
       p.t_scale = e.t_scale + k.d0;

@@ -1,8 +1,10 @@
 // cwq_capi.hip -- the C ABI declared in include/cwq.h.
 //
-// Thin: validates arguments, carves the caller's workspace, picks the tiling
-// and enqueues the kernels on the caller's stream.  Never allocates, never
-// synchronises, never throws.
+// Validates arguments, carves the caller's workspace, picks the tiling and
+// enqueues the kernels on the caller's stream.  None allocates device memory or
+// throws.  Most only enqueue.  Those that wait for the device: the three budget
+// calls that sort their blocks (once, in sort_blocks), and the grouped coders
+// and decoders and cwq_debug_group_starts_device, which return host results.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -62,22 +64,6 @@ int check_ws(const void* workspace, size_t workspace_bytes, size_t need, NullWs 
   if (workspace_bytes < need || (!workspace && (need || rule == NullWs::Refused)))
     return fail(CWQ_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
   return CWQ_OK;
-}
-
-#ifndef CWQ_TARGET_TILES
-#define CWQ_TARGET_TILES 16384  // tiles per launch the tiling aims for (tuning builds)
-#endif
-void choose_tiling(int64_t nb, int64_t n_cand, int64_t* tiles_per_block, int64_t* cand_per_tile) {
-  const int64_t kTargetTiles = CWQ_TARGET_TILES;
-  int64_t want = nb > 0 ? (kTargetTiles + nb - 1) / nb : 1;
-  int64_t max_split = (n_cand + 255) / 256;  // at least one candidate per lane
-  if (want > max_split) want = max_split;
-  if (want < 1) want = 1;
-  int64_t cpt = (n_cand + want - 1) / want;
-  cpt = (cpt + 255) / 256 * 256;
-  if (cpt < 256) cpt = 256;
-  *cand_per_tile = cpt;
-  *tiles_per_block = (n_cand + cpt - 1) / cpt;
 }
 
 // Eigen 3.3 AVX inner-dim sum order, host side.
@@ -311,7 +297,7 @@ void fill_encode_args(cwq::EncodeArgs& a, const float* t_loc, const float* t_sca
   a.total_dims = total_dims;
   a.max_d = max_d;
   a.n_cand = (int64_t)1 << n_bits;
-  choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
+  cwq::choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
   a.n_steps = n_steps;
   a.prune = o.prune_mode;
   a.seed = seed;
@@ -378,6 +364,93 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
   return ok();
 }
 
+// ---- blocks with a bit budget each: what the three calls share ----------------
+// A bucket's own call takes the options without the eval events: they go around all.
+cwq_options without_events(cwq_options o) {
+  o.eval_start_event = o.eval_stop_event = nullptr;
+  o.eval_ms_out = nullptr;
+  o.item_ready = nullptr;
+  return o;
+}
+
+// What sort_blocks hands back: the sorted view's arrays (SortedWs), the buckets
+// to launch, and the table's entries outside [0, 2^n_bits[g]) (no table: 0).
+struct SortedBlocks {
+  float *t_loc, *t_scale, *p_loc, *p_scale, *sample;
+  int32_t *seeds, *perm;
+  int64_t *soff, *src;  // ragged blocks only
+  cwq::BudgetPlan plan;
+  uint32_t bad_entries;
+};
+
+// A budget call up to its one wait (block_off nullptr: uniform
+// blocks of max_block_dim dims).  Enqueues the sort by budget, the sorted layout
+// and copies of the inputs in[] and, given `table` (backfitting), its rows
+// gathered into table_s, their range check counted in *bad_dev: all of it writes
+// the workspace alone, whatever the values.  Then the one copy-back and the one
+// synchronisation, and the plan or the refusal (cwq_budget_plan.h).
+int sort_blocks(const char* who, const float* const in[4], const int64_t* block_off, int64_t nb,
+                int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits, int n_steps,
+                int32_t seed, int64_t block_id_base, int prune_mode, void* w,
+                const cwq::SortedWs& l, const int32_t* table, int32_t* table_s,
+                uint32_t* bad_dev, hipStream_t st, SortedBlocks* s) {
+  const bool csr = block_off != nullptr;
+  *s = {at<float>(w, l.t_loc),   at<float>(w, l.t_scale), at<float>(w, l.p_loc),
+        at<float>(w, l.p_scale), at<float>(w, l.sample),  at<int32_t>(w, l.seeds),
+        at<int32_t>(w, l.perm),  at<int64_t>(w, l.soff),  at<int64_t>(w, l.src)};
+  uint32_t* counts_dev = at<uint32_t>(w, l.counts);
+  cwq::VbcFacts* facts_dev = at<cwq::VbcFacts>(w, l.facts);
+  int64_t* roff = at<int64_t>(w, l.roff);
+  hipError_t e = cwq::launch_vb_sort(n_bits, nb, s->perm, at<uint32_t>(w, l.hist), counts_dev, st);
+  if (e == hipSuccess && csr) {
+    e = cwq::launch_vbc_layout(n_bits, block_off, s->perm, nb, counts_dev,
+                               at<unsigned long long>(w, l.wgfacts), facts_dev, seed,
+                               block_id_base, s->soff, roff, s->src, s->seeds,
+                               at<int64_t>(w, l.partial), st);
+    if (e == hipSuccess)
+      e = cwq::launch_vbc_gather(in[0], in[1], in[2], in[3], s->soff, s->src, nb, total_dims,
+                                 s->t_loc, s->t_scale, s->p_loc, s->p_scale, st);
+  } else if (e == hipSuccess) {
+    e = cwq::launch_vb_gather(in[0], in[1], in[2], in[3], s->perm, nb, max_block_dim, seed,
+                              block_id_base, s->t_loc, s->t_scale, s->p_loc, s->p_scale, s->seeds,
+                              st);
+  }
+  if (e == hipSuccess && table)
+    e = cwq::launch_vb_gather_table(table, n_bits, s->perm, nb, n_steps, table_s, bad_dev, st);
+  if (e != hipSuccess)
+    return fail(CWQ_ERR_HIP, "%s (sort / gather): %s", who, hipGetErrorString(e));
+  cwq::VbcFacts f;
+  uint32_t cb[33] = {0};  // uniform blocks: the counts and the check's word in one copy
+  if (csr) {
+    e = hipMemcpyAsync(&f, facts_dev, sizeof(f), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && table)
+      e = hipMemcpyAsync(&cb[32], bad_dev, 4, hipMemcpyDeviceToHost, st);
+  } else {
+    e = hipMemcpyAsync(cb, counts_dev, (table ? 33 : 32) * 4, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(CWQ_ERR_HIP, "%s (facts): %s", who, hipGetErrorString(e));
+  if (!csr) f = cwq::uniform_facts(cb, max_block_dim);
+  s->bad_entries = cb[32];
+  const cwq::BudgetPlan& p = s->plan;
+  switch (cwq::budget_plan(f, csr, nb, total_dims, max_block_dim, n_steps, prune_mode, roff,
+                           &s->plan)) {
+    case cwq::BudgetRefusal::BitsOutOfRange:
+      return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", (unsigned)p.got,
+                  (long long)p.limit, CWQ_MAX_BITS_PER_STEP);
+    case cwq::BudgetRefusal::BadLength:
+      return fail(CWQ_ERR_INVALID, "block_off decreases at %lld blocks", (long long)p.got);
+    case cwq::BudgetRefusal::TooManyDims:
+      return fail(CWQ_ERR_INVALID, "the blocks hold %lld dims, total_dims=%lld", (long long)p.got,
+                  (long long)p.limit);
+    case cwq::BudgetRefusal::BlockTooLong:
+      return fail(CWQ_ERR_INVALID, "a block holds %lld dims, max_block_dim=%lld",
+                  (long long)p.got, (long long)p.limit);
+    case cwq::BudgetRefusal::None:
+      break;
+  }
+  return CWQ_OK;
+}
 }  // namespace
 
 namespace cwq {
@@ -563,46 +636,23 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
   if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
   hipStream_t st = (hipStream_t)stream;
   void* w = workspace;
-  float* tl_s = at<float>(w, l.t_loc);
-  float* ts_s = at<float>(w, l.t_scale);
-  float* pl_s = at<float>(w, l.p_loc);
-  float* ps_s = at<float>(w, l.p_scale);
-  float* sample_s = at<float>(w, l.sample);
-  int32_t* seeds_s = at<int32_t>(w, l.seeds);
-  int32_t* perm = at<int32_t>(w, l.perm);
-  uint32_t* counts_dev = at<uint32_t>(w, l.counts);
-  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, at<uint32_t>(w, l.hist), counts_dev, st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (sort)");
-  // the one synchronisation: the bucket sizes decide the launches
-  uint32_t counts[32];
-  e = hipMemcpyAsync(counts, counts_dev, sizeof(counts), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (counts)");
-  if (counts[31] != 0)
-    return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", counts[31],
-                (long long)nb, CWQ_MAX_BITS_PER_STEP);
-  e = cwq::launch_vb_gather(t_loc, t_scale, p_loc, p_scale, perm, nb, d, seed, block_id_base,
-                            tl_s, ts_s, pl_s, ps_s, seeds_s, st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (gather)");
-  // the eval events go around all the buckets' launches, so each bucket's own
-  // call takes the options without them
-  cwq_options ob = o;
-  ob.eval_start_event = ob.eval_stop_event = nullptr;
-  ob.eval_ms_out = nullptr;
-  ob.item_ready = nullptr;
+  const float* const in[4] = {t_loc, t_scale, p_loc, p_scale};
+  SortedBlocks s;
+  if ((rc = sort_blocks("cwq_greedy_encode_uniform_var", in, nullptr, nb, nb * d, d, n_bits,
+                        n_steps, seed, block_id_base, o.prune_mode, w, l.s, nullptr, nullptr,
+                        nullptr, st, &s)))
+    return rc;
+  const cwq_options ob = without_events(o);
+  hipError_t e;
   if (o.eval_start_event &&
       (e = hipEventRecord((hipEvent_t)o.eval_start_event, st)) != hipSuccess)
     return hip_fail(e, "cwq_greedy_encode_uniform_var (event)");
-  int64_t end = nb;  // the buckets lie in ascending order of bits: walk them from the top
-  for (int b = CWQ_MAX_BITS_PER_STEP; b >= 0; --b) {
-    const int64_t c = counts[b];
-    if (c == 0) continue;
-    const int64_t r0 = end - c;
-    end = r0;
-    rc = encode_impl(tl_s + r0 * d, ts_s + r0 * d, pl_s + r0 * d, ps_s + r0 * d, nullptr, d, c,
-                     c * d, d, b, n_steps, seed, rho, block_id_base, out_idx + r0 * n_steps,
-                     sample_s + r0 * d, at<char>(w, l.enc), l.enc.bytes, &ob, stream,
-                     seeds_s + r0);
+  for (int i = 0; i < s.plan.n_buckets; ++i) {
+    const cwq::BudgetBucket& k = s.plan.buckets[i];
+    rc = encode_impl(s.t_loc + k.d0, s.t_scale + k.d0, s.p_loc + k.d0, s.p_scale + k.d0, nullptr,
+                     d, k.count, k.dims, d, k.bits, n_steps, seed, rho, block_id_base,
+                     out_idx + k.r0 * n_steps, s.sample + k.d0, at<char>(w, l.enc), l.enc.bytes,
+                     &ob, stream, s.seeds + k.r0);
     if (rc) return rc;
   }
   if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
@@ -610,7 +660,7 @@ int cwq_greedy_encode_uniform_var(const float* t_loc, const float* t_scale, cons
   int32_t* stage = at<int32_t>(w, l.stage);
   e = hipMemcpyAsync(stage, out_idx, (size_t)nb * n_steps * 4, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess)
-    e = cwq::launch_vb_scatter(sample_s, stage, perm, nb, d, n_steps, out_sample, out_idx, st);
+    e = cwq::launch_vb_scatter(s.sample, stage, s.perm, nb, d, n_steps, out_sample, out_idx, st);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_uniform_var (scatter)");
   return ok();
 }
@@ -675,80 +725,34 @@ int cwq_greedy_encode_var(const float* t_loc, const float* t_scale, const float*
     return fail(CWQ_ERR_INVALID, "block_off / n_bits / out_idx is null");
   if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale || !out_sample))
     return fail(CWQ_ERR_INVALID, "null input/output pointer");
-  const cwq::VarCsrWs l = cwq::var_csr_ws(nb, total_dims, max_block_dim, n_steps);
+  const cwq::VarWs l = cwq::var_csr_ws(nb, total_dims, max_block_dim, n_steps);
   if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
   hipStream_t st = (hipStream_t)stream;
   void* w = workspace;
-  float* tl_s = at<float>(w, l.t_loc);
-  float* ts_s = at<float>(w, l.t_scale);
-  float* pl_s = at<float>(w, l.p_loc);
-  float* ps_s = at<float>(w, l.p_scale);
-  float* sample_s = at<float>(w, l.sample);
-  int32_t* seeds_s = at<int32_t>(w, l.seeds);
-  int32_t* perm = at<int32_t>(w, l.perm);
-  uint32_t* counts_dev = at<uint32_t>(w, l.counts);
-  cwq::VbcFacts* facts_dev = at<cwq::VbcFacts>(w, l.facts);
-  int64_t* soff = at<int64_t>(w, l.soff);
-  int64_t* roff = at<int64_t>(w, l.roff);
-  int64_t* src = at<int64_t>(w, l.src);
   int32_t* stage = at<int32_t>(w, l.stage);
-  // sort, the buckets' facts, the sorted layout and the sorted copies (all in
-  // the workspace) are enqueued before the host waits for the facts
-  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, at<uint32_t>(w, l.hist), counts_dev, st);
-  if (e == hipSuccess)
-    e = cwq::launch_vbc_layout(n_bits, block_off, perm, nb, counts_dev,
-                               at<unsigned long long>(w, l.wgfacts), facts_dev, seed,
-                               block_id_base, soff, roff, src, seeds_s, at<int64_t>(w, l.partial),
-                               st);
-  if (e == hipSuccess)
-    e = cwq::launch_vbc_gather(t_loc, t_scale, p_loc, p_scale, soff, src, nb, total_dims, tl_s,
-                               ts_s, pl_s, ps_s, st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_var (sort / gather)");
-  // the one synchronisation: the buckets' sizes decide the launches
-  cwq::VbcFacts f;
-  e = hipMemcpyAsync(&f, facts_dev, sizeof(f), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_var (facts)");
-  if (f.counts[31] != 0)
-    return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", f.counts[31],
-                (long long)nb, CWQ_MAX_BITS_PER_STEP);
-  if (f.bad_len != 0)
-    return fail(CWQ_ERR_INVALID, "block_off decreases at %lld blocks", (long long)f.bad_len);
-  int64_t sum_dims = 0, longest = 0;
-  for (int b = 0; b <= CWQ_MAX_BITS_PER_STEP; ++b) {
-    sum_dims += f.dims[b];
-    longest = std::max(longest, f.maxd[b]);
-  }
-  if (sum_dims > total_dims)
-    return fail(CWQ_ERR_INVALID, "the blocks hold %lld dims, total_dims=%lld", (long long)sum_dims,
-                (long long)total_dims);
-  if (longest > max_block_dim)
-    return fail(CWQ_ERR_INVALID, "a block holds %lld dims, max_block_dim=%lld",
-                (long long)longest, (long long)max_block_dim);
-  // the eval events go around all the buckets' launches, so each bucket's own
-  // call takes the options without them
-  cwq_options ob = o;
-  ob.eval_start_event = ob.eval_stop_event = nullptr;
-  ob.eval_ms_out = nullptr;
-  ob.item_ready = nullptr;
+  const float* const in[4] = {t_loc, t_scale, p_loc, p_scale};
+  SortedBlocks s;
+  if ((rc = sort_blocks("cwq_greedy_encode_var", in, block_off, nb, total_dims, max_block_dim,
+                        n_bits, n_steps, seed, block_id_base, o.prune_mode, w, l.s, nullptr,
+                        nullptr, nullptr, st, &s)))
+    return rc;
+  const cwq_options ob = without_events(o);
+  hipError_t e;
   if (o.eval_start_event &&
       (e = hipEventRecord((hipEvent_t)o.eval_start_event, st)) != hipSuccess)
     return hip_fail(e, "cwq_greedy_encode_var (event)");
-  for (int b = CWQ_MAX_BITS_PER_STEP; b >= 0; --b) {
-    const int64_t c = f.counts[b];
-    if (c == 0) continue;
-    const int64_t r0 = f.start[b], d0 = f.pre[b];
-    const bool rows_wave = cwq::bucket_takes_rows_wave(b, f.dims[b], c, o.prune_mode);
-    // the bucket's own longest block: short blocks stay off the long-block path
-    rc = encode_impl(tl_s + d0, ts_s + d0, pl_s + d0, ps_s + d0, roff + r0 + b, 0, c, f.dims[b],
-                     f.maxd[b], b, n_steps, seed, rho, block_id_base, stage + r0 * n_steps,
-                     sample_s + d0, at<char>(w, l.enc), l.enc.bytes, &ob, stream, seeds_s + r0,
-                     nullptr, nullptr, nullptr, rows_wave);
+  for (int i = 0; i < s.plan.n_buckets; ++i) {
+    const cwq::BudgetBucket& k = s.plan.buckets[i];
+    rc = encode_impl(s.t_loc + k.d0, s.t_scale + k.d0, s.p_loc + k.d0, s.p_scale + k.d0,
+                     k.block_off, 0, k.count, k.dims, k.maxd, k.bits, n_steps, seed, rho,
+                     block_id_base, stage + k.r0 * n_steps, s.sample + k.d0, at<char>(w, l.enc),
+                     l.enc.bytes, &ob, stream, s.seeds + k.r0, nullptr, nullptr, nullptr,
+                     k.rows_wave);
     if (rc) return rc;
   }
   if (o.eval_stop_event && (e = hipEventRecord((hipEvent_t)o.eval_stop_event, st)) != hipSuccess)
     return hip_fail(e, "cwq_greedy_encode_var (event)");
-  e = cwq::launch_vbc_scatter(sample_s, stage, soff, src, perm, nb, total_dims, n_steps,
+  e = cwq::launch_vbc_scatter(s.sample, stage, s.soff, s.src, s.perm, nb, total_dims, n_steps,
                               out_sample, out_idx, st);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_var (scatter)");
   return ok();
@@ -3123,11 +3127,9 @@ int cwq_greedy_backfit(const float* t_loc, const float* t_scale, const float* p_
   return ok();
 }
 
-// Backfitting under per-block budgets: the budget call's sort,
-// sorted layout and gather, the table's rows gathered with their range check,
-// one wait for the buckets' facts and the check's count, then launch_backfit
-// over all sorted blocks with a scoring launch sequence per bucket, and the
-// scatter back.  The caller's arrays are written by that scatter alone.
+// Backfitting under per-block budgets: sort_blocks with the
+// table, then launch_backfit over all sorted blocks with a scoring launch
+// sequence per bucket, and the scatter back, which alone writes the caller's arrays.
 int cwq_greedy_backfit_var(const float* t_loc, const float* t_scale, const float* p_loc,
                            const float* p_scale, const int64_t* block_off, int64_t nb,
                            int64_t total_dims, int64_t max_block_dim, const int32_t* n_bits,
@@ -3156,124 +3158,43 @@ int cwq_greedy_backfit_var(const float* t_loc, const float* t_scale, const float
   if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
   hipStream_t st = (hipStream_t)stream;
   void* w = workspace;
-  float* tl_s = at<float>(w, l.t_loc);
-  float* ts_s = at<float>(w, l.t_scale);
-  float* pl_s = at<float>(w, l.p_loc);
-  float* ps_s = at<float>(w, l.p_scale);
-  float* sample_s = at<float>(w, l.sample);
-  int32_t* seeds_s = at<int32_t>(w, l.seeds);
-  int32_t* perm = at<int32_t>(w, l.perm);
-  uint32_t* counts_dev = at<uint32_t>(w, l.counts);  // 32 counts, then `bad`
-  uint32_t* bad_dev = at<uint32_t>(w, l.bad);
   int32_t* table = at<int32_t>(w, l.table);
-  cwq::VbcFacts* facts_dev = at<cwq::VbcFacts>(w, l.facts);
-  int64_t* soff = at<int64_t>(w, l.soff);
-  int64_t* roff = at<int64_t>(w, l.roff);
-  int64_t* src = at<int64_t>(w, l.src);
-  // everything up to the sorted copies lies in the workspace and is enqueued
-  // before the host waits; nothing here depends on the values being valid
-  hipError_t e = cwq::launch_vb_sort(n_bits, nb, perm, at<uint32_t>(w, l.hist), counts_dev, st);
-  if (e == hipSuccess && csr) {
-    e = cwq::launch_vbc_layout(n_bits, block_off, perm, nb, counts_dev,
-                               at<unsigned long long>(w, l.wgfacts), facts_dev, seed,
-                               block_id_base, soff, roff, src, seeds_s, at<int64_t>(w, l.partial),
-                               st);
-    if (e == hipSuccess)
-      e = cwq::launch_vbc_gather(t_loc, t_scale, p_loc, p_scale, soff, src, nb, total_dims, tl_s,
-                                 ts_s, pl_s, ps_s, st);
-  } else if (e == hipSuccess) {
-    e = cwq::launch_vb_gather(t_loc, t_scale, p_loc, p_scale, perm, nb, d, seed, block_id_base,
-                              tl_s, ts_s, pl_s, ps_s, seeds_s, st);
-  }
-  if (e == hipSuccess)
-    e = cwq::launch_vb_gather_table(idx_inout, n_bits, perm, nb, n_steps, table, bad_dev, st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var (sort / gather)");
-  // the one synchronisation: the buckets' sizes decide the launches, and the
-  // table's check comes with them
-  cwq::VbcFacts f;
-  uint32_t cb[33];  // uniform blocks: the counts and the check's word in one copy
-  if (csr) {
-    e = hipMemcpyAsync(&f, facts_dev, sizeof(f), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&cb[32], bad_dev, 4, hipMemcpyDeviceToHost, st);
-  } else {
-    e = hipMemcpyAsync(cb, counts_dev, sizeof(cb), hipMemcpyDeviceToHost, st);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var (facts)");
-  if (!csr) {  // the facts of uniform blocks follow from the counts
-    int64_t row = 0;
-    f.bad_len = 0;
-    for (int b = 0; b < 32; ++b) {
-      f.counts[b] = cb[b];
-      f.start[b] = (uint32_t)row;
-      f.pre[b] = row * d;
-      f.dims[b] = (int64_t)cb[b] * d;
-      f.maxd[b] = cb[b] ? d : 0;
-      row += cb[b];
-    }
-  }
-  if (f.counts[31] != 0)
-    return fail(CWQ_ERR_INVALID, "%u of %lld n_bits values outside [0, %d]", f.counts[31],
-                (long long)nb, CWQ_MAX_BITS_PER_STEP);
-  if (f.bad_len != 0)
-    return fail(CWQ_ERR_INVALID, "block_off decreases at %lld blocks", (long long)f.bad_len);
-  int64_t sum_dims = 0, longest = 0;
-  for (int b = 0; b <= CWQ_MAX_BITS_PER_STEP; ++b) {
-    sum_dims += f.dims[b];
-    longest = std::max(longest, f.maxd[b]);
-  }
-  if (sum_dims > total_dims)
-    return fail(CWQ_ERR_INVALID, "the blocks hold %lld dims, total_dims=%lld", (long long)sum_dims,
-                (long long)total_dims);
-  if (longest > max_block_dim)
-    return fail(CWQ_ERR_INVALID, "a block holds %lld dims, max_block_dim=%lld",
-                (long long)longest, (long long)max_block_dim);
-  if (cb[32] != 0)
+  const float* const in[4] = {t_loc, t_scale, p_loc, p_scale};
+  SortedBlocks s;
+  if ((rc = sort_blocks("cwq_greedy_backfit_var", in, block_off, nb, total_dims, max_block_dim,
+                        n_bits, n_steps, seed, block_id_base, o.prune_mode, w, l.s, idx_inout,
+                        table, at<uint32_t>(w, l.bad), st, &s)))
+    return rc;
+  if (s.bad_entries != 0)
     return fail(CWQ_ERR_INVALID, "%u of %lld entries of idx_inout lie outside [0, 2^n_bits[g])",
-                cb[32], (long long)nb * n_steps);
-  // the buckets that score: at least one bit and one block, from the top as
-  // cwq_greedy_encode_var walks them
-  cwq::BackfitBucket buckets[CWQ_MAX_BITS_PER_STEP];
-  int n_buckets = 0, top = 0;
-  for (int b = CWQ_MAX_BITS_PER_STEP; b >= 1; --b) {
-    const int64_t c = f.counts[b];
-    if (c == 0) continue;
-    top = std::max(top, b);
-    cwq::BackfitBucket& k = buckets[n_buckets++];
-    k.bits = b;
-    k.r0 = f.start[b];
-    k.d0 = f.pre[b];
-    k.count = c;
-    k.dims = f.dims[b];
-    k.maxd = f.maxd[b];  // its own longest block: short blocks stay off the long-block path
-    k.block_off = csr ? roff + k.r0 + b : nullptr;
-    choose_tiling(c, (int64_t)1 << b, &k.tiles_per_block, &k.cand_per_tile);
-    k.rows_wave = csr && cwq::bucket_takes_rows_wave(b, f.dims[b], c, o.prune_mode);
-  }
-  char* encw = at<char>(w, l.enc);
+                s.bad_entries, (long long)nb * n_steps);
+  const cwq::BudgetPlan& p = s.plan;
   cwq::BackfitArgs a;
-  fill_encode_args(a.enc, tl_s, ts_s, pl_s, ps_s, csr ? soff : nullptr, csr ? 0 : d, nb, sum_dims,
-                   longest, top, n_steps, seed, rho, block_id_base, table, sample_s, o, l.encl,
-                   encw);
-  a.enc.seeds = seeds_s;
+  fill_encode_args(a.enc, s.t_loc, s.t_scale, s.p_loc, s.p_scale, csr ? s.soff : nullptr,
+                   csr ? 0 : d, nb, p.sum_dims, p.longest, p.top, n_steps, seed, rho,
+                   block_id_base, table, s.sample, o, l.encl, at<char>(w, l.enc));
+  a.enc.seeds = s.seeds;
   a.sweeps = sweeps;
   a.rows = at<float>(w, l.rows);
   a.value = at<float>(w, l.value);
   a.count = at<int32_t>(w, l.count);
   a.out_value = nullptr;  // the scatter below writes the caller's arrays
   a.out_accepted = nullptr;
-  a.path = cwq::backfit_plan(longest, nb);
-  a.buckets = buckets;
-  a.n_buckets = n_buckets;
-  e = cwq::launch_backfit(a, st);
+  a.path = cwq::backfit_plan(p.longest, nb);
+  // the buckets that score have at least one bit: the blocks of the 0-bit
+  // bucket (the plan's last) keep row 0
+  a.buckets = p.buckets;
+  a.n_buckets = p.n_buckets - (p.n_buckets && p.buckets[p.n_buckets - 1].bits == 0);
+  hipError_t e = cwq::launch_backfit(a, st);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var");
   if (csr)
-    e = cwq::launch_vbc_scatter(sample_s, table, soff, src, perm, nb, total_dims, n_steps,
+    e = cwq::launch_vbc_scatter(s.sample, table, s.soff, s.src, s.perm, nb, total_dims, n_steps,
                                 out_sample, idx_inout, st);
   else
-    e = cwq::launch_vb_scatter(sample_s, table, perm, nb, d, n_steps, out_sample, idx_inout, st);
+    e = cwq::launch_vb_scatter(s.sample, table, s.perm, nb, d, n_steps, out_sample, idx_inout,
+                               st);
   if (e == hipSuccess)
-    e = cwq::launch_vb_scatter_blocks(a.value, a.count, perm, nb, out_value, out_accepted, st);
+    e = cwq::launch_vb_scatter_blocks(a.value, a.count, s.perm, nb, out_value, out_accepted, st);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_backfit_var (scatter)");
   return ok();
 }

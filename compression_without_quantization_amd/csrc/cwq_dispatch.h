@@ -50,6 +50,23 @@ namespace cwq {
 constexpr int64_t kCsrPrunedMinCand = 4096;
 constexpr int64_t kChipLanes = 1536 * 256;  // lanes the whole chip holds
 
+#ifndef CWQ_TARGET_TILES
+#define CWQ_TARGET_TILES 16384  // tiles per launch the tiling aims for (tuning builds)
+#endif
+inline void choose_tiling(int64_t nb, int64_t n_cand, int64_t* tiles_per_block,
+                          int64_t* cand_per_tile) {
+  const int64_t kTargetTiles = CWQ_TARGET_TILES;
+  int64_t want = nb > 0 ? (kTargetTiles + nb - 1) / nb : 1;
+  int64_t max_split = (n_cand + 255) / 256;  // at least one candidate per lane
+  if (want > max_split) want = max_split;
+  if (want < 1) want = 1;
+  int64_t cpt = (n_cand + want - 1) / want;
+  cpt = (cpt + 255) / 256 * 256;
+  if (cpt < 256) cpt = 256;
+  *cand_per_tile = cpt;
+  *tiles_per_block = (n_cand + cpt - 1) / cpt;
+}
+
 struct EncodeShape {
   bool csr;        // ragged blocks (block_off given); false: uniform blocks of ud dims
   int64_t ud;      // uniform block length (csr: unused)

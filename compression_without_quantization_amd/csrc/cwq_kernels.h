@@ -5,6 +5,7 @@
 
 #include "cwq_dispatch.h"
 #include "cwq_workspace.h"
+#include "cwq_budget_plan.h"
 
 namespace cwq {
 
@@ -234,18 +235,8 @@ hipError_t launch_block_bits_csr(const float* q_loc, const float* q_scale, const
                                  double extra_bits, int n_steps, int32_t min_bits,
                                  int32_t max_bits, int32_t* bits_out, float* kl_bits_out,
                                  hipStream_t stream);
-// What the host reads back (one copy) to launch the buckets of a sorted CSR
-// call: bucket b holds the sorted rows [start[b], start[b] + counts[b]), their
-// dims[b] dims lie at [pre[b], pre[b] + dims[b]) of the sorted arrays, and none
-// of its blocks is longer than maxd[b].  bad_len: blocks of negative length
-// (they count as empty everywhere).
-struct VbcFacts {
-  int64_t dims[32], maxd[32], pre[32];
-  uint32_t counts[32], start[32];
-  int64_t bad_len;
-};
-static_assert(sizeof(VbcFacts) == kVbcFactsBytes, "var_csr_ws sizes the facts by it");
-// The sorted layout, from the sort's perm and counts: the facts; soff[0..nb]
+// The sorted layout, from the sort's perm and counts: the facts (VbcFacts,
+// cwq_budget_plan.h: what the host reads back, in one copy); soff[0..nb]
 // the exclusive scan of the block lengths in sorted order; roff [nb + 33]:
 // bucket b's own offsets, relative to its first dim, with a terminator of its
 // own, at roff + start[b] + b (counts[b] + 1 entries); src[r] =
@@ -321,18 +312,6 @@ hipError_t launch_prep_dims(const float* t_scale, const float* p_loc, const floa
 hipError_t launch_score_step(const EncodeArgs& a, int step, hipStream_t stream);
 // rows, value, count: what a backfit call has beyond the encoder's arrays
 // (backfit_ws, cwq_workspace.h)
-// One budget's slice of a call whose blocks are sorted by budget (DESIGN.md
-// 4h): rows [r0, r0 + count) and dims [d0, d0 + dims) of the call's arrays, none
-// of its blocks longer than maxd.  Its scoring launches get the call's arrays
-// shifted to r0 / d0, the offsets block_off (relative to d0; nullptr: uniform)
-// and the shape's own candidate count, tiling and path.
-struct BackfitBucket {
-  int bits;
-  int64_t r0, d0, count, dims, maxd;
-  const int64_t* block_off;
-  int64_t tiles_per_block, cand_per_tile;
-  bool rows_wave;
-};
 struct BackfitArgs {
   EncodeArgs enc;      // the encoder's arguments; out_idx is the table (in and out),
                        // out_sample the carried vector between the launches and the result
@@ -347,7 +326,7 @@ struct BackfitArgs {
   // sequence per step.  Otherwise the call's buckets (each of at least one bit
   // and one block): a scoring launch sequence per step and bucket; blocks in no
   // bucket keep key 0, i.e. row 0.  Everything else covers all blocks at once.
-  const BackfitBucket* buckets = nullptr;
+  const BudgetBucket* buckets = nullptr;
   int n_buckets = 0;
 };
 hipError_t launch_backfit(const BackfitArgs& a, hipStream_t stream);

@@ -121,37 +121,60 @@ inline EncWs enc_ws_uniform(int64_t nb, int64_t d) {
   return enc_ws(nb, nb * d, has_screen_arrays(false, d, nb), has_long_block_records(false, d, nb));
 }
 
+// ---- blocks sorted by bit budget: the sorted view (cwq_capi.hip sort_blocks) ----
+// What the three budget calls share.  Uniform blocks have the four sorted inputs
+// back to back (unrounded) in `sorted_in`; ragged blocks have a region for each,
+// and the sorted layout's arrays (launch_vbc_layout) behind the counts.  Regions
+// the blocks' form does not have are empty.
+struct SortedWs {
+  Region sorted_in, t_loc, t_scale, p_loc, p_scale;  // sorted_in: the four behind it (uniform)
+  Region sample, seeds, perm, hist, counts;
+  Region wgfacts, facts, soff, roff, src, partial;  // ragged blocks only
+};
+inline SortedWs sorted_ws(Arena& a, bool csr, int64_t nb, int64_t total_dims) {
+  SortedWs l{};
+  const size_t n = (size_t)nb, row = (size_t)total_dims * 4, tiles = (size_t)vb_tiles(nb);
+  Arena in{a.o};
+  auto input = [&] { return csr ? a.take(row) : in.take_packed(row); };
+  l.t_loc = input(), l.t_scale = input(), l.p_loc = input(), l.p_scale = input();
+  if (!csr) l.sorted_in = a.take(in);
+  l.sample = a.take(row);
+  l.seeds = a.take(n * 4);
+  l.perm = a.take(n * 4);
+  l.hist = a.take(tiles * kVbBins * 4);
+  l.counts = a.take(32 * 4);
+  if (csr) {
+    l.wgfacts = a.take(tiles * kVbcFactsRow * 8);
+    l.facts = a.take(kVbcFactsBytes);
+    l.soff = a.take((n + 1) * 8);
+    l.roff = a.take((n + 33) * 8);
+    l.src = a.take(n * 8);
+    l.partial = a.take(tiles * 8);
+  }
+  return l;
+}
+
 // ---- uniform blocks with a bit budget each (cwq_greedy_encode_uniform_var) ----
-// The four sorted inputs lie back to back (unrounded).  Every bucket's encode
-// runs in `enc`, sized for the whole call (no bucket's layout exceeds it).  The
-// encoders write the sorted index rows into the caller's out_idx; they are
-// staged for the scatter in the sorted inputs' region (16 nb d bytes, dead by
-// then) when 4 nb n_steps bytes fit there, i.e. n_steps <= 4 d, else in a tail
-// of that size: cwq_greedy_encode_uniform_var_workspace_size is n_steps = 1.
+// Every bucket's encode runs in `enc`, sized for the whole call (no bucket's
+// layout exceeds it).  The encoders write the sorted index rows into the
+// caller's out_idx; they are staged for the scatter in the sorted inputs'
+// region (16 nb d bytes, dead by then) when 4 nb n_steps bytes fit there, i.e.
+// n_steps <= 4 d, else in a tail of that size:
+// cwq_greedy_encode_uniform_var_workspace_size is n_steps = 1.
 struct VarWs {
-  Region t_loc, t_scale, p_loc, p_scale, sorted_in;  // sorted_in: the four above
-  Region sample, seeds, perm, hist, counts, enc, stage;
+  SortedWs s;
+  Region enc, stage;
   size_t total;
   bool stage_aliases_sorted_in;
 };
 inline VarWs var_ws(int64_t nb, int64_t d, int64_t n_steps) {
   VarWs l;
-  Arena a, in;
-  const size_t n = (size_t)nb, row = n * (size_t)d * 4;
-  l.t_loc = in.take_packed(row);
-  l.t_scale = in.take_packed(row);
-  l.p_loc = in.take_packed(row);
-  l.p_scale = in.take_packed(row);
-  l.sorted_in = a.take(in);
-  l.sample = a.take(row);
-  l.seeds = a.take(n * 4);
-  l.perm = a.take(n * 4);
-  l.hist = a.take((size_t)vb_tiles(nb) * kVbBins * 4);
-  l.counts = a.take(32 * 4);
+  Arena a;
+  l.s = sorted_ws(a, false, nb, nb * d);
   l.enc = a.take(enc_ws_uniform(nb, d).total);
   l.stage_aliases_sorted_in = n_steps <= 4 * d;
-  const size_t stage = n * (size_t)n_steps * 4;
-  l.stage = l.stage_aliases_sorted_in ? Region{l.sorted_in.off, stage} : a.take(stage);
+  const size_t stage = (size_t)nb * (size_t)n_steps * 4;
+  l.stage = l.stage_aliases_sorted_in ? Region{l.s.sorted_in.off, stage} : a.take(stage);
   l.total = a.o;
   return l;
 }
@@ -174,32 +197,11 @@ inline PackWs pack_ws(int64_t nb) {
 // ---- ragged blocks with a bit budget each (cwq_greedy_encode_var) -------------
 // Every bucket is a CSR encode in `enc`, sized for the whole call's nb,
 // total_dims and max_block_dim, which no bucket exceeds (enc_ws_csr is monotone).
-struct VarCsrWs {
-  Region t_loc, t_scale, p_loc, p_scale, sample, seeds, perm, hist, counts, wgfacts, facts, soff,
-      roff, src, partial, stage, enc;
-  size_t total;
-};
-inline VarCsrWs var_csr_ws(int64_t nb, int64_t total_dims, int64_t max_block_dim,
-                           int64_t n_steps) {
-  VarCsrWs l;
+inline VarWs var_csr_ws(int64_t nb, int64_t total_dims, int64_t max_block_dim, int64_t n_steps) {
+  VarWs l{};
   Arena a;
-  const size_t n = (size_t)nb, row = (size_t)total_dims * 4, tiles = (size_t)vb_tiles(nb);
-  l.t_loc = a.take(row);
-  l.t_scale = a.take(row);
-  l.p_loc = a.take(row);
-  l.p_scale = a.take(row);
-  l.sample = a.take(row);
-  l.seeds = a.take(n * 4);
-  l.perm = a.take(n * 4);
-  l.hist = a.take(tiles * kVbBins * 4);
-  l.counts = a.take(32 * 4);
-  l.wgfacts = a.take(tiles * kVbcFactsRow * 8);
-  l.facts = a.take(kVbcFactsBytes);
-  l.soff = a.take((n + 1) * 8);
-  l.roff = a.take((n + 33) * 8);
-  l.src = a.take(n * 8);
-  l.partial = a.take(tiles * 8);
-  l.stage = a.take(n * (size_t)n_steps * 4);
+  l.s = sorted_ws(a, true, nb, total_dims);
+  l.stage = a.take((size_t)nb * (size_t)n_steps * 4);  // a region of its own
   l.enc = a.take(enc_ws_csr(nb, total_dims, max_block_dim).total);
   l.total = a.o;
   return l;
@@ -533,8 +535,8 @@ inline BackfitWs backfit_ws(bool csr, int64_t nb, int64_t total_dims, int64_t ma
 //   uniform  var_ws(nb, d, 1) + up(4 nb n_steps) + the same difference at
 //            (nb, nb d, d, n_steps)
 struct BackfitVarWs {
-  Region t_loc, t_scale, p_loc, p_scale, sorted_in, sample, seeds, perm, hist, counts, bad,
-      wgfacts, facts, soff, roff, src, partial, table, enc, rows, value, count;
+  SortedWs s;
+  Region bad, table, enc, rows, value, count;
   size_t total;
   bool csr;
   EncWs encl;  // the arrays inside `enc` (offsets relative to it)
@@ -544,25 +546,13 @@ inline BackfitVarWs backfit_var_ws(bool csr, int64_t nb, int64_t total_dims, int
   BackfitVarWs l{};
   l.csr = csr;
   const size_t n = (size_t)nb;
-  Arena a;
-  if (csr) {
-    const VarCsrWs v = var_csr_ws(nb, total_dims, max_block_dim, n_steps);
-    l.t_loc = v.t_loc, l.t_scale = v.t_scale, l.p_loc = v.p_loc, l.p_scale = v.p_scale;
-    l.sample = v.sample, l.seeds = v.seeds, l.perm = v.perm, l.hist = v.hist, l.counts = v.counts;
-    l.wgfacts = v.wgfacts, l.facts = v.facts, l.soff = v.soff, l.roff = v.roff, l.src = v.src;
-    l.partial = v.partial, l.table = v.stage, l.enc = v.enc;
-    l.encl = enc_ws_csr(nb, total_dims, max_block_dim);
-    a.o = v.total;
-  } else {
-    const VarWs v = var_ws(nb, max_block_dim, 1);
-    l.t_loc = v.t_loc, l.t_scale = v.t_scale, l.p_loc = v.p_loc, l.p_scale = v.p_scale;
-    l.sorted_in = v.sorted_in, l.sample = v.sample, l.seeds = v.seeds, l.perm = v.perm;
-    l.hist = v.hist, l.counts = v.counts, l.enc = v.enc;
-    l.encl = enc_ws_uniform(nb, max_block_dim);
-    a.o = v.total;
-    l.table = a.take(n * (size_t)n_steps * 4);
-  }
-  l.bad = Region{l.counts.off + l.counts.bytes, 4};  // in the counts' rounding room
+  const VarWs v = csr ? var_csr_ws(nb, total_dims, max_block_dim, n_steps)
+                      : var_ws(nb, max_block_dim, 1);
+  l.s = v.s, l.enc = v.enc;
+  l.encl = csr ? enc_ws_csr(nb, total_dims, max_block_dim) : enc_ws_uniform(nb, max_block_dim);
+  Arena a{v.total};
+  l.table = csr ? v.stage : a.take(n * (size_t)n_steps * 4);
+  l.bad = Region{l.s.counts.off + l.s.counts.bytes, 4};  // in the counts' rounding room
   l.rows = a.take((size_t)n_steps * total_dims * 4);
   l.value = a.take(n * 4);
   l.count = a.take(n * 4);

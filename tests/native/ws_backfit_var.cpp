@@ -16,20 +16,25 @@ extern "C" {
 int wsb_dump(const int64_t* v, char* out, int cap) {
   using namespace cwq;
   const BackfitVarWs l = backfit_var_ws(v[0] != 0, v[1], v[2], v[3], (int)v[4]);
-  static const char* const names[] = {"t_loc",   "t_scale", "p_loc", "p_scale", "sorted_in",
-                                      "sample",  "seeds",   "perm",  "hist",    "counts",
-                                      "bad!",    "wgfacts", "facts", "soff",    "roff",
-                                      "src",     "partial", "table", "enc",     "rows",
-                                      "value",   "count"};
-  const Region* r = &l.t_loc;
-  const int n_regions = (int)((const Region*)&l.total - r);
-  if (n_regions != (int)(sizeof(names) / sizeof(names[0]))) return -2;
+  static const char* const sorted[] = {"sorted_in", "t_loc",   "t_scale", "p_loc",
+                                       "p_scale",   "sample",  "seeds",   "perm",
+                                       "hist",      "counts",  "wgfacts", "facts",
+                                       "soff",      "roff",    "src",     "partial"};
+  static const char* const own[] = {"bad!", "table", "enc", "rows", "value", "count"};
   int n = 0;
-  for (int i = 0; i < n_regions; ++i) {
-    const int w = snprintf(out + n, cap - n, "%s %zu %zu\n", names[i], r[i].off, r[i].bytes);
-    if (w < 0 || w >= cap - n) return -2;
-    n += w;
-  }
+  // regions [r, end) under the names (one per region)
+  auto regions = [&](const Region* r, const void* end, const char* const* names, size_t count) {
+    if ((size_t)((const Region*)end - r) != count) return false;
+    for (size_t i = 0; i < count; ++i) {
+      const int w = snprintf(out + n, cap - n, "%s %zu %zu\n", names[i], r[i].off, r[i].bytes);
+      if (w < 0 || w >= cap - n) return false;
+      n += w;
+    }
+    return true;
+  };
+  if (!regions(&l.s.sorted_in, &l.bad, sorted, sizeof(sorted) / sizeof(sorted[0])) ||
+      !regions(&l.bad, &l.total, own, sizeof(own) / sizeof(own[0])))
+    return -2;
   const int w = snprintf(out + n, cap - n, "total %zu\n", l.total);
   if (w < 0 || w >= cap - n) return -2;
   return n + w;

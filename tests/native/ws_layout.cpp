@@ -65,22 +65,21 @@ int wsl_dump(const char* what, const int64_t* v, char* out, int cap) {
     total(o, l.total);
   } else if (is("var")) {
     const VarWs l = var_ws(v[0], v[1], v[2]);
-    regions(o, &l.t_loc, &l.total,
-            l.stage_aliases_sorted_in
-                ? "t_loc@sorted_in t_scale@sorted_in p_loc@sorted_in p_scale@sorted_in sorted_in "
-                  "sample seeds perm hist counts enc stage~sorted_in"
-                : "t_loc@sorted_in t_scale@sorted_in p_loc@sorted_in p_scale@sorted_in sorted_in "
-                  "sample seeds perm hist counts enc stage");
+    regions(o, &l.s.sorted_in, &l.s.wgfacts,
+            "sorted_in t_loc@sorted_in t_scale@sorted_in p_loc@sorted_in p_scale@sorted_in "
+            "sample seeds perm hist counts");
+    regions(o, &l.enc, &l.total, l.stage_aliases_sorted_in ? "enc stage~sorted_in" : "enc stage");
     total(o, l.total);
   } else if (is("pack")) {
     const PackWs l = pack_ws(v[0]);
     regions(o, &l.off, &l.total, "off partial flag");
     total(o, l.total);
   } else if (is("var_csr")) {
-    const VarCsrWs l = var_csr_ws(v[0], v[1], v[2], v[3]);
-    regions(o, &l.t_loc, &l.total,
+    const VarWs l = var_csr_ws(v[0], v[1], v[2], v[3]);
+    regions(o, &l.s.t_loc, &l.enc,
             "t_loc t_scale p_loc p_scale sample seeds perm hist counts wgfacts facts soff roff src "
-            "partial stage enc");
+            "partial");
+    regions(o, &l.enc, &l.total, "enc stage");
     total(o, l.total);
   } else if (is("part") || is("part_debug")) {
     const PartDebugWs l = part_debug_ws(v[0]);

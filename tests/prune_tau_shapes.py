@@ -42,7 +42,7 @@ ORACLE_STRIDE = 4096
 
 
 def tiling(nb, n_cand, target=16384):
-    """csrc/cwq_capi.hip choose_tiling: (tiles per block, candidates per tile)."""
+    """csrc/cwq_dispatch.h choose_tiling: (tiles per block, candidates per tile)."""
     want = max(1, min(-(-target // nb), -(-n_cand // 256)))
     cpt = max(256, -(-(-(-n_cand // want)) // 256) * 256)
     return -(-n_cand // cpt), cpt

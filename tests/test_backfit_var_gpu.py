@@ -434,6 +434,24 @@ def test_refusals_leave_the_callers_arrays(cwq, cwqlib, name):
     t = _tensors(cwq, name, table, wide)
     assert _raw(cwqlib, t, 1) == -1 and b"n_bits" in cwqlib.cwq_last_error()
     _untouched(t, table)
+    # ragged blocks: what only the buckets' facts can tell.  The real arrays at
+    # full length (every read stays inside them), one scalar or one offset wrong
+    if _input(name)[1] is None:
+        off = _input(name)[0][0]
+        lowered = off.copy()
+        lowered[2] = off[1] - 1  # block 1 ends before it starts; block 2 is longer by as much
+        D, longest = int(off[-1]), int(np.diff(off).max())
+        assert 0 <= lowered[2] < lowered[1] and lowered.max() == D
+        for change, msg in [
+                (dict(D=D - 1), b"the blocks hold %d dims, total_dims=%d" % (D, D - 1)),
+                (dict(longest=longest - 1),
+                 b"a block holds %d dims, max_block_dim=%d" % (longest, longest - 1)),
+                (dict(off=torch.from_numpy(lowered).cuda()), b"block_off decreases at 1 blocks")]:
+            t = _tensors(cwq, name, table)
+            t.update(change)
+            assert _raw(cwqlib, t, 1) == -1 and cwqlib.cwq_last_error() == msg, \
+                cwqlib.cwq_last_error()
+            _untouched(t, table)
     # a workspace one byte short
     t = _tensors(cwq, name, table)
     assert _raw(cwqlib, t, 1, ws_bytes=t["need"] - 1) == -3

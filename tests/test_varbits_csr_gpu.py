@@ -299,6 +299,30 @@ def test_short_workspace_wrong_length_and_block_arguments(cwq, cwqlib):
                                         workspace=ws)
     fresh, fsample = cwq.encode_blocks_var(tl, ts, pl, ps, bits, n_steps, 1, block_off=off)
     assert torch.equal(idx, fresh) and np.array_equal(_u32(sample), _u32(fsample))
+    # what only the buckets' facts can tell, through the raw call: the real
+    # arrays at full length (every read stays inside them) and one scalar or one
+    # offset wrong; the workspace is the true shape's
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    arrays = [dev(a) for a in (tl, ts, pl, ps)]
+    bits_d, longest = dev(bits), int(np.diff(off).max())
+    lowered = off.copy()
+    lowered[2] = off[1] - 1  # block 1 ends before it starts; block 2 is longer by as much
+    assert 0 <= lowered[2] < lowered[1] and lowered.max() == D
+    for offs, total, maxd, msg in [
+            (off, D - 1, longest, b"the blocks hold %d dims, total_dims=%d" % (D, D - 1)),
+            (off, D, longest - 1, b"a block holds %d dims, max_block_dim=%d" % (longest,
+                                                                                longest - 1)),
+            (lowered, D, longest, b"block_off decreases at 1 blocks")]:
+        offs_d = dev(offs)
+        out_idx = torch.full((NB, n_steps), -77, dtype=torch.int32, device="cuda")
+        out_sample = torch.full((D,), -77.0, dtype=torch.float32, device="cuda")
+        rc = cwqlib.cwq_greedy_encode_var(
+            *[a.data_ptr() for a in arrays], offs_d.data_ptr(), NB, total, maxd,
+            bits_d.data_ptr(), n_steps, 1, 1.0, 0, out_idx.data_ptr(), out_sample.data_ptr(),
+            ws.data_ptr(), need, None, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert rc == -1 and cwqlib.cwq_last_error() == msg, cwqlib.cwq_last_error()
+        assert (out_idx == -77).all() and (out_sample == -77.0).all()
     for kw in ({}, {"block_dim": 1, "block_off": off}):
         with pytest.raises(ValueError):
             cwq.encode_blocks_var(tl, ts, pl, ps, bits, n_steps, 1, **kw)
