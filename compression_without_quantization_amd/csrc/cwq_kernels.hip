@@ -184,6 +184,22 @@ constexpr float kPruneC1 = 0x1p-14f;
 // read (VisitRec::next); 0: it adds the record size (A/B builds)
 #define CWQ_LINKED_VISIT 1
 #endif
+#ifndef CWQ_FOLD_ROUND0
+// the screening loop takes a visit's Philox block as (lane's row part) +
+// (record's part) inside round 0's multiply-add, from per-wave records
+// (VisitRec::add); 0: one record set, the block formed by a v_add3 (A/B builds)
+#define CWQ_FOLD_ROUND0 1
+#endif
+#ifndef CWQ_BORROW_REFILL
+// static rows are handed out downwards and the subtract's borrow tells which
+// lanes have used theirs up; 0: upwards, with a compare per iteration (A/B builds)
+#define CWQ_BORROW_REFILL 1
+#endif
+#ifndef CWQ_POOL_RANGE_SKIP
+// the pool refill leaves out its range compare when the wave's counter shows
+// that every row handed out is in range (CWQ_BORROW_REFILL builds); 0: always compares
+#define CWQ_POOL_RANGE_SKIP 1
+#endif
 
 // best + (loc_s + scale_s z) - mu  (misc.py:14-15, coded_greedy_sampler.py:57, TFP _z numerator)
 template <bool STEP0>
@@ -208,12 +224,20 @@ __device__ __forceinline__ float lp_from_z(float z, float cc) {
 // What the screening loop reads at one visit position, in one LDS record: the
 // loop carries the record's byte offset, so the three reads share one address
 // register and differ in their immediate offsets only.
+//
+// With CWQ_FOLD_ROUND0 every wave has its own G records.  A lane carries its
+// row as ng = (n - w0) G, relative to its wave's first row w0, and the Philox
+// block of a visit, ng + w0 G + g_k, is never formed: the record holds
+// add = M0 (w0 G + g_k), and round 0's product is M0 ng + add, the multiply
+// round 0 needs anyway with the record's pair as its addend
+// (cwq_philox_lo.h; ng + w0 G + g_k is a real block index below 2^32, so the
+// 64-bit sum does not wrap).  The part w0 G is the wave's own, hence a record
+// set per wave.  Without the fold add is g_k itself.
 struct VisitRec {
-  float4 sa, sb;  // a_j = RN(sa z' + sb) of the group's four dims
-  int grp;        // Philox group of this visit position
-  int bk;         // bits of B_{k+1}
-  int next;       // byte offset of the next visit position's record; 0 in the last
-  int pad;
+  float4 sa, sb;     // a_j = RN(sa z' + sb) of the group's four dims
+  uint32_t add[2];   // round 0's addend (low, high word), or {g_k, 0}
+  int bk;            // bits of B_{k+1}
+  int next;          // byte offset of the next visit position's record; 0 in the last
 };
 static_assert(sizeof(VisitRec) == 48, "VisitRec: 48 bytes");
 
@@ -301,6 +325,12 @@ struct TauGuessWaveDims {
     return o;
   }
 };
+// a 64-bit value that is in scalar registers already, marked wave-uniform
+__device__ __forceinline__ uint64_t sgpr_pair_uniform(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
 // qm_cell's test value (allow_screen bits 1-2 == 2): tau_g = FLT_MAX, which no
 // row reaches, so every screened tile takes the retry
 constexpr float kTauForceRetry = -2.0f;
@@ -329,7 +359,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
   constexpr int RW = (64 / G) < 8 ? (64 / G) : 8;
   __shared__ double logtab[32];
   __shared__ float4 cst[G * NF];     // constants of the k-th visited group
-  __shared__ VisitRec vrec[G];       // screening pass: all it reads at the k-th visited group
+  // screening pass: all it reads at the k-th visited group; set w is wave w's
+  constexpr int NREC = CWQ_FOLD_ROUND0 ? 4 : 1;
+  __shared__ VisitRec vrec[NREC * G];
+  __shared__ uint32_t w0g_cell[4];   // per wave: its first row's Philox block (the loops' rare paths)
   __shared__ int2 meta[G];           // {Philox group of visit k, bits of B_{k+1}}
   __shared__ float rowbuf[4][RW * D];  // per wave: the terms of RW survivor rows
   __shared__ float dscore[D];
@@ -447,8 +480,18 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       }
       gpos[q] = r;
       meta[r].x = q;
-      vrec[r].grp = q;
-      vrec[r].next = r + 1 < G ? (r + 1) * (int)sizeof(VisitRec) : 0;
+#pragma unroll
+      for (int w = 0; w < NREC; ++w) {
+        // wave w's first row is n0 + w per_wave (as below); a wave whose share
+        // is empty reads no record, so a product that wraps there is harmless
+        const uint32_t wg = (uint32_t)(n0 + (int64_t)w * ((n1 - n0 + 3) / 4)) * (uint32_t)G;
+        const uint64_t add =
+            CWQ_FOLD_ROUND0 ? cwq::philox_round0_addend(wg + (uint32_t)q) : (uint64_t)q;
+        VisitRec& v = vrec[w * G + r];
+        v.add[0] = (uint32_t)add;
+        v.add[1] = (uint32_t)(add >> 32);
+        v.next = r + 1 < G ? (w * G + r + 1) * (int)sizeof(VisitRec) : 0;
+      }
     }
     __syncthreads();
     // (d) constants in visit order (reloaded: nothing is held across the syncs)
@@ -470,9 +513,12 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       den_ok = markstein_ok_den(sgj) ? 1 : 0;
       // screening constants; the gate includes den_ok's test of sigma
       const ScreenDim o = screen_dim<STEP0>(fj[0], fj[1], fj[2], sgj, fj[4], fj[6]);
-      float* sc = reinterpret_cast<float*>(&vrec[k]);
-      sc[w] = o.sa;
-      sc[4 + w] = o.sb;
+#pragma unroll
+      for (int c = 0; c < NREC; ++c) {
+        float* sc = reinterpret_cast<float*>(&vrec[c * G + k]);
+        sc[w] = o.sa;
+        sc[4 + w] = o.sb;
+      }
       dA[j] = o.A;
       dC[j] = o.C;
       scr_ok = o.ok ? 1 : 0;
@@ -533,7 +579,8 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
                                 : round_up_f32(rf + 0x1p-14 * kk + marg);
         if (kb >= 1) {
           meta[kb - 1].y = (int)f2u(bk);
-          vrec[kb - 1].bk = (int)f2u(bk);
+#pragma unroll
+          for (int c = 0; c < NREC; ++c) vrec[c * G + kb - 1].bk = (int)f2u(bk);
         }
         if (kb == G) lowc = round_up_f32(0x1p-14 * kk + marg);
       } else if (screen) {  // As, Pq with this kernel's fixed 2^-14 slack
@@ -570,46 +617,72 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     const int64_t w0 = n0 + (int64_t)wv * per_wave;
     const int64_t w1 = (w0 + per_wave < n1) ? w0 + per_wave : n1;
     // A lane carries its row as ng = (n - w0) * G, the row's first Philox block
-    // relative to the wave's: the block of a visit is then one add (ng + group
-    // + w0g), the range test one compare with ng_end, and the refill one
-    // shift-add or mad.  Rows and Philox blocks stay below 2^32 in this kernel
-    // (launch_prune_t), and w0g + ng + group is taken mod 2^32 like n * G +
-    // group; ng itself stays below (per_wave + 128) * G, far below 2^32 (a
-    // wave's share is a quarter of a tile; see the refill below).  The
-    // wave-uniform values are made scalar once per tile, so the loop's
-    // counters run on the SALU.
+    // relative to the wave's.  The block of a visit, ng + w0g + group, is
+    // formed inside round 0's multiply-add from the wave's records (VisitRec;
+    // without CWQ_FOLD_ROUND0 by one v_add3), the range test is one compare
+    // with ng_end, and the refill one mad.  Rows and Philox blocks stay below
+    // 2^32 in this kernel (launch_prune_t); ng itself stays below
+    // (per_wave + 128) * G, far below 2^32 (a wave's share is a quarter of a
+    // tile), except in a lane that has just run out of static rows (below).
+    // The wave-uniform values are made scalar once per tile, so the loop's
+    // counters run on the SALU.  w0g is kept in LDS for the places that need
+    // it outside the screening loop's common path (a survivor's row, the
+    // exact pass), so that it holds no scalar register across the loop.
     const uint32_t w0g =
         (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)w0 * (uint32_t)G));
+    if (lane == 0) w0g_cell[wv] = w0g;  // read by this wave only: LDS keeps a wave's order
     const uint32_t wrows = w1 > w0 ? (uint32_t)(w1 - w0) : 0u;  // R, the wave's share
     const uint32_t ng_end =
         (uint32_t)__builtin_amdgcn_readfirstlane((int)(wrows * (uint32_t)G));
     // Static-stride refill (cwq_refill.h).  The first S = refill_static_rows(R)
     // rows of the share are handed out without any lane arithmetic: lane l
-    // owns rows l, l + 64, ... below S, and a finished lane moves on with
-    // ng += 64 G.  The rows [S, R) are the dynamic pool, handed to finished
-    // lanes by rank from the wave-uniform counter wnext_g, which starts at
-    // refill_pool_start(S) * G.  ng_stat = S * G.
+    // owns rows l, l + 64, ... below S.  The rows [S, R) are the dynamic pool,
+    // handed to finished lanes by rank from the wave-uniform counter wnext_g,
+    // which starts at refill_pool_start(S) * G.  ng_stat = S * G.
+    //
+    // CWQ_BORROW_REFILL: a lane takes its static rows from the last one down.
+    // It starts on row l + S - 64 (row l when S = 0) and a finished lane moves
+    // on with ng -= 64 G; the subtract borrows exactly when ng was below 64 G,
+    // that is on row l, the lane's last static row.  The borrow bits of the
+    // finished lanes go into the scalar mask `left` of the lanes that have
+    // left the static region (all ones from the start when S = 0), and the
+    // finished lanes of `left` take pool rows in the same iteration.
     //   * Every row of [0, R) is started by exactly one lane, and no row
     //     outside it: the static rows of different lanes are disjoint by
     //     construction (S is a multiple of 64, so each lane owns S / 64 of
-    //     them), a lane's ng reaches or passes ng_stat only when its last
-    //     static row is done, and from then on it takes pool rows only, which
-    //     the rank arithmetic hands out once each (refill_sim.cpp replays
-    //     this on the host).  A row at or past ng_end makes its lane inactive.
-    //   * With S = 0 (R < 128: tiles of 256 candidates, short tail tiles)
-    //     every lane starts on row `lane`, ng >= ng_stat = 0 always holds and
-    //     every finished lane refills from the pool, which starts at row 64.
-    //   * ng + 64 G cannot wrap: a lane's ng is below ng_end + 64 G before the
-    //     add (static rows are below ng_stat <= ng_end, pool rows below
-    //     wnext_g + 64 G with wnext_g kept at or below ng_end), and ng_end
-    //     is at most a quarter of a tile's Philox blocks, far below 2^32.
+    //     them, and walks them all: l + S - 64, ..., l + 64, l), a lane enters
+    //     `left` only when its row l is done, and from then on it takes pool
+    //     rows only, which the rank arithmetic hands out once each
+    //     (tests/native/refill_desc_sim.cpp replays this on the host).  A row
+    //     at or past ng_end makes its lane inactive.
+    //   * The only wrap is that borrow.  Outside `left` ng >= 64 G before
+    //     every subtract but the last, which leaves ng + 2^32 - 64 G in a lane
+    //     that is then in `left` and finished, so the pool branch of the same
+    //     iteration overwrites it before anything reads it.  Inside `left` a
+    //     finished lane's subtract may wrap too (an inactive lane's ng_end
+    //     below 64 G; pool rows are not): such a lane is again finished and in
+    //     `left`, and overwritten likewise; its borrow bit changes nothing.
+    //     The subtract's carry-out is ANDed with the finished lanes' mask: what
+    //     it holds for the other lanes is not relied on.
+    //   * wnext_g is kept at or below ng_end (rows from there on are out of
+    //     range alike), so a pool row is below ng_end + 64 G: ng_end is at most
+    //     a quarter of a tile's Philox blocks, far below 2^32.  Only a pool
+    //     row can be out of range (static rows are below ng_stat <= ng_end),
+    //     so the range test is taken in the pool branch only.
     //   * Which lane scores a row, and when, changes nothing else: tau stays
     //     wave-uniform (the keep branch and the share are as they were), and
     //     a survivor's row is n = (w0g + ng) / G as before.
+    // Without CWQ_BORROW_REFILL the static rows go upwards (ng += 64 G from
+    // row l) and a compare with ng_stat per iteration finds the lanes past them.
     const uint32_t ng_stat = (uint32_t)__builtin_amdgcn_readfirstlane(
         (int)(cwq::refill_static_rows(wrows) * (uint32_t)G));
     const uint32_t ng_pool0 = (uint32_t)__builtin_amdgcn_readfirstlane(
         (int)(cwq::refill_pool_start(cwq::refill_static_rows(wrows)) * (uint32_t)G));
+    // lane 0's first row: S - 64 going down (0 when S = 0), 0 going up
+    const uint32_t ng_first =
+        (CWQ_BORROW_REFILL && ng_stat != 0u) ? ng_stat - 64u * (uint32_t)G : 0u;
+    // the wave's records start here (bytes)
+    const uint32_t kbase = CWQ_FOLD_ROUND0 ? wv * (uint32_t)(G * sizeof(VisitRec)) : 0u;
 #ifndef CWQ_TAU_FROM_KEYS
 #define CWQ_TAU_FROM_KEYS 1  // INTER: start the lanes' tau at keys[g]'s value, not at the first share
 #endif
@@ -637,11 +710,20 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       // its VisitRec, the exact pass as the index k of meta[k] and cst
       constexpr uint32_t KS = SCREEN ? (uint32_t)sizeof(VisitRec) : 1u;
       constexpr bool LINKED = SCREEN && CWQ_LINKED_VISIT;
-      uint32_t ng = lane * (uint32_t)G;
+      uint32_t ng = ng_first + lane * (uint32_t)G;
       uint32_t wnext_g = ng_pool0;  // (next unassigned pool row - w0) * G: wave-uniform
-      uint32_t kp = 0;
+      // lanes that have left the static region (CWQ_BORROW_REFILL): wave-uniform
+      // (opaque, so that it starts in scalar registers: begun in a VGPR pair,
+      // the whole chain of ORs and ANDs below was moved to the VALU)
+      uint64_t left;
+      asm volatile("s_cmp_eq_u32 %1, 0\n\ts_cselect_b64 %0, -1, 0" : "=s"(left) : "s"(ng_stat) : "scc");
+      const uint32_t kb = SCREEN ? kbase : 0u;  // the first visit position
+      uint32_t kp = kb;
       float s = 0.0f;
       uint32_t iter = 0;
+      // the exact pass forms its blocks with a plain add
+      uint32_t w0g_x = 0u;
+      if constexpr (!SCREEN || !CWQ_FOLD_ROUND0) w0g_x = w0g;
       // a lane is active while its row is in the wave's range: the compare is
       // taken in the pool refill only (static rows are in range), its mask
       // carried in SGPRs.  The loop's only exit is at its end, so its
@@ -652,24 +734,36 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         int2 mt;
         float4 sa, sb;
         uint32_t kp_next = 0;
+        uint64_t p0;  // round 0's product of this visit's Philox block
         if constexpr (SCREEN) {
           const char* rp = reinterpret_cast<const char*>(vrec) + kp;
           sa = *reinterpret_cast<const float4*>(rp);
           sb = *reinterpret_cast<const float4*>(rp + 16);
-          const int4 lk = *reinterpret_cast<const int4*>(rp + 32);
-          mt = int2{lk.x, lk.y};
-          kp_next = (uint32_t)lk.z;
+          typedef int v4i __attribute__((ext_vector_type(4)));
+          v4i lk = *reinterpret_cast<const v4i*>(rp + 32);
+          // the four words through an opaque move: where the addend is seen
+          // as one 64-bit value, the 16-byte read is split in two 8-byte
+          // ones, whose offsets no longer fit the record's address register
+          if constexpr (CWQ_FOLD_ROUND0) asm volatile("" : "+v"(lk));
+          mt = int2{lk.x, lk.z};
+          kp_next = (uint32_t)lk.w;
+          if constexpr (CWQ_FOLD_ROUND0) {
+            p0 = cwq::philox_round0_product(
+                ng, (uint64_t)(uint32_t)lk.x | ((uint64_t)(uint32_t)lk.y << 32));
+          } else {
+            p0 = (uint64_t)kPhiloxM0 * ((ng + (uint32_t)mt.x) + w0g_x);
+          }
         } else {
           mt = meta[kp];
+          p0 = (uint64_t)kPhiloxM0 * ((ng + (uint32_t)mt.x) + w0g_x);
         }
-        const uint32_t grp = (ng + (uint32_t)mt.x) + w0g;
         // the key through an opaque move each iteration: the fourteen round
         // keys are then formed here by scalar adds, not held in SGPRs across
         // the loop, where they pushed the loop's lane masks and counters out
         // into VGPR lanes (v_writelane / v_readlane every iteration)
         uint32_t pk0 = st.k0, pk1 = st.k1;
         asm volatile("" : "+s"(pk0), "+s"(pk1));
-        const U4 x = philox10_lo(grp, lok, pk0, pk1);
+        const U4 x = philox10_lo_p0(p0, lok, pk0, pk1);
         float z0, z1, z2, z3;
         float upper;
         if constexpr (SCREEN) {
@@ -722,7 +816,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           kp = kp_next;
         else
           kp += KS;
-        const bool complete = LINKED ? (kp == 0u) : (kp == KS * (uint32_t)G);
+        const bool complete = LINKED ? (kp == 0u) : (kp == kb + KS * (uint32_t)G);
         const bool below = upper < tau;
         // Screening pass: one compare of (upper, tau) serves the drop test and
         // the keep test, !(upper < tau) == (upper >= tau), because neither is
@@ -740,7 +834,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         const bool reach = SCREEN ? !below : (upper >= tau);
 #ifdef CWQ_PRUNE_STATS
         const bool prune = !complete && below;
-        const uint32_t k = (LINKED && complete) ? (uint32_t)G : kp / KS;
+        const uint32_t k = (LINKED && complete) ? (uint32_t)G : (kp - kb) / KS;
 #endif
         const bool done = complete || below || !active;
         // the finished lanes' mask from the compares' own masks (SALU).  The
@@ -773,7 +867,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         //     NaN lower (s = +inf) is left out of the max and the row, whose
         //     upper is +inf, is pushed.
         if (__builtin_expect(m_keep != 0ull, 0)) {
-          const bool keep = complete && active && reach;
+          // (going down, `active` is carried as the scalar m_act alone: the
+          // lane's bit of m_keep is complete && active && reach)
+          const bool keep = CWQ_BORROW_REFILL ? ((m_keep >> lane) & 1ull) != 0ull
+                                              : (complete && active && reach);
           float lower;
           if constexpr (SCREEN)
             lower = screen_row_lower(s, kScreenC2, sA, sPq);
@@ -782,10 +879,13 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           tau = tau_raise_wave(tau, keep, lower);
           if (__builtin_expect(keep && upper >= tau, 0)) {
             // the row, n = (w0g + ng) / G (exact: n * G < 2^32), from an opaque
-            // copy of ng, so that w0g + ng is not shared with the loop's grp
+            // copy of ng, so that w0g + ng is not shared with the loop's grp,
+            // and w0g from the wave's cell, not from a register held across
+            // the loop
             uint32_t ngc = ng;
             asm volatile("" : "+v"(ngc));
-            const uint32_t n = (w0g + ngc) / (uint32_t)G;
+            const uint32_t n =
+                (*const_cast<const volatile uint32_t*>(&w0g_cell[wv]) + ngc) / (uint32_t)G;
 #ifdef CWQ_PRUNE_STATS
             atomicAdd(&s_ps[66], 1u);
 #endif
@@ -806,43 +906,108 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           }
         }
 #ifdef CWQ_PRUNE_STATS
-        if (active && (complete || prune)) atomicAdd(&s_ps[k], 1u);
-        if (active && complete) atomicAdd(&s_ps[65], 1u);
+        const bool act_l = ((m_act >> lane) & 1ull) != 0ull;
+        if (act_l && (complete || prune)) atomicAdd(&s_ps[k], 1u);
+        if (act_l && complete) atomicAdd(&s_ps[65], 1u);
 #endif
-        // a finished lane steps to its next static row.  The empty asm keeps
-        // this a branch on the exec mask (one add and two moves under it):
-        // turned into selects it is an add and three v_cndmask for all lanes
-        if (done) {
-          asm volatile("" : "+v"(ng));
-          ng += 64u * (uint32_t)G;
-          kp = 0;
-          s = 0.0f;
+        uint64_t m_pool;
+        if constexpr (CWQ_BORROW_REFILL) {
+          // a finished lane steps down to its next static row: one subtract
+          // and two moves with the exec mask set to the finished lanes (full
+          // on entry, as everywhere in this loop).  Written out, because the
+          // subtract's borrow is wanted as a scalar pair: it marks the lanes
+          // that were on their last static row.  Only the finished lanes'
+          // bits of it are used (the first s_and_b64).  `left` and m_pool are
+          // formed here too: left as C++ ORs and ANDs, the chain was moved to
+          // the VALU (two v_or, two v_and, a 64-bit v_cmp, two v_readfirstlane).
+          // The exec mask is full here, so it is set back to -1, not saved.
+          asm volatile(
+              "s_mov_b64 exec, %[m]\n\t"
+              "v_subrev_co_u32 %[ng], vcc, %[c], %[ng]\n\t"
+              "v_mov_b32 %[kp], %[kb]\n\t"
+              "v_mov_b32 %[s], 0\n\t"
+              "s_mov_b64 exec, -1\n\t"
+              "s_and_b64 %[mp], vcc, %[m]\n\t"
+              "s_or_b64 %[left], %[left], %[mp]\n\t"
+              "s_and_b64 %[mp], %[left], %[m]"
+              : [ng] "+v"(ng), [kp] "+v"(kp), [s] "+v"(s), [mp] "=&s"(m_pool),
+                [left] "+s"(left)
+              : [m] "s"(m), [c] "n"(64 * G), [kb] "s"(kb)
+              : "vcc", "scc");
+          // the compiler takes a scalar output of a statement that also has
+          // vector outputs for a per-lane value once it crosses a block (a
+          // 64-bit v_cmp for the branch below, the masks in VGPRs);
+          // readfirstlane tells it otherwise and folds to a scalar copy
+          left = sgpr_pair_uniform(left);
+          m_pool = sgpr_pair_uniform(m_pool);
+        } else {
+          // a finished lane steps to its next static row.  The empty asm keeps
+          // this a branch on the exec mask (one add and two moves under it):
+          // turned into selects it is an add and three v_cndmask for all lanes
+          if (done) {
+            asm volatile("" : "+v"(ng));
+            ng += 64u * (uint32_t)G;
+            kp = kb;
+            s = 0.0f;
+          }
+          m_pool = 0ull;
         }
         // share tau across the workgroup's waves: it is wave-uniform already,
         // so one returning LDS max by lane 0 and one v_max, no reduce (and no
         // "raised since the last share" flag: both of its arms would be this)
         if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) tau = tau_share_wave(&tau_cell, tau);
         // Pool refill, taken by the whole wave when a finished lane has left
-        // its static rows (or was in the pool, or inactive: ng >= ng_stat):
-        // those lanes take pool rows by rank, and the range test, which only a
-        // pool row can fail, is taken here.  Lanes still on a row keep their
-        // ng: static rows are below ng_stat <= ng_end, pool rows in progress
-        // passed the test when they were handed out, inactive lanes are all
-        // finished lanes, so the compare gives every lane's `active` anew.
-        // wnext_g is kept at or below ng_end (rows from there on are out of
-        // range alike), which bounds ng however long lanes stay inactive.
-        const uint64_t m_pool = m & __builtin_amdgcn_uicmp(ng, ng_stat, 35 /* uge */);
-        if (m_pool != 0ull) {
+        // its static rows (or was in the pool, or inactive): those lanes take
+        // pool rows by rank, and the range test, which only a pool row can
+        // fail, is taken here.  Lanes still on a row keep their ng: static
+        // rows are below ng_stat <= ng_end, pool rows in progress passed the
+        // test when they were handed out, inactive lanes are all finished
+        // lanes (and in `left`: a lane becomes inactive on a pool row, or
+        // starts so when S = 0), so the compare gives every lane's `active`
+        // anew.  wnext_g is kept at or below ng_end (rows from there on are
+        // out of range alike), which bounds ng however long lanes stay inactive.
+        if constexpr (CWQ_BORROW_REFILL) {
+          if (m_pool != 0ull) {
 #ifdef CWQ_PRUNE_STATS
-          if (lane == 0) atomicAdd(&s_ps[70], 1u);
+            if (lane == 0) atomicAdd(&s_ps[70], 1u);
 #endif
-          const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
-              (uint32_t)(m_pool >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_pool, 0u));
-          if (done && ng >= ng_stat) ng = wnext_g + rank * (uint32_t)G;
-          wnext_g += (uint32_t)__builtin_popcountll(m_pool) * (uint32_t)G;
-          wnext_g = wnext_g < ng_end ? wnext_g : ng_end;
-          active = ng < ng_end;
-          m_act = __builtin_amdgcn_ballot_w64(active);
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
+                (uint32_t)(m_pool >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_pool, 0u));
+            // ng = wnext_g + rank G in the lanes of m_pool, the others' kept:
+            // one mad under that exec mask (rank <= 63 and G <= 16: 24-bit
+            // factors), instead of a mad for all lanes and a select
+            asm volatile(
+                "s_mov_b64 exec, %[mp]\n\t"
+                "v_mad_u32_u24 %[ng], %[rank], %[g], %[wn]\n\t"
+                "s_mov_b64 exec, -1"
+                : [ng] "+v"(ng)
+                : [mp] "s"(m_pool), [rank] "v"(rank), [g] "n"(G), [wn] "s"(wnext_g));
+            // the rows handed out are wnext_g .. want - G: all in range when
+            // want <= ng_end, and then the lanes of m_pool are active and the
+            // other lanes' state is what it was (no compare)
+            const uint32_t want = wnext_g + (uint32_t)__builtin_popcountll(m_pool) * (uint32_t)G;
+            if (CWQ_POOL_RANGE_SKIP && want <= ng_end) {
+              wnext_g = want;
+              m_act |= m_pool;
+            } else {
+              wnext_g = want < ng_end ? want : ng_end;
+              m_act = __builtin_amdgcn_uicmp(ng, ng_end, 36 /* ult */);
+            }
+          }
+        } else {
+          m_pool = m & __builtin_amdgcn_uicmp(ng, ng_stat, 35 /* uge */);
+          if (m_pool != 0ull) {
+#ifdef CWQ_PRUNE_STATS
+            if (lane == 0) atomicAdd(&s_ps[70], 1u);
+#endif
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
+                (uint32_t)(m_pool >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_pool, 0u));
+            if (done && ng >= ng_stat) ng = wnext_g + rank * (uint32_t)G;
+            wnext_g += (uint32_t)__builtin_popcountll(m_pool) * (uint32_t)G;
+            wnext_g = wnext_g < ng_end ? wnext_g : ng_end;
+            active = ng < ng_end;
+            m_act = __builtin_amdgcn_ballot_w64(active);
+          }
         }
 #ifdef CWQ_PRUNE_STATS
         if (lane == 0) atomicAdd(&s_ps[71], 1u);
