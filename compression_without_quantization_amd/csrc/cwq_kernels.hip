@@ -200,6 +200,24 @@ constexpr float kPruneC1 = 0x1p-14f;
 // that every row handed out is in range (CWQ_BORROW_REFILL builds); 0: always compares
 #define CWQ_POOL_RANGE_SKIP 1
 #endif
+#ifndef CWQ_PARK_COMPLETE
+// in tiles of CWQ_PARK_MIN_ROWS rows or more at d = 32, of as many Philox
+// blocks at other d, of blocks of CWQ_PARK_MIN_D dims or more (the kernel's
+// PARK instances; the rule is launch_prune_t's) a row that has passed its last visit position is not looked for every
+// iteration: it walks on to a sentinel record and waits there for the
+// iteration that shares tau, which finds it (k_encode_prune); 0: every tile
+// takes the completion compare per iteration (A/B builds)
+#define CWQ_PARK_COMPLETE 1
+#endif
+#ifndef CWQ_PARK_MIN_ROWS
+#define CWQ_PARK_MIN_ROWS 8192
+#endif
+#ifndef CWQ_PARK_MIN_D
+#define CWQ_PARK_MIN_D 16  // ... and of blocks of at least this many dims (launch_prune_t)
+#endif
+#if CWQ_PARK_COMPLETE && !(CWQ_LINKED_VISIT && CWQ_BORROW_REFILL)
+#error "CWQ_PARK_COMPLETE needs CWQ_LINKED_VISIT and CWQ_BORROW_REFILL"
+#endif
 
 // best + (loc_s + scale_s z) - mu  (misc.py:14-15, coded_greedy_sampler.py:57, TFP _z numerator)
 template <bool STEP0>
@@ -343,7 +361,9 @@ __device__ __forceinline__ float tau_guess_of(float qm, float As, float Pq) {
   return tg == tg ? tg : -__builtin_inff();
 }
 
-template <int D, bool STEP0, bool INTER>
+// PARK: the screening loop without its per-iteration completion test
+// (CWQ_PARK_COMPLETE; chosen per launch from the rows per tile, launch_prune_t)
+template <int D, bool STEP0, bool INTER, bool PARK>
 __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     const float* __restrict__ t_loc, const float* __restrict__ t_scale,
     const float* __restrict__ loc_s, const float* __restrict__ scale_s,
@@ -352,6 +372,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     int allow_screen, unsigned long long* __restrict__ keys, int64_t tail_from, int tail_div,
     uint32_t* __restrict__ tq) {
   static_assert(D % 8 == 0 && D >= 8 && D <= 64, "pruned path: D % 8 == 0, D <= 64");
+  static_assert(!PARK || CWQ_PARK_COMPLETE, "PARK instances exist in CWQ_PARK_COMPLETE builds only");
   constexpr int G = D / 4;
   constexpr int NF = STEP0 ? 6 : 7;  // loc_s, scale_s, mu, sigma, c, 1/sigma[, best]
   // survivor rows one wave scores per pass: a lane per Philox block of a row,
@@ -361,7 +382,14 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
   __shared__ float4 cst[G * NF];     // constants of the k-th visited group
   // screening pass: all it reads at the k-th visited group; set w is wave w's
   constexpr int NREC = CWQ_FOLD_ROUND0 ? 4 : 1;
-  __shared__ VisitRec vrec[NREC * G];
+  // PARK: each set ends in a sentinel record, which the last visit position
+  // links to and which links to itself.  Its sa and sb are 0, so a visit
+  // leaves s as it is (a = fma(0, z', 0) = 0 for the finite z', s = fma(-0, 0,
+  // s) = s), and its B is +inf, so upper = fma(s, c1, +inf) = +inf is below no
+  // tau (s is finite): a row that gets there has completed, and waits with its
+  // s and its ng until it is found.
+  constexpr int RPW = G + (PARK ? 1 : 0);  // records per set
+  __shared__ VisitRec vrec[NREC * RPW];
   __shared__ uint32_t w0g_cell[4];   // per wave: its first row's Philox block (the loops' rare paths)
   __shared__ int2 meta[G];           // {Philox group of visit k, bits of B_{k+1}}
   __shared__ float rowbuf[4][RW * D];  // per wave: the terms of RW survivor rows
@@ -487,11 +515,21 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         const uint32_t wg = (uint32_t)(n0 + (int64_t)w * ((n1 - n0 + 3) / 4)) * (uint32_t)G;
         const uint64_t add =
             CWQ_FOLD_ROUND0 ? cwq::philox_round0_addend(wg + (uint32_t)q) : (uint64_t)q;
-        VisitRec& v = vrec[w * G + r];
+        VisitRec& v = vrec[w * RPW + r];
         v.add[0] = (uint32_t)add;
         v.add[1] = (uint32_t)(add >> 32);
-        v.next = r + 1 < G ? (w * G + r + 1) * (int)sizeof(VisitRec) : 0;
+        // the last position links to 0, or to the set's sentinel (PARK)
+        v.next = (r + 1 < G || PARK) ? (w * RPW + r + 1) * (int)sizeof(VisitRec) : 0;
       }
+    }
+    if (PARK && tid >= 64 && tid < 64 + NREC) {  // the sentinels (any Philox block will do: add 0)
+      VisitRec& v = vrec[(tid - 64) * RPW + G];
+      v.sa = float4{0.f, 0.f, 0.f, 0.f};
+      v.sb = float4{0.f, 0.f, 0.f, 0.f};
+      v.add[0] = 0u;
+      v.add[1] = 0u;
+      v.bk = (int)f2u(__builtin_inff());
+      v.next = (int)((tid - 64) * RPW + G) * (int)sizeof(VisitRec);
     }
     __syncthreads();
     // (d) constants in visit order (reloaded: nothing is held across the syncs)
@@ -515,7 +553,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       const ScreenDim o = screen_dim<STEP0>(fj[0], fj[1], fj[2], sgj, fj[4], fj[6]);
 #pragma unroll
       for (int c = 0; c < NREC; ++c) {
-        float* sc = reinterpret_cast<float*>(&vrec[c * G + k]);
+        float* sc = reinterpret_cast<float*>(&vrec[c * RPW + k]);
         sc[w] = o.sa;
         sc[4 + w] = o.sb;
       }
@@ -580,7 +618,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         if (kb >= 1) {
           meta[kb - 1].y = (int)f2u(bk);
 #pragma unroll
-          for (int c = 0; c < NREC; ++c) vrec[c * G + kb - 1].bk = (int)f2u(bk);
+          for (int c = 0; c < NREC; ++c) vrec[c * RPW + kb - 1].bk = (int)f2u(bk);
         }
         if (kb == G) lowc = round_up_f32(0x1p-14 * kk + marg);
       } else if (screen) {  // As, Pq with this kernel's fixed 2^-14 slack
@@ -682,7 +720,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     const uint32_t ng_first =
         (CWQ_BORROW_REFILL && ng_stat != 0u) ? ng_stat - 64u * (uint32_t)G : 0u;
     // the wave's records start here (bytes)
-    const uint32_t kbase = CWQ_FOLD_ROUND0 ? wv * (uint32_t)(G * sizeof(VisitRec)) : 0u;
+    const uint32_t kbase = CWQ_FOLD_ROUND0 ? wv * (uint32_t)(RPW * sizeof(VisitRec)) : 0u;
 #ifndef CWQ_TAU_FROM_KEYS
 #define CWQ_TAU_FROM_KEYS 1  // INTER: start the lanes' tau at keys[g]'s value, not at the first share
 #endif
@@ -710,6 +748,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       // its VisitRec, the exact pass as the index k of meta[k] and cst
       constexpr uint32_t KS = SCREEN ? (uint32_t)sizeof(VisitRec) : 1u;
       constexpr bool LINKED = SCREEN && CWQ_LINKED_VISIT;
+      // the screening pass of a PARK instance: completed rows wait at the
+      // sentinel record (see "Parked rows" in the loop)
+      constexpr bool PARKED = SCREEN && PARK && CWQ_PARK_COMPLETE;
       uint32_t ng = ng_first + lane * (uint32_t)G;
       uint32_t wnext_g = ng_pool0;  // (next unassigned pool row - w0) * G: wave-uniform
       // lanes that have left the static region (CWQ_BORROW_REFILL): wave-uniform
@@ -735,6 +776,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         float4 sa, sb;
         uint32_t kp_next = 0;
         uint64_t p0;  // round 0's product of this visit's Philox block
+#ifdef CWQ_PRUNE_STATS
+        const uint32_t kp_was = kp;
+#endif
         if constexpr (SCREEN) {
           const char* rp = reinterpret_cast<const char*>(vrec) + kp;
           sa = *reinterpret_cast<const float4*>(rp);
@@ -816,7 +860,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           kp = kp_next;
         else
           kp += KS;
-        const bool complete = LINKED ? (kp == 0u) : (kp == kb + KS * (uint32_t)G);
+        // (PARKED: the last position links to the sentinel and no lane tests
+        // for it here; see "Parked rows" below)
+        const bool complete =
+            PARKED ? false : (LINKED ? (kp == 0u) : (kp == kb + KS * (uint32_t)G));
         const bool below = upper < tau;
         // Screening pass: one compare of (upper, tau) serves the drop test and
         // the keep test, !(upper < tau) == (upper >= tau), because neither is
@@ -833,8 +880,12 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // both compares: a NaN row is neither dropped early nor kept.
         const bool reach = SCREEN ? !below : (upper >= tau);
 #ifdef CWQ_PRUNE_STATS
-        const bool prune = !complete && below;
-        const uint32_t k = (LINKED && complete) ? (uint32_t)G : (kp - kb) / KS;
+        // (PARKED: the stats build keeps a completion compare of its own, true
+        // in the iteration in which the row leaves its last real position)
+        const bool complete_st =
+            PARKED ? (kp == kb + KS * (uint32_t)G && kp_was != kb + KS * (uint32_t)G) : complete;
+        const bool prune = !complete_st && below;
+        const uint32_t k = (LINKED && complete_st) ? (uint32_t)G : (kp - kb) / KS;
 #endif
         const bool done = complete || below || !active;
         // the finished lanes' mask from the compares' own masks (SALU).  The
@@ -866,16 +917,52 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         //     ordered compare), so it is neither dropped above nor pushed here; a
         //     NaN lower (s = +inf) is left out of the max and the row, whose
         //     upper is +inf, is pushed.
-        if (__builtin_expect(m_keep != 0ull, 0)) {
+        //
+        // Parked rows (PARKED).  The loop has no completion test: a row that
+        // passes its last real position without falling below tau there (the
+        // ordinary test, with the full row's B) walks on to the sentinel and
+        // stays there, active, with its s and ng unchanged, its upper end +inf
+        // and so never below.  The iteration that shares tau
+        // (every CWQ_TAU_SHARE_MASK + 1) compares kp with the sentinel's offset:
+        // the lanes at it that are active and did not just drop are the
+        // completed rows not yet seen (a lane that dropped at its last real
+        // position has kp there too and is in m_below: it is finished the
+        // ordinary way).  They take this same keep step, each exactly once,
+        // and are ORed into that iteration's done mask, so the step and the
+        // resets below move them on.  A wave cannot leave the loop with a row
+        // parked, since a parked lane is active, and the pass's final share
+        // comes after the loop, so after the last of these steps.  With tau
+        // raised up to CWQ_TAU_SHARE_MASK iterations later than before:
+        //   * tau is still only raised to lower ends of rows completed in this
+        //     tile, later: it stays a lower bound of such a row's exact value;
+        //   * a row is dropped on upper < tau at a real position only, as
+        //     before, against a tau that is at most what it was before there;
+        //   * a row whose exact value equals the best row's has upper >= every
+        //     tau of the pass, so it is dropped nowhere, parks, and is pushed
+        //     when found, whichever tau the wave has by then;
+        //   * which rows are pushed may differ (a later push meets a higher
+        //     tau); the survivors' exact values, and so the result, do not.
+        // A parked lane idles for at most CWQ_TAU_SHARE_MASK iterations.
+        auto keep_rows = [&](const uint64_t mk) {
           // (going down, `active` is carried as the scalar m_act alone: the
-          // lane's bit of m_keep is complete && active && reach)
-          const bool keep = CWQ_BORROW_REFILL ? ((m_keep >> lane) & 1ull) != 0ull
+          // lane's bit of mk is complete && active && reach)
+          const bool keep = CWQ_BORROW_REFILL ? ((mk >> lane) & 1ull) != 0ull
                                               : (complete && active && reach);
           float lower;
           if constexpr (SCREEN)
             lower = screen_row_lower(s, kScreenC2, sA, sPq);
           else
             lower = (s - __builtin_fabsf(s) * kPruneC1) - lc;
+          // PARKED: the completed row's upper end (the loop's is the
+          // sentinel's +inf by now), from the full row's B in meta (through an
+          // opaque index: read here, not held across the loop) and the row's
+          // s, which nothing has touched since its last unit: the value the
+          // loop formed there
+          if constexpr (PARKED) {
+            uint32_t kf = (uint32_t)G - 1u;
+            asm volatile("" : "+v"(kf));
+            upper = screen_row_upper(s, kScreenC1, u2f((uint32_t)meta[kf].y));
+          }
           tau = tau_raise_wave(tau, keep, lower);
           if (__builtin_expect(keep && upper >= tau, 0)) {
             // the row, n = (w0g + ng) / G (exact: n * G < 2^32), from an opaque
@@ -904,11 +991,23 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
               bestk = kv > bestk ? kv : bestk;
             }
           }
+        };
+        if constexpr (!PARKED) {
+          if (__builtin_expect(m_keep != 0ull, 0)) keep_rows(m_keep);
+        } else {
+          // the share first, so that the parked rows meet the freshest tau
+          if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {
+            tau = tau_share_wave(&tau_cell, tau);
+            const uint64_t m_park =
+                __builtin_amdgcn_uicmp(kp, kb + KS * (uint32_t)G, 32 /* eq */) & m_act & ~m_below;
+            if (__builtin_expect(m_park != 0ull, 0)) keep_rows(m_park);
+            m |= m_park;
+          }
         }
 #ifdef CWQ_PRUNE_STATS
         const bool act_l = ((m_act >> lane) & 1ull) != 0ull;
-        if (act_l && (complete || prune)) atomicAdd(&s_ps[k], 1u);
-        if (act_l && complete) atomicAdd(&s_ps[65], 1u);
+        if (act_l && (complete_st || prune)) atomicAdd(&s_ps[k], 1u);
+        if (act_l && complete_st) atomicAdd(&s_ps[65], 1u);
 #endif
         uint64_t m_pool;
         if constexpr (CWQ_BORROW_REFILL) {
@@ -955,7 +1054,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // share tau across the workgroup's waves: it is wave-uniform already,
         // so one returning LDS max by lane 0 and one v_max, no reduce (and no
         // "raised since the last share" flag: both of its arms would be this)
-        if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) tau = tau_share_wave(&tau_cell, tau);
+        // (PARKED: shared above, with the look for parked rows)
+        if (!PARKED && ((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {
+          tau = tau_share_wave(&tau_cell, tau);
+        }
         // Pool refill, taken by the whole wave when a finished lane has left
         // its static rows (or was in the pool, or inactive): those lanes take
         // pool rows by rank, and the range test, which only a pool row can
@@ -3695,7 +3797,7 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
   if (seeded) {
     const int64_t cpt_s = seed_n < CWQ_SEED_TILE ? (seed_n > 0 ? seed_n : 1) : CWQ_SEED_TILE;
     const int64_t nt_s = a.nb * (seed_n / cpt_s);
-    hipLaunchKernelGGL((k_encode_prune<D, STEP0, true>),
+    hipLaunchKernelGGL((k_encode_prune<D, STEP0, true, false>),
                        dim3((unsigned)(nt_s < kPruneGrid ? nt_s : kPruneGrid)), dim3(256), 0,
                        stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                        nt_s, seed_n / cpt_s, cpt_s, seed_n, seeds_of(a), step,
@@ -3724,6 +3826,26 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
     const int64_t cap = tq ? (int64_t)CWQ_QUEUE_GRID : kPruneGrid;
     return (unsigned)(nt < cap ? nt : cap);
   };
+  // The loop variant (CWQ_PARK_COMPLETE): tiles of CWQ_PARK_MIN_ROWS rows or
+  // more take the instance whose completed rows park.  A parked row idles for
+  // up to CWQ_TAU_SHARE_MASK iterations, which is nothing where a handful of a
+  // tile's rows complete (C4: 15 of 65,536) and a cliff where most do, as in
+  // tiles of a few rows per lane, whose tau has no time to rise, and in rows of
+  // two units (d = 8), which complete whenever their first unit does not drop
+  // them.  Measured on one-tile blocks: d = 32 at 4,096 rows
+  // +0.2%, at 8,192 -0.8%, at 16,384 -1.9%; d = 64 at 8,192 -1.5%; d = 16 at
+  // 8,192 +1.5%, at 16,384 -0.3%; d = 8 at 8,192 +1.7%.  Parking pays from
+  // about 2^16 Philox blocks per tile on, so the threshold is stated in rows of
+  // a d = 32 tile and scaled by 32 / d.  The rows are those of a full tile; the
+  // tail tiles of such a launch are a quarter of it and start from keys[g], the
+  // tiles before them having finished.
+  const int64_t tile_rows = a.cand_per_tile < a.n_cand ? a.cand_per_tile : a.n_cand;
+  auto with_park = [&](auto launch) {
+    if constexpr (CWQ_PARK_COMPLETE && D >= CWQ_PARK_MIN_D) {
+      if (tile_rows * D >= (int64_t)CWQ_PARK_MIN_ROWS * 32) return launch(std::true_type{});
+    }
+    return launch(std::false_type{});
+  };
   if (CWQ_TILE_INTERLEAVE && (a.tiles_per_block > 1 || seeded)) {
     // tail: the last tile of each block's few last tiles split in CWQ_TAIL_SPLIT,
     // about two resident rounds (1,536 workgroups) of short tiles at the end
@@ -3740,16 +3862,21 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
     }
     const int64_t tpb2 = from + (tpb - from) * div;
     const int64_t nt2 = a.nb * tpb2;
-    hipLaunchKernelGGL((k_encode_prune<D, STEP0, true>),
-                       dim3(qgrid(nt2)), dim3(256), 0,
-                       stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
-                       nt2, tpb2, a.cand_per_tile, a.n_cand, seeds_of(a), step,
-                       prune_screen_arg(a), a.keys, from, (int)div, tq);
+    with_park([&](auto park) {
+      hipLaunchKernelGGL((k_encode_prune<D, STEP0, true, decltype(park)::value>),
+                         dim3(qgrid(nt2)), dim3(256), 0,
+                         stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
+                         nt2, tpb2, a.cand_per_tile, a.n_cand, seeds_of(a), step,
+                         prune_screen_arg(a), a.keys, from, (int)div, tq);
+    });
   } else {
-    hipLaunchKernelGGL((k_encode_prune<D, STEP0, false>), dim3(qgrid(ntiles)), dim3(256), 0,
-                       stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
-                       ntiles, a.tiles_per_block, a.cand_per_tile, a.n_cand, seeds_of(a), step,
-                       prune_screen_arg(a), a.keys, a.tiles_per_block, 1, tq);
+    with_park([&](auto park) {
+      hipLaunchKernelGGL((k_encode_prune<D, STEP0, false, decltype(park)::value>),
+                         dim3(qgrid(ntiles)), dim3(256), 0,
+                         stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
+                         ntiles, a.tiles_per_block, a.cand_per_tile, a.n_cand, seeds_of(a), step,
+                         prune_screen_arg(a), a.keys, a.tiles_per_block, 1, tq);
+    });
   }
 }
 
