@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cwq_dispatch.h"
 #include "cwq_math.h"
 #include "cwq_philox_lo.h"
 #include "cwq_screen.h"
@@ -420,11 +421,6 @@ __device__ __forceinline__ float eval_row_f(const PhiloxStream& st, uint64_t kba
   return eigen_fold8(p, t);
 }
 
-static inline unsigned grid_for(int64_t work, int64_t per_block, unsigned cap) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
+// grid_for: cwq_dispatch.h (the decode plan computes launch sizes with it)
 
 }  // namespace cwq

@@ -1,7 +1,9 @@
 // cwq_dispatch.h -- which encoder path one launch_encode call takes, defined
 // once for the workspace layout (cwq_capi.hip), the launchers
 // (cwq_kernels.hip) and the host, where tests/test_encode_plan.py checks a
-// table of shapes against it (DESIGN.md "Encode dispatch").
+// table of shapes against it (DESIGN.md "Encode dispatch"); and which decoder
+// kernel one launch_decode call takes (DESIGN.md "Decode dispatch",
+// tests/test_decode_plan.py).
 //
 // Everything here is a pure function of the call's shape; no pointer is read.
 // Host only: no kernel needs it, and it includes nothing from HIP.
@@ -41,6 +43,9 @@
 #endif
 #ifndef CWQ_SPLIT_FEW
 #define CWQ_SPLIT_FEW 3  // parts of a cooperative (few long rows) launch
+#endif
+#ifndef CWQ_DECODE_GLDS
+#define CWQ_DECODE_GLDS 1  // 0: the register-prefetch decoder for single-step codes too
 #endif
 
 namespace cwq {
@@ -187,6 +192,58 @@ inline BackfitPath backfit_plan(int64_t max_d, int64_t nb) {
   return max_d >= 0 && max_d <= CWQ_FUSED_DMAX && nb >= kBackfitLaneMinBlocks
              ? BackfitPath::LanePerBlock
              : BackfitPath::WavePerBlock;
+}
+
+// ---- greedy decoders (launch_decode, DESIGN.md "Decode dispatch") -----------
+// Workgroups of a grid-stride launch: `per_block` items of `work` each, at
+// least one, at most `cap`.
+inline unsigned grid_for(int64_t work, int64_t per_block, unsigned cap) {
+  int64_t g = (work + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (unsigned)g;
+}
+
+// The float4 lane-per-Philox-block kernels (k_decode_q4, k_decode_q4_glds,
+// k_encode_finalize_q4): uniform d % 4 == 0, d <= 256.
+inline bool q4_shape(bool csr, int64_t ud) {
+  return !csr && ud > 0 && ud % 4 == 0 && ud <= 256;
+}
+
+struct DecodeShape {
+  bool csr;            // ragged blocks (block_off given); false: uniform blocks of ud dims
+  int64_t ud;          // uniform block length (csr: unused)
+  int64_t nb;
+  int64_t total_dims;  // uniform: nb * ud
+  int n_steps;
+  bool aligned16;      // p_loc, p_scale and out_sample all lie on 16-byte boundaries
+};
+
+// General: k_decode, a thread per dim.  Q4: k_decode_q4, a lane per Philox
+// block of a row, inputs prefetched in registers.  Q4Glds: k_decode_q4_glds,
+// the same mapping for single-step codes, inputs streamed through LDS.
+enum class DecodeKernel { General, Q4, Q4Glds };
+
+struct DecodePlan {
+  DecodeKernel kernel;
+  uint32_t qpb, bpw;    // Q4*: Philox blocks per row, blocks per chunk (General: 0)
+  int64_t groups;       // Q4*: wave groups of bpw * qpb blocks (General: 0)
+  unsigned workgroups;  // of 256 threads; 0: nothing to launch (no block)
+};
+
+constexpr unsigned kDecodeGeneralGridCap = 16384;  // k_decode strides over the dims beyond
+constexpr unsigned kDecodeQ4GridCap = 1u << 20;    // the q4 kernels over the groups beyond
+
+inline DecodePlan decode_plan(const DecodeShape& s) {
+  if (s.nb <= 0) return {DecodeKernel::General, 0u, 0u, 0, 0u};
+  if (q4_shape(s.csr, s.ud) && s.aligned16) {
+    const uint32_t qpb = (uint32_t)(s.ud / 4), bpw = 64u / qpb;
+    const int64_t B = (int64_t)bpw * qpb;
+    const int64_t groups = (s.nb + B - 1) / B;
+    return {CWQ_DECODE_GLDS && s.n_steps == 1 ? DecodeKernel::Q4Glds : DecodeKernel::Q4, qpb, bpw,
+            groups, grid_for(groups, 4, kDecodeQ4GridCap)};  // a wave per group
+  }
+  return {DecodeKernel::General, 0u, 0u, 0, grid_for(s.total_dims, 256, kDecodeGeneralGridCap)};
 }
 
 // cwq_greedy_encode_var's bucket rule.  Long rows at few candidates (DESIGN.md

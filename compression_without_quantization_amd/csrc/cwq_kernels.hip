@@ -3276,9 +3276,7 @@ __global__ void __launch_bounds__(256, CWQ_DECODE_MIN_WAVES) k_decode_q4(
 // between can only make it wait longer).  All LDS is one array (logf table
 // first): a second __shared__ object makes hipcc wait vmcnt(0) before every
 // LDS read (cdna_hip_programming.md, "three .s-level traps").
-#ifndef CWQ_DECODE_GLDS
-#define CWQ_DECODE_GLDS 1  // 0: the register-prefetch decoder for single-step codes too
-#endif
+// CWQ_DECODE_GLDS (cwq_dispatch.h) 0: k_decode_q4 for single-step codes too.
 #ifndef CWQ_GLDS_SLOTS
 #define CWQ_GLDS_SLOTS 2  // ring slots per wave (chunks in flight: slots - 1)
 #endif
@@ -3720,11 +3718,8 @@ static SeedSpec seeds_of(const EncodeArgs& a) {
   return SeedSpec{a.seed, a.block_id_base, a.seeds};
 }
 
-// The float4 lane-per-Philox-block kernels: uniform d % 4 == 0, d <= 256.
-static bool q4_shape(const int64_t* block_off, int64_t ud) {
-  return block_off == nullptr && ud > 0 && ud % 4 == 0 && ud <= 256;
-}
-// float4 access needs 16-byte aligned bases (callers may pass offset views)
+// float4 access needs 16-byte aligned bases (callers may pass offset views);
+// with q4_shape (cwq_dispatch.h) the condition of the float4 kernels
 static bool aligned16(const void* a, const void* b, const void* c) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
 }
@@ -4088,7 +4083,8 @@ static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool eve
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (plan.self_finalizing) continue;
-    if (q4_shape(a.block_off, a.ud) && aligned16(a.loc_s, a.scale_s, a.out_sample)) {
+    if (q4_shape(a.block_off != nullptr, a.ud) &&
+        aligned16(a.loc_s, a.scale_s, a.out_sample)) {
       const uint32_t qpb = (uint32_t)(a.ud / 4), bpw = 64u / qpb;
       hipLaunchKernelGGL(k_encode_finalize_q4, dim3(grid_for(a.nb, 4 * (int64_t)bpw, 1u << 20)),
                          dim3(256), 0, stream, (const float4*)a.loc_s, (const float4*)a.scale_s,
@@ -4254,27 +4250,30 @@ hipError_t launch_decode(const int32_t* idx, const float* p_loc, const float* p_
                          int n_bits,
                          int n_steps, int32_t seed, float rho, int64_t block_id_base,
                          float* out_sample, hipStream_t stream) {
-  if (nb <= 0) return hipSuccess;
+  // the kernel and its launch size: decode_plan alone (cwq_dispatch.h)
+  const DecodePlan p = decode_plan(DecodeShape{block_off != nullptr, ud, nb, total_dims, n_steps,
+                                               aligned16(p_loc, p_scale, out_sample)});
+  if (p.workgroups == 0) return hipSuccess;
   const float nst = (float)n_steps;
   const float sdiv = (float)__builtin_sqrt((double)n_steps);
-  if (q4_shape(block_off, ud) && aligned16(p_loc, p_scale, out_sample)) {
-    const uint32_t qpb = (uint32_t)(ud / 4), bpw = 64u / qpb;
-    const int64_t ngroups = (nb + (int64_t)bpw * qpb - 1) / ((int64_t)bpw * qpb);
-    if (CWQ_DECODE_GLDS && n_steps == 1) {
-      hipLaunchKernelGGL(k_decode_q4_glds, dim3(grid_for(ngroups, 4, 1u << 20)), dim3(256), 0,
-                         stream, idx, (const float4*)p_loc, (const float4*)p_scale, qpb, bpw, nb,
+  switch (p.kernel) {
+    case DecodeKernel::Q4Glds:
+      hipLaunchKernelGGL(k_decode_q4_glds, dim3(p.workgroups), dim3(256), 0, stream, idx,
+                         (const float4*)p_loc, (const float4*)p_scale, p.qpb, p.bpw, nb,
                          (int64_t)1 << n_bits, rho, seed, block_id_base, (float4*)out_sample);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_decode_q4, dim3(grid_for(ngroups, 4, 1u << 20)), dim3(256), 0,
-                       stream, idx, (const float4*)p_loc, (const float4*)p_scale, qpb, bpw, nb,
-                       n_steps, (int64_t)1 << n_bits, nst, sdiv, rho, seed, block_id_base,
-                       (float4*)out_sample);
-    return hipGetLastError();
+      break;
+    case DecodeKernel::Q4:
+      hipLaunchKernelGGL(k_decode_q4, dim3(p.workgroups), dim3(256), 0, stream, idx,
+                         (const float4*)p_loc, (const float4*)p_scale, p.qpb, p.bpw, nb, n_steps,
+                         (int64_t)1 << n_bits, nst, sdiv, rho, seed, block_id_base,
+                         (float4*)out_sample);
+      break;
+    case DecodeKernel::General:
+      hipLaunchKernelGGL(k_decode, dim3(p.workgroups), dim3(256), 0, stream, idx, p_loc, p_scale,
+                         block_off, ud, nb, n_steps, (int64_t)1 << n_bits, nst, sdiv, rho, seed,
+                         block_id_base, out_sample);
+      break;
   }
-  hipLaunchKernelGGL(k_decode, dim3(grid_for(total_dims, 256, 16384)), dim3(256), 0, stream, idx,
-                     p_loc, p_scale, block_off, ud, nb, n_steps, (int64_t)1 << n_bits, nst, sdiv,
-                     rho, seed, block_id_base, out_sample);
   return hipGetLastError();
 }
 

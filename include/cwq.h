@@ -203,12 +203,18 @@ int cwq_greedy_encode_uniform(const float* t_loc, const float* t_scale, const fl
 
 /* Decoder (coded_greedy_sampler.py:93-167): sample = sum over steps of the
  * proposal-shard candidate idx[g*n_steps + i] of step i.  O(n_steps * d) per
- * block (only the selected row of the candidate stream is regenerated). */
+ * block (only the selected row of the candidate stream is regenerated).
+ * An index outside [0, 2^n_bits_per_step) -- a corrupt code -- is no error:
+ * every dim of its block decodes to NaN, whichever of the block's steps holds
+ * it, no other block is affected, and the call returns CWQ_OK. */
 int cwq_greedy_decode(const int32_t* idx, const float* p_loc, const float* p_scale,
                       const int64_t* block_off, int64_t nb, int64_t total_dims,
                       int64_t max_block_dim, int n_bits_per_step, int n_steps, int32_t seed,
                       float rho, int64_t block_id_base, float* out_sample, void* stream);
 
+/* Same with every block of dimension d; out-of-range indices as above.  The
+ * arrays need no alignment beyond float's (d % 4 == 0, d <= 256 with all three
+ * on 16-byte boundaries takes faster kernels; the results are the same bits). */
 int cwq_greedy_decode_uniform(const int32_t* idx, const float* p_loc, const float* p_scale,
                               int64_t nb, int64_t d, int n_bits_per_step, int n_steps,
                               int32_t seed, float rho, int64_t block_id_base, float* out_sample,

@@ -1,10 +1,11 @@
 // Host build of the product's device-math restatement (csrc/cwq_math.h) and of
-// the screening bound (csrc/cwq_screen.h), of the encode dispatch
+// the screening bound (csrc/cwq_screen.h), of the encode and decode dispatch
 // (csrc/cwq_dispatch.h) and of the importance coder's launch plan
 // (csrc/cwq_imp_plan.h).  tests/test_math_exhaustive.py compares the first
 // with the host glibc over the full Box-Muller input domains;
 // tests/test_screen_bound.py checks the second's inequalities,
-// tests/test_encode_plan.py the third's table of shapes and
+// tests/test_encode_plan.py and tests/test_decode_plan.py the third's tables
+// of shapes and
 // tests/test_importance_plan.py the fourth's.
 // Test-only shim; not part of the product.
 #include <stdint.h>
@@ -130,6 +131,20 @@ void mc_dispatch_consts(int64_t* out) {
   out[0] = (int64_t)CWQ_CSR_COOP_ROWS_PER_LANE * cwq::kChipLanes;
   out[1] = CWQ_CSR_COOP_MIN_D;
   out[2] = CWQ_CSR_LDS_DIMS;
+}
+
+// The decode dispatch (csrc/cwq_dispatch.h) of one launch_decode call.
+// out = (kernel, qpb, bpw, groups, workgroups); kernel in DecodeKernel's order.
+void mc_decode_plan(int csr, int64_t ud, int64_t nb, int64_t total_dims, int n_steps,
+                    int aligned16, int64_t* out) {
+  const cwq::DecodePlan p =
+      cwq::decode_plan(cwq::DecodeShape{csr != 0, ud, nb, total_dims, n_steps, aligned16 != 0});
+  out[0] = (int64_t)p.kernel; out[1] = p.qpb; out[2] = p.bpw; out[3] = p.groups;
+  out[4] = p.workgroups;
+}
+// (k_decode's grid cap, the q4 kernels' grid cap, CWQ_DECODE_GLDS)
+void mc_decode_consts(int64_t* out) {
+  out[0] = cwq::kDecodeGeneralGridCap; out[1] = cwq::kDecodeQ4GridCap; out[2] = CWQ_DECODE_GLDS;
 }
 
 // The importance coder's launch plan (csrc/cwq_imp_plan.h).

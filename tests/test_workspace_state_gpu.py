@@ -28,6 +28,7 @@ import pytest
 import torch
 
 import encode_shapes as S
+from decode_shapes import DECODE_CASES
 from poison import poisoned
 
 pytestmark = pytest.mark.gpu
@@ -573,12 +574,7 @@ def test_decode_blocks_var_from_the_stream(cwq, cwqlib, oracle):
     _same(got, _canon(want), "decode_blocks_var against the oracle")
 
 
-# d = 12: three Philox blocks per row, 21 rows per wave; d = 36: nine per row,
-# 63 of 64 lanes active; d = 256: a wave per row; ragged: the general kernel
-DECODE_CASES = [("d12_1step", 12, 37, 1), ("d12_3steps", 12, 37, 3), ("d36", 36, 9, 1),
-                ("d256", 256, 3, 1), ("ragged", [3, 20, 0, 45, 1, 64, 130, 0], None, 2)]
-
-
+# tests/decode_shapes.py; test_decode_plan.py holds each to the kernel it names
 @pytest.mark.parametrize("name,d,nb,n_steps", DECODE_CASES)
 def test_decode_blocks_ignores_buffer_contents(cwq, oracle, name, d, nb, n_steps):
     bits = 10
