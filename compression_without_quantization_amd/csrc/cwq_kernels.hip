@@ -218,6 +218,25 @@ constexpr float kPruneC1 = 0x1p-14f;
 #if CWQ_PARK_COMPLETE && !(CWQ_LINKED_VISIT && CWQ_BORROW_REFILL)
 #error "CWQ_PARK_COMPLETE needs CWQ_LINKED_VISIT and CWQ_BORROW_REFILL"
 #endif
+#ifndef CWQ_SHARE_UNROLL
+// While a wave's pool holds the rows that a trip can take at most, the
+// screening loop runs trips of this many copies of its body (1, 2, 4 or 8)
+// with no exit and no test of the active mask inside a trip, the tau share in
+// the last copy: at 8 = CWQ_TAU_SHARE_MASK + 1 no iteration counts or tests a
+// counter (cwq_refill.h unroll_due, unroll_trip_rows).  The one-copy loop
+// behind it hands out the rest.  1: that loop alone (A/B builds).  C4 against
+// 1: at 2 +0.4 ms, at 4 -1.4 ms, at 8 -3.8 ms of 255.5
+#define CWQ_SHARE_UNROLL 8
+#endif
+#ifndef CWQ_PARK_LOOK_MASK
+// PARK instances look for parked rows every CWQ_PARK_LOOK_MASK + 1 iterations
+// (a v_cmp and a scalar test each; a parked row idles for at most that many).
+// Every 4th (3u) in copies 4 and 8: C4 +2.7 ms against every 8th
+#define CWQ_PARK_LOOK_MASK CWQ_TAU_SHARE_MASK
+#endif
+#if CWQ_SHARE_UNROLL != 1 && CWQ_SHARE_UNROLL != 2 && CWQ_SHARE_UNROLL != 4 && CWQ_SHARE_UNROLL != 8
+#error "CWQ_SHARE_UNROLL is 1, 2, 4 or 8"
+#endif
 
 // best + (loc_s + scale_s z) - mu  (misc.py:14-15, coded_greedy_sampler.py:57, TFP _z numerator)
 template <bool STEP0>
@@ -359,6 +378,12 @@ __device__ __forceinline__ float tau_guess_of(float qm, float As, float Pq) {
   if (!(qm >= 0.0f)) return -__builtin_inff();
   const float tg = cwq::screen_row_lower(-qm, cwq::kScreenC2, As, Pq);
   return tg == tg ? tg : -__builtin_inff();
+}
+
+// one trip of an unrolled loop: the body's copies 0 .. U - 1 in turn
+template <class F, uint32_t... I>
+__device__ __forceinline__ void unroll_each(F& f, std::integer_sequence<uint32_t, I...>) {
+  (f(std::integral_constant<uint32_t, I>{}, std::integral_constant<uint32_t, (uint32_t)sizeof...(I)>{}), ...);
 }
 
 // PARK: the screening loop without its per-iteration completion test
@@ -767,11 +792,40 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
       if constexpr (!SCREEN || !CWQ_FOLD_ROUND0) w0g_x = w0g;
       // a lane is active while its row is in the wave's range: the compare is
       // taken in the pool refill only (static rows are in range), its mask
-      // carried in SGPRs.  The loop's only exit is at its end, so its
+      // carried in SGPRs.  Each loop's only exit is at its end, so its
       // wave-uniform counters (iter, wnext_g) stay scalar.
       bool active = ng < ng_end;
       uint64_t m_act = __builtin_amdgcn_ballot_w64(active);
-      while (m_act != 0ull) {
+      // The body of one iteration, written once: copy C of a loop of UU
+      // copies (the unrolled screening loop of a PARK instance: UU =
+      // CWQ_SHARE_UNROLL; the loop behind it, the other instances' screening
+      // loop and the exact pass: 1).
+      //   * Between two pool refills no lane's bit of m_act changes.  m_act is
+      //     assigned in the refill and nowhere else: a static row is in range,
+      //     a parked lane stays active, and a lane that finishes a row either
+      //     steps to a static row or is in m_pool in the same iteration.
+      //   * In the unrolled loop (FAST) no refill changes it either (see the
+      //     loops below): every lane is active, so the copies neither read
+      //     m_act nor write it.
+      // Only the PARK instances unroll: the others run shares of 4,096 rows,
+      // the fewest with an unrolled trip at U = 8, at d = 8 alone
+      // (launch_prune_t), and their keep step, which every copy would hold
+      // with its list-full row scoring, made them 84 KB of code against 33.
+      constexpr uint32_t U = PARKED ? (uint32_t)CWQ_SHARE_UNROLL : 1u;
+      constexpr uint32_t LOOK_MASK = PARKED ? (uint32_t)(CWQ_PARK_LOOK_MASK) : 0u;
+      static_assert(LOOK_MASK <= CWQ_TAU_SHARE_MASK, "a look at least as often as a share");
+      auto body = [&](auto copy_tag, auto unroll_tag) {
+        constexpr uint32_t C = decltype(copy_tag)::value;
+        constexpr uint32_t UU = decltype(unroll_tag)::value;  // copies in this loop
+        constexpr bool FAST = UU > 1u;
+        // iter counts the iterations, a trip at a time, in a loop with a test that needs it
+        constexpr bool COUNTS = cwq::unroll_counts<CWQ_TAU_SHARE_MASK, UU>() ||
+                                cwq::unroll_counts<LOOK_MASK, UU>();
+        if constexpr (COUNTS && C + 1u == UU) iter += UU;
+        const bool share_due = cwq::unroll_due<CWQ_TAU_SHARE_MASK, UU, C>(iter);
+#ifdef CWQ_PRUNE_STATS
+        if (lane == 0) atomicAdd(&s_ps[71], 1u);
+#endif
         int2 mt;
         float4 sa, sb;
         uint32_t kp_next = 0;
@@ -804,7 +858,12 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // the key through an opaque move each iteration: the fourteen round
         // keys are then formed here by scalar adds, not held in SGPRs across
         // the loop, where they pushed the loop's lane masks and counters out
-        // into VGPR lanes (v_writelane / v_readlane every iteration)
+        // into VGPR lanes (v_writelane / v_readlane every iteration).  Today's
+        // loop has room for them (without the copy every instance still builds
+        // at 106 SGPRs with no lane move in its loops, the keys formed once
+        // per pass), but it is no faster for the 17 scalar instructions less:
+        // C4 the same in the one-copy loop and 3.8 ms slower in the unrolled
+        // one, at equal clock and VALU count.  The copy stays.
         uint32_t pk0 = st.k0, pk1 = st.k1;
         asm volatile("" : "+s"(pk0), "+s"(pk1));
         const U4 x = philox10_lo_p0(p0, lok, pk0, pk1);
@@ -896,11 +955,22 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // compare of (upper, tau), a v_cndmask and a v_cmp every iteration.
         const uint64_t m_cpl = __builtin_amdgcn_ballot_w64(complete);
         const uint64_t m_below = __builtin_amdgcn_fcmpf(upper, tau, 4 /* olt */);
-        uint64_t m = m_cpl | m_below | (__builtin_amdgcn_read_exec() & ~m_act);
+        // (FAST: every lane is active)
+        uint64_t m = m_cpl | m_below;
+        if constexpr (!FAST) m |= __builtin_amdgcn_read_exec() & ~m_act;
         uint64_t m_keep =
-            m_cpl & m_act &
+            m_cpl & (FAST ? ~0ull : m_act) &
             (SCREEN ? ~m_below : (uint64_t)__builtin_amdgcn_fcmpf(upper, tau, 3 /* oge */));
-        asm volatile("" : "+s"(m), "+s"(m_keep));
+        // (A copy of the unrolled PARKED loop with no look has no branch
+        // between the compares and the step, so nothing to pin: without the
+        // asm it loses the s_nop behind it; PARKED never reads m_keep, which
+        // through the asm cost a move of 0 into a scalar pair.)
+        constexpr bool LOOK_HERE =
+            PARKED && (C + 1u == UU || (LOOK_MASK + 1u <= UU && ((C + 1u) & LOOK_MASK) == 0u));
+        if constexpr (!PARKED)
+          asm volatile("" : "+s"(m), "+s"(m_keep));
+        else if constexpr (!FAST || LOOK_HERE)
+          asm volatile("" : "+s"(m));
         // Rows that completed and may be the best.  The branch is taken by the
         // whole wave (on the scalar m_keep, so the exec mask stays full for the
         // wave max): tau is raised to the largest lower end among these rows in
@@ -922,8 +992,9 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // passes its last real position without falling below tau there (the
         // ordinary test, with the full row's B) walks on to the sentinel and
         // stays there, active, with its s and ng unchanged, its upper end +inf
-        // and so never below.  The iteration that shares tau
-        // (every CWQ_TAU_SHARE_MASK + 1) compares kp with the sentinel's offset:
+        // and so never below.  Every (CWQ_PARK_LOOK_MASK + 1)-th iteration,
+        // which with the mask of the tau share is the one that shares tau
+        // (the unrolled loop's last copy), compares kp with the sentinel's offset:
         // the lanes at it that are active and did not just drop are the
         // completed rows not yet seen (a lane that dropped at its last real
         // position has kp there too and is in m_below: it is finished the
@@ -932,7 +1003,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // resets below move them on.  A wave cannot leave the loop with a row
         // parked, since a parked lane is active, and the pass's final share
         // comes after the loop, so after the last of these steps.  With tau
-        // raised up to CWQ_TAU_SHARE_MASK iterations later than before:
+        // raised up to CWQ_PARK_LOOK_MASK iterations later than before:
         //   * tau is still only raised to lower ends of rows completed in this
         //     tile, later: it stays a lower bound of such a row's exact value;
         //   * a row is dropped on upper < tau at a real position only, as
@@ -942,7 +1013,8 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         //     when found, whichever tau the wave has by then;
         //   * which rows are pushed may differ (a later push meets a higher
         //     tau); the survivors' exact values, and so the result, do not.
-        // A parked lane idles for at most CWQ_TAU_SHARE_MASK iterations.
+        // A parked lane idles for at most CWQ_PARK_LOOK_MASK iterations, over
+        // both loops: the unrolled one leaves iter a multiple of its trip.
         auto keep_rows = [&](const uint64_t mk) {
           // (going down, `active` is carried as the scalar m_act alone: the
           // lane's bit of mk is complete && active && reach)
@@ -996,10 +1068,10 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
           if (__builtin_expect(m_keep != 0ull, 0)) keep_rows(m_keep);
         } else {
           // the share first, so that the parked rows meet the freshest tau
-          if (((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {
-            tau = tau_share_wave(&tau_cell, tau);
-            const uint64_t m_park =
-                __builtin_amdgcn_uicmp(kp, kb + KS * (uint32_t)G, 32 /* eq */) & m_act & ~m_below;
+          if (share_due) tau = tau_share_wave(&tau_cell, tau);
+          if (cwq::unroll_due<LOOK_MASK, UU, C>(iter)) {
+            const uint64_t m_park = __builtin_amdgcn_uicmp(kp, kb + KS * (uint32_t)G, 32 /* eq */) &
+                                    (FAST ? ~0ull : m_act) & ~m_below;
             if (__builtin_expect(m_park != 0ull, 0)) keep_rows(m_park);
             m |= m_park;
           }
@@ -1055,7 +1127,7 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // so one returning LDS max by lane 0 and one v_max, no reduce (and no
         // "raised since the last share" flag: both of its arms would be this)
         // (PARKED: shared above, with the look for parked rows)
-        if (!PARKED && ((++iter) & CWQ_TAU_SHARE_MASK) == 0u) {
+        if (!PARKED && share_due) {
           tau = tau_share_wave(&tau_cell, tau);
         }
         // Pool refill, taken by the whole wave when a finished lane has left
@@ -1069,7 +1141,8 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         // anew.  wnext_g is kept at or below ng_end (rows from there on are
         // out of range alike), which bounds ng however long lanes stay inactive.
         if constexpr (CWQ_BORROW_REFILL) {
-          if (m_pool != 0ull) {
+          // (FAST: the refill out of line, so that a copy falls through to the next)
+          if (FAST ? __builtin_expect(m_pool != 0ull, 0) : (m_pool != 0ull)) {
 #ifdef CWQ_PRUNE_STATS
             if (lane == 0) atomicAdd(&s_ps[70], 1u);
 #endif
@@ -1088,7 +1161,11 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
             // want <= ng_end, and then the lanes of m_pool are active and the
             // other lanes' state is what it was (no compare)
             const uint32_t want = wnext_g + (uint32_t)__builtin_popcountll(m_pool) * (uint32_t)G;
-            if (CWQ_POOL_RANGE_SKIP && want <= ng_end) {
+            if constexpr (FAST) {
+              // want <= ng_end by the loop's entry test: the rows are in range
+              // and every lane stays active, so m_act is not touched
+              wnext_g = want;
+            } else if (CWQ_POOL_RANGE_SKIP && want <= ng_end) {
               wnext_g = want;
               m_act |= m_pool;
             } else {
@@ -1111,10 +1188,28 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
             m_act = __builtin_amdgcn_ballot_w64(active);
           }
         }
-#ifdef CWQ_PRUNE_STATS
-        if (lane == 0) atomicAdd(&s_ps[71], 1u);
-#endif
+      };
+      constexpr std::integral_constant<uint32_t, 0u> c0{};
+      constexpr std::integral_constant<uint32_t, 1u> u1{};
+      // The unrolled loop: U copies of the body per trip and no exit but at
+      // the trip's end.  It runs while every lane is active and the pool holds
+      // the 64 U rows that U refills can take at most, so that inside a trip
+      //   * every pool row handed out is in range (want <= ng_end),
+      //   * no lane turns inactive: m_act stays all ones and is not read,
+      //   * and the wave cannot run out of rows, so no copy tests for it.
+      // It leaves on a trip boundary, with iter a multiple of the trip, and in
+      // the state the one-copy loop below expects, which hands out the rest
+      // and is the whole pass of a wave with a small share (below 4,096 rows
+      // at U = 8) or without a row.
+      if constexpr (U > 1u) {
+        while (m_act == ~0ull && wnext_g + cwq::unroll_trip_rows(U) * (uint32_t)G <= ng_end)
+          unroll_each(body, std::make_integer_sequence<uint32_t, U>{});
       }
+      // (Leaving this loop from the refill that clears the last bit of m_act,
+      // with no test at its end, was built and measured: C4 -1.2 ms alone,
+      // -0.2 ms behind the unrolled loop, neither five times the parent's
+      // spread: not kept)
+      while (m_act != 0ull) body(c0, u1);
     };
 #ifdef CWQ_PRUNE_STATS
     if (screen && tid == 0) atomicAdd(&g_prune_stats[67], 1ull);

@@ -40,4 +40,30 @@ CWQ_REFILL_HD uint32_t refill_static_rows(uint32_t R) {
 // those 64 first rows, as it did before there was a static region.
 CWQ_REFILL_HD uint32_t refill_pool_start(uint32_t S) { return S < kRefillLanes ? kRefillLanes : S; }
 
+// The unrolled loop (k_encode_prune, CWQ_SHARE_UNROLL).  The loop's body stands
+// U times in the loop; an event of period M + 1 iterations (the tau share, the
+// look for parked rows; M + 1 a power of two) falls on the iterations whose
+// number, counted from 1, is a multiple of M + 1.  With M + 1 <= U that is a
+// property of the copy C alone, and nothing is counted.  Otherwise only the
+// last copy can hold the event: it adds U to the iteration counter and tests
+// it, once per trip.  With U = 1 that is the test of every iteration.
+// `iters`: the iterations up to and including this trip.
+template <uint32_t M, uint32_t U, uint32_t C>
+CWQ_REFILL_HD bool unroll_due(uint32_t iters) {
+  static_assert((M & (M + 1u)) == 0u && (U & (U - 1u)) == 0u && U >= 1u && C < U,
+                "unroll_due: M + 1 and U are powers of two, C < U");
+  if constexpr (M + 1u <= U)
+    return ((C + 1u) & M) == 0u;
+  else if constexpr (C + 1u != U)
+    return false;
+  else
+    return (iters & M) == 0u;
+}
+// whether the last copy counts the iterations for an event of period M + 1
+template <uint32_t M, uint32_t U>
+constexpr bool unroll_counts() { return M + 1u > U; }
+// pool rows that must be left for a trip of U copies to be sure of its rows:
+// a refill hands out at most a row per lane
+constexpr uint32_t unroll_trip_rows(uint32_t U) { return U * kRefillLanes; }
+
 }  // namespace cwq
