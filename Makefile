@@ -19,7 +19,8 @@ $(ORACLE_SO): oracle/cwq_oracle.c
 $(MATHCHECK_SO): tests/native/mathcheck.cpp compression_without_quantization_amd/csrc/cwq_math.h \
 		compression_without_quantization_amd/csrc/cwq_screen.h \
 		compression_without_quantization_amd/csrc/cwq_dispatch.h \
-		compression_without_quantization_amd/csrc/cwq_imp_plan.h
+		compression_without_quantization_amd/csrc/cwq_imp_plan.h \
+		compression_without_quantization_amd/csrc/cwq_imp_screen.h
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -fno-fast-math -mfma -fPIC -shared -o $@ $<
 
 # rocRAND's Philox4x32-10 (SDK header) on the host: an independent pin (test shim).

@@ -1038,6 +1038,113 @@ CWQO_API int cwqo_importance_encode(const float* t_loc, const float* t_scale, co
   return err ? -1 : 0;
 }
 
+/* The importance score under its neighbouring arithmetics (the
+ * importance certificate; tests/imp_near_ties.py).  Every candidate row of a
+ * group is scored as declared (cwqo_importance_encode_block) and under
+ *   1..5  the declared terms summed in sem_rowsum's other orders (sse4, avx8x2,
+ *         avx512, seq, tree);
+ *   6     both log-probs in the TFP >= 0.8 squared_difference form;
+ *   7     x with the multiply-add contracted: fmaf(ps, z, pl);
+ *   8     lq without the round trip through x: -0.5 z^2 - cp;
+ *   9     the whole term as the real quadratic A z^2 + B z + C (a = ps / ts,
+ *         b = (pl - tl) / ts, A = (1 - a^2) / 2, B = -a b, C = cp - ct - b^2 / 2,
+ *         the coefficients rounded from double) in float Horner form: what a
+ *         coder would emit that let a screened value stand in for an exact one;
+ *   10,11 ct one ulp up, down;   12,13 cp one ulp up, down.
+ * out_vidx[g * IMP_NV + v]: the index variant v would emit (v = 0: declared);
+ * out_gap[g]: declared best minus second-best row value; out_dev[g * IMP_NV +
+ * v] (optional): variant v's value of the declared best row minus the declared
+ * value; out_ndiff[g * IMP_NV + v] (optional): the candidate rows variant v
+ * scores differently from the declared arithmetic (0: it is no neighbour on
+ * this group at all). */
+#define IMP_NV 14
+#define IMP_NROW 9 /* term arrays: declared, tfp08, fma, lq, quad, ct+, ct-, cp+, cp- */
+CWQO_API int cwqo_importance_num_variants(void) { return IMP_NV; }
+
+CWQO_API int cwqo_importance_encode_semvar(const float* t_loc, const float* t_scale,
+                                           const float* p_loc, const float* p_scale,
+                                           const int64_t* block_off, int64_t nb,
+                                           const int64_t* n_samples, int32_t seed,
+                                           int64_t block_id_base, int64_t* out_vidx,
+                                           double* out_gap, float* out_dev,
+                                           int64_t* out_ndiff, int nthreads) {
+  int err = 0;
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+#pragma omp parallel for schedule(dynamic, 1) reduction(| : err)
+#endif
+  for (int64_t g = 0; g < nb; ++g) {
+    const int64_t o = block_off[g], d = block_off[g + 1] - block_off[g];
+    const int64_t dd = d > 0 ? d : 1;
+    const int32_t sg = (int32_t)((uint32_t)seed + (uint32_t)(block_id_base + g));
+    const float *tl = t_loc + o, *ts = t_scale + o, *pl = p_loc + o, *ps = p_scale + o;
+    if (n_samples[g] < 1) { err |= 1; continue; }
+    float* buf = (float*)malloc((size_t)(IMP_NROW + 5) * (size_t)dd * sizeof(float));
+    if (!buf) { err |= 1; continue; }
+    float *ct = buf, *cp = buf + dd, *qa = buf + 2 * dd, *qb = buf + 3 * dd, *qc = buf + 4 * dd;
+    float* row = buf + 5 * dd; /* [IMP_NROW][dd] */
+    for (int64_t j = 0; j < d; ++j) {
+      ct[j] = cwqo_log_normalization(ts[j]);
+      cp[j] = cwqo_log_normalization(ps[j]);
+      const double a = (double)ps[j] / (double)ts[j];
+      const double b = ((double)pl[j] - (double)tl[j]) / (double)ts[j];
+      qa[j] = (float)(0.5 * (1.0 - a * a));
+      qb[j] = (float)(-a * b);
+      qc[j] = (float)((double)cp[j] - (double)ct[j] - 0.5 * b * b);
+    }
+    normal_stream st;
+    memset(&st, 0, sizeof(st));
+    cwqo_generate_key(sg, 42, st.key, st.ctr);
+    float bv[IMP_NV], bdev[IMP_NV];
+    int64_t bi[IMP_NV], nd[IMP_NV];
+    for (int v = 0; v < IMP_NV; ++v) { bv[v] = -FLT_MAX; bi[v] = 0; bdev[v] = 0.0f; nd[v] = 0; }
+    float second = -FLT_MAX;
+    for (int64_t n = 0; n < n_samples[g]; ++n) {
+      for (int64_t j = 0; j < d; ++j) {
+        const float z = stream_normal(&st, (uint64_t)(n * d + j));
+        float x = ps[j] * z;
+        x = pl[j] + x;
+        const float lt = log_prob_c(x, tl[j], ts[j], ct[j]);
+        const float lq = log_prob_c(x, pl[j], ps[j], cp[j]);
+        row[0 * dd + j] = lt - lq;
+        row[1 * dd + j] = log_prob_tfp08(x, tl[j], ts[j], ct[j]) -
+                          log_prob_tfp08(x, pl[j], ps[j], cp[j]);
+        const float xf = fmaf(ps[j], z, pl[j]);
+        row[2 * dd + j] = log_prob_c(xf, tl[j], ts[j], ct[j]) - log_prob_c(xf, pl[j], ps[j], cp[j]);
+        const float lz = -0.5f * (z * z);
+        row[3 * dd + j] = lt - (lz - cp[j]);
+        row[4 * dd + j] = fmaf(fmaf(qa[j], z, qb[j]), z, qc[j]);
+        row[5 * dd + j] = log_prob_c(x, tl[j], ts[j], nextafterf(ct[j], INFINITY)) - lq;
+        row[6 * dd + j] = log_prob_c(x, tl[j], ts[j], nextafterf(ct[j], -INFINITY)) - lq;
+        row[7 * dd + j] = lt - log_prob_c(x, pl[j], ps[j], nextafterf(cp[j], INFINITY));
+        row[8 * dd + j] = lt - log_prob_c(x, pl[j], ps[j], nextafterf(cp[j], -INFINITY));
+      }
+      float vals[IMP_NV];
+      for (int v = 0; v < IMP_NV; ++v) {
+        const float val = v < SEM_NSUM ? sem_rowsum(row, d, v)
+                                       : cwqo_eigen_rowsum(row + (v - SEM_NSUM + 1) * dd, d);
+        vals[v] = val;
+        if (v == 0) {
+          if (val > bv[0]) second = bv[0];
+          else if (val > second) second = val;
+        }
+        if (val > bv[v]) { bv[v] = val; bi[v] = n; }
+        nd[v] += val != vals[0];
+      }
+      if (bi[0] == n)
+        for (int v = 0; v < IMP_NV; ++v) bdev[v] = vals[v] - vals[0];
+    }
+    if (out_gap) out_gap[g] = (double)bv[0] - (double)second;
+    for (int v = 0; v < IMP_NV; ++v) {
+      out_vidx[g * IMP_NV + v] = bi[v];
+      if (out_dev) out_dev[g * IMP_NV + v] = bdev[v];
+      if (out_ndiff) out_ndiff[g * IMP_NV + v] = nd[v];
+    }
+    free(buf);
+  }
+  return err ? -1 : 0;
+}
+
 /* tf.quantization.quantize(x, -30, 30, tf.quint16) (MIN_COMBINED, unsigned fast
  * path): cast<uint16>((clamp(x) - min) * scale + 0.5f), scale = float(65535/60). */
 CWQO_API void cwqo_quantize_quint16(const float* x, int64_t n, float mn, float mx,

@@ -70,6 +70,9 @@ def lib():
             "cwqo_importance_decode_block": (None, [i64, vp, vp, i64, i32, vp]),
             "cwqo_importance_encode": (ci, [vp, vp, vp, vp, vp, i64, vp, i32, i64, vp, vp, ci]),
             "cwqo_importance_scores": (ci, [vp, vp, vp, vp, i64, i32, vp, i64, vp]),
+            "cwqo_importance_num_variants": (ci, []),
+            "cwqo_importance_encode_semvar": (ci, [vp, vp, vp, vp, vp, i64, vp, i32, i64, vp, vp,
+                                                   vp, vp, ci]),
             "cwqo_quantize_quint16": (None, [vp, i64, f32, f32, vp]),
             "cwqo_dequantize_quint16": (None, [vp, i64, f32, f32, vp]),
         }
@@ -374,6 +377,36 @@ def importance_scores(t_loc, t_scale, p_loc, p_scale, seed, rows):
                                       r.size, _p(out))
     assert rc == 0, rc
     return out[:r.size]
+
+
+IMP_VARIANTS = ("declared",) + SEM_ORDERS[1:] + ("tfp08", "fma_x", "lq_direct", "quadratic",
+                                                 "ct_up", "ct_dn", "cp_up", "cp_dn")
+
+
+def importance_encode_semvar(t_loc, t_scale, p_loc, p_scale, block_off, n_samples, seed,
+                             block_id_base=0, nthreads=0):
+    """importance_encode with every candidate row also scored under each
+    neighbouring arithmetic (IMP_VARIANTS, cwq_oracle.c).  Returns (vidx int64
+    [nb, V]: the index each variant would emit, column 0 the declared one; gap
+    float64 [nb]: declared best - second-best score; dev float32 [nb, V]:
+    variant v's score of the declared best row minus the declared score; ndiff
+    int64 [nb, V]: the candidate rows variant v scores differently at all)."""
+    tl, ts, pl, ps = map(_f32, (t_loc, t_scale, p_loc, p_scale))
+    off = np.ascontiguousarray(np.asarray(block_off, dtype=np.int64))
+    ns = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64))
+    nb = off.size - 1
+    nv = lib().cwqo_importance_num_variants()
+    assert nv == len(IMP_VARIANTS)
+    vidx = np.zeros(max(nb, 1) * nv, dtype=np.int64)
+    gap = np.zeros(max(nb, 1), dtype=np.float64)
+    dev = np.zeros(max(nb, 1) * nv, dtype=np.float32)
+    ndiff = np.zeros(max(nb, 1) * nv, dtype=np.int64)
+    rc = lib().cwqo_importance_encode_semvar(_p(tl), _p(ts), _p(pl), _p(ps), _p(off), nb, _p(ns),
+                                             int(seed), int(block_id_base), _p(vidx), _p(gap),
+                                             _p(dev), _p(ndiff), int(nthreads))
+    assert rc == 0, rc
+    return (vidx.reshape(-1, nv)[:nb], gap[:nb], dev.reshape(-1, nv)[:nb],
+            ndiff.reshape(-1, nv)[:nb])
 
 
 def quantize_quint16(x, mn=-30.0, mx=30.0):

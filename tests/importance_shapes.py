@@ -21,8 +21,11 @@ SMALL_N = 128
 class Blocks:
     """One cwq_importance_encode launch: group lengths, counts, seed, base."""
 
-    def __init__(self, name, sizes, counts, seed, base=0, kind="normal", rng_seed=0):
+    def __init__(self, name, sizes, counts, seed, base=0, kind="normal", rng_seed=0,
+                 eps=2.0 ** -24, certify=None, lead=None):
         self.name, self.kind = name, kind
+        # of the "near" kind (NEAR_TIE_CASES)
+        self.eps, self.certify, self.lead = eps, certify, lead
         self.sizes = np.asarray(sizes, dtype=np.int64)
         self.counts = np.asarray(counts, dtype=np.int64)
         assert self.sizes.size == self.counts.size
@@ -35,6 +38,9 @@ class Blocks:
 
     def inputs(self):
         """(t_loc, t_scale, p_loc, p_scale) float32 [D]."""
+        if self.kind == "near":      # rounding-sized gaps under a non-standard proposal
+            import imp_near_ties
+            return imp_near_ties.inputs(self.off, self.rng_seed, self.eps, self.lead)
         rng = np.random.default_rng(self.rng_seed)
         D = int(self.off[-1])
         tl = (rng.standard_normal(D) * 0.7).astype(np.float32)
@@ -146,6 +152,65 @@ def cpt_ladder(name, kind="normal"):
             sizes.append(CPT_LADDER_DIMS[i]); counts.append(head[i])
     assert sum(counts) == T
     return Blocks(f"cpt_ladder_{name}_{kind}", sizes, counts, 2024, 1, kind=kind, rng_seed=c)
+
+
+# ---------------------------------------------------------------------------
+# near ties: one case per scoring path, certified by tests/test_imp_near_ties.py
+# ---------------------------------------------------------------------------
+NT_SEED, NT_BASE = 2 ** 31 - 4, 5       # seed + base + g wraps int32 in every case
+# (input rng seed, eps) of each case: chosen on the CPU so that the oracle alone
+# meets the certificate's conditions (tests/test_imp_near_ties.py)
+NT_LEVELS = {"nt_small": (1, 2.0 ** -24), "nt_short": (1, 2.0 ** -24),
+             "nt_pruned": (1, 2.0 ** -25), "nt_tiles": (1, 2.0 ** -24),
+             "nt_exact": (3, 2.0 ** -27), "nt_overflow": (1, 2.0 ** -26),
+             "nt_sum": (7, 2.0 ** -24)}
+# nt_sum: every group's first dim has the target N(p_loc, p_scale / 7.5): scores
+# of log 7.5 = 2.01 and rounding-sized gaps at 60,000 rows (imp_near_ties.inputs)
+NT_SUM_LEAD, NT_SUM_ROWS = 7.5, 60000
+NT_OVERFLOW_LADDER = [2 * i + 1 for i in range(len(CPT_LADDER_DIMS))]  # cpt_ladder's head groups
+
+
+def _nt_draw(name, nb, dims, counts, always=()):
+    """nb groups with lengths and counts drawn from the given values; the
+    counts in ``always`` (and every length) occur at least once."""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    sizes = rng.choice(dims, nb)
+    sizes[:len(dims)] = dims
+    ns = rng.choice(counts, nb) if not isinstance(counts, range) else \
+        rng.integers(counts.start, counts.stop, nb)
+    ns[nb - len(always):] = always
+    perm = rng.permutation(nb)
+    return sizes[perm], ns[perm]
+
+
+def near_tie_case(name):
+    rng_seed, eps = NT_LEVELS[name]
+    kw = dict(kind="near", rng_seed=rng_seed, eps=eps)
+    if name == "nt_overflow":
+        c = cpt_ladder("t21p", "near")
+        return Blocks(name, c.sizes, c.counts, NT_SEED, NT_BASE, certify=NT_OVERFLOW_LADDER, **kw)
+    if name == "nt_sum":        # scores above 1 (a lead dim): the order of the row sum shows
+        sizes, counts = _nt_draw(name, 64, [9, 33, 100], [NT_SUM_ROWS])
+        return Blocks(name, sizes, counts, NT_SEED, NT_BASE, lead=NT_SUM_LEAD, **kw)
+    if name == "nt_small":      # k_imp_small; a few groups of one and two candidates
+        sizes, counts = _nt_draw(name, 64, list(range(1, 17)), [63, 64, 65, 127, 128],
+                                 always=[1, 1, 2, 2, 63, 64, 65, 127, 128])
+    elif name == "nt_short":    # short screened form
+        sizes, counts = _nt_draw(name, 48, [1, 2, 3, 4], range(129, 1025), always=[129, 1024])
+    elif name == "nt_pruned":   # pruned screened form
+        sizes, counts = _nt_draw(name, 48, [5, 8, 9, 32, 100, 256], range(129, 1025),
+                                 always=[129, 1024])
+    elif name == "nt_tiles":    # two to four 1,024-row tiles per group
+        sizes, counts = _nt_draw(name, 32, [3, 8, 33], [1025, 2085, 3072, 3073],
+                                 always=[1025, 2085, 3072, 3073])
+    else:                       # exact rows by length
+        assert name == "nt_exact", name
+        sizes, counts = _nt_draw(name, 16, [257, 300], [129, 1500], always=[129, 1500])
+    return Blocks(name, sizes, counts, NT_SEED, NT_BASE, **kw)
+
+
+NEAR_TIE_CASES = ["nt_small", "nt_short", "nt_pruned", "nt_tiles", "nt_exact", "nt_overflow",
+                  "nt_sum"]
 
 
 # ---------------------------------------------------------------------------

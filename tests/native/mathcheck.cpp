@@ -6,12 +6,14 @@
 // tests/test_screen_bound.py checks the second's inequalities,
 // tests/test_encode_plan.py and tests/test_decode_plan.py the third's tables
 // of shapes and
-// tests/test_importance_plan.py the fourth's.
+// tests/test_importance_plan.py the fourth's; tests/test_imp_screen_bound.py
+// checks the importance coder's screening bound (csrc/cwq_imp_screen.h).
 // Test-only shim; not part of the product.
 #include <stdint.h>
 #include <vector>
 #include "../../compression_without_quantization_amd/csrc/cwq_dispatch.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_imp_plan.h"
+#include "../../compression_without_quantization_amd/csrc/cwq_imp_screen.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_math.h"
 #include "../../compression_without_quantization_amd/csrc/cwq_screen.h"
 
@@ -103,6 +105,78 @@ int mc_screen_row_bounds(int step0, int64_t d, const float* ls, const float* ss,
     out[3 * r] = cwq::screen_row_lower(s, b.c2, b.as, b.pq);
     out[3 * r + 1] = cwq::eigen_fold8(p, t);
     out[3 * r + 2] = cwq::screen_row_upper(s, b.c1, b.bf);
+  }
+  return 1;
+}
+
+// The importance coder's screening bound (csrc/cwq_imp_screen.h).
+// n dims at once: out[7 n] = (A, B, C, err, mag, umax, gated in)
+void mc_imp_screen_dim_many(int64_t n, const float* tl, const float* ts, const float* pl,
+                            const float* ps, const float* ct, const float* cp, float* out) {
+  for (int64_t i = 0; i < n; ++i) {
+    cwq::ImpScreenDim o = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bool ok = cwq::imp_screen_dim(tl[i], ts[i], pl[i], ps[i], ct[i], cp[i], o);
+    float* q = out + 7 * i;
+    q[0] = o.A; q[1] = o.B; q[2] = o.C; q[3] = o.err; q[4] = o.mag; q[5] = o.umax;
+    q[6] = ok ? 1.0f : 0.0f;
+  }
+}
+// screened[i] = the screened term of dim constants (A, B, C) at z'
+void mc_imp_screen_term_many(int64_t n, const float* A, const float* B, const float* C,
+                             const float* zp, float* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = cwq::imp_screen_term(A[i], B[i], C[i], zp[i]);
+}
+// A group of d dims (its row bound E and suffix sums as thread 0 of k_imp_eval
+// builds them) and rows of it: zp[r d + j] the screening normals z' of row r,
+// tx[r d + j] the exact float terms.  For each row, in the kernel's float
+// order: out[4 r ..] = (s, slack, exact, E) with s the screened sum of the
+// completed row, slack = imp_screen_slack(E, s) and exact the Eigen-order sum
+// of tx; pre[4 r + a] = the least (s_j + slack_j) + dsuf[j] - exact over the
+// prefix lengths j < d at which the pruned loop tests a row whose first Philox
+// block is entered at word a (j = 4 - a, 8 - a, ...), +inf if there is none.
+// dsuf_out (d + 1 floats, may be null) gets the suffix sums.  Returns 1, or 0
+// when the value gate rejects a dim or E is not finite (outputs untouched).
+int mc_imp_screen_row_bounds(int64_t d, const float* tl, const float* ts, const float* pl,
+                             const float* ps, const float* ct, const float* cp, int64_t rows,
+                             const float* zp, const float* tx, float* out, double* pre,
+                             float* dsuf_out) {
+  if (d < 1 || d > cwq::kImpScreenMaxD) return 0;
+  std::vector<cwq::ImpScreenDim> o(d);
+  std::vector<float> derr(d), dmag(d), dumax(d), dsuf(d + 1);
+  for (int64_t j = 0; j < d; ++j) {
+    if (!cwq::imp_screen_dim(tl[j], ts[j], pl[j], ps[j], ct[j], cp[j], o[j])) return 0;
+    derr[j] = o[j].err; dmag[j] = o[j].mag; dumax[j] = o[j].umax;
+  }
+  const float E = cwq::imp_screen_row_bound(derr.data(), dmag.data(), d);
+  cwq::imp_screen_suffix(dumax.data(), d, dsuf.data());
+  if (!(E - E == 0.0f)) return 0;
+  if (dsuf_out) for (int64_t j = 0; j <= d; ++j) dsuf_out[j] = dsuf[j];
+  for (int64_t r = 0; r < rows; ++r) {
+    const float* x = tx + r * d;
+    const int64_t vec = d & ~(int64_t)7;
+    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int64_t j = 0; j < vec; j += 8)
+      for (int l = 0; l < 8; ++l) p[l] = p[l] + x[j + l];
+    float t = 0.0f;
+    for (int64_t j = vec; j < d; ++j) t = t + x[j];
+    const float exact = cwq::eigen_fold8(p, t);
+    double least[4] = {__builtin_inf(), __builtin_inf(), __builtin_inf(), __builtin_inf()};
+    float s = 0.0f;
+    for (int64_t j = 0; j < d; ++j) {
+      s = s + cwq::imp_screen_term(o[j].A, o[j].B, o[j].C, zp[r * d + j]);
+      const int64_t v = j + 1;  // dims visited
+      if (v == d) break;
+      const float slack = cwq::imp_screen_slack(E, s);
+      const float upper = cwq::imp_screen_upper(s, slack, dsuf[v]);
+      const int a = (int)((4 - (v & 3)) & 3);  // the loop stops after v dims iff v = 4 - a mod 4
+      const double m = (double)upper - (double)exact;
+      least[a] = m < least[a] ? m : least[a];
+    }
+    out[4 * r] = s;
+    out[4 * r + 1] = cwq::imp_screen_slack(E, s);
+    out[4 * r + 2] = exact;
+    out[4 * r + 3] = E;
+    for (int a = 0; a < 4; ++a) pre[4 * r + a] = least[a];
   }
   return 1;
 }

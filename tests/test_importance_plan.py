@@ -331,3 +331,91 @@ def test_hi_counters_shapes(mc):
     assert int(p["forms"][0]) == PRUNED                # HI0 off
     assert int(case.counts[0]) * S.HI_ENCODE_D > 2 ** 34
     assert p["tiles"] == S.HI_ENCODE_N // 16384
+
+
+# ---------------------------------------------------------------------------
+# the near-tie cases (tests/test_imp_near_ties.py certifies their inputs,
+# tests/test_imp_near_ties_gpu.py runs them): each takes the path it names
+# ---------------------------------------------------------------------------
+def _nt(mc, name, cpt=1024):
+    case = S.near_tie_case(name)
+    assert case.kind == "near" and (case.seed, case.base) == (2 ** 31 - 4, 5)
+    return case, check_blocks(mc, case, cpt=cpt, dynamic=False)
+
+
+def test_near_tie_cases_are_listed():
+    assert S.NEAR_TIE_CASES == ["nt_small", "nt_short", "nt_pruned", "nt_tiles", "nt_exact",
+                                "nt_overflow", "nt_sum"]
+    assert set(S.NT_LEVELS) == set(S.NEAR_TIE_CASES)
+
+
+def test_nt_small_shape(mc):
+    case, p = _nt(mc, "nt_small")
+    assert case.sizes.size == 64 and sorted(set(case.sizes.tolist())) == list(range(1, 17))
+    assert sorted(set(case.counts.tolist())) == [1, 2, 63, 64, 65, 127, 128]
+    assert (p["small"], p["tiles"]) == (64, 0)                # k_imp_small codes every group
+    assert set((p["forms"] & 3).tolist()) == {SMALL}
+    assert int((case.counts <= 2).sum()) <= 4                 # the rest can spread their winners
+
+
+def test_nt_short_shape(mc):
+    case, p = _nt(mc, "nt_short")
+    assert case.sizes.size == 48 and sorted(set(case.sizes.tolist())) == [1, 2, 3, 4]
+    assert case.counts.min() == 129 and case.counts.max() == 1024
+    assert set(p["forms"].tolist()) == {SHORT | HI0}
+    c = (I64 * 10)()
+    mc.mc_importance_consts(c)
+    # one tile per group and no more rows than the survivor list holds: every
+    # survivor is re-scored from the list
+    assert (p["small"], p["tiles"]) == (0, 48) and case.counts.max() <= c[9]
+
+
+def test_nt_pruned_shape(mc):
+    case, p = _nt(mc, "nt_pruned")
+    assert case.sizes.size == 48 and sorted(set(case.sizes.tolist())) == [5, 8, 9, 32, 100, 256]
+    assert case.counts.min() == 129 and case.counts.max() == 1024
+    assert set(p["forms"].tolist()) == {PRUNED | HI0} and (p["small"], p["tiles"]) == (0, 48)
+
+
+def test_nt_tiles_shape(mc):
+    case, p = _nt(mc, "nt_tiles")
+    assert case.sizes.size == 32 and sorted(set(case.sizes.tolist())) == [3, 8, 33]
+    assert sorted(set(case.counts.tolist())) == [1025, 2085, 3072, 3073]
+    assert set(p["forms"].tolist()) == {SHORT | HI0, PRUNED | HI0}
+    tiles = [-(-int(n) // 1024) for n in case.counts]
+    assert set(tiles) == {2, 3, 4} and p["tiles"] == sum(tiles)
+    # both screened forms under two, three and four tiles
+    for f in (SHORT, PRUNED):
+        assert {t for t, g in zip(tiles, p["forms"]) if g & 3 == f} == {2, 3, 4}
+
+
+def test_nt_exact_shape(mc):
+    case, p = _nt(mc, "nt_exact")
+    assert case.sizes.size == 16 and sorted(set(case.sizes.tolist())) == [257, 300]
+    assert sorted(set(case.counts.tolist())) == [129, 1500]
+    assert set(p["forms"].tolist()) == {EXACT | HI0}          # with screening on: by length
+    assert case.sizes.min() > 256 and p["small"] == 0
+    for d in (257, 300):
+        assert set(case.counts[case.sizes == d].tolist()) == {129, 1500}
+
+
+def test_nt_overflow_shape(mc):
+    case, p = _nt(mc, "nt_overflow", cpt=2048)
+    ladder = S.cpt_ladder("t21p")
+    assert np.array_equal(case.sizes, ladder.sizes) and np.array_equal(case.counts, ladder.counts)
+    assert p["T"] == 2 ** 21 + 1
+    c = (I64 * 10)()
+    mc.mc_importance_consts(c)
+    assert p["cpt"] > c[9]                                    # a tile outgrows the survivor list
+    assert case.sizes[case.certify].tolist() == S.CPT_LADDER_DIMS
+    assert case.counts[case.certify].tolist() == S.cpt_ladder_counts(2048)
+    assert int((case.counts[case.certify] > c[9]).sum()) >= 8
+    assert {PRUNED | HI0, SHORT | HI0} <= set(p["forms"][case.certify].tolist())
+
+
+def test_nt_sum_shape(mc):
+    case, p = _nt(mc, "nt_sum", cpt=2048)
+    assert case.sizes.size == 64 and sorted(set(case.sizes.tolist())) == [9, 33, 100]
+    assert set(case.counts.tolist()) == {S.NT_SUM_ROWS} and case.lead == S.NT_SUM_LEAD
+    assert set(p["forms"].tolist()) == {PRUNED | HI0}
+    assert p["tiles"] == 64 * -(-S.NT_SUM_ROWS // 2048) and p["small"] == 0   # 30 tiles a group
