@@ -143,6 +143,10 @@ SIGNATURES = {
     "cwq_selftest_encode_uniform_tau_guess": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int,
                                                       c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp,
                                                       c_size, c_opts, c_vp, c_int]),
+    "cwq_greedy_encode_uniform_defer_bytes": (c_size, [c_i64, c_i64]),
+    "cwq_selftest_encode_uniform_defer": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int,
+                                                  c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp,
+                                                  c_size, c_opts, c_vp, c_int]),
     "cwq_beam_encode_workspace_size": (c_size, [c_i64, c_i64, c_i64, c_int, c_int]),
     "cwq_beam_encode": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int,
                                 c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp, c_size, c_opts,
@@ -180,7 +184,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 15
+ABI_VERSION = (0 << 16) | 16
 
 _lib = None
 

@@ -106,10 +106,12 @@ class Normal:
 def encode_workspace_bytes(nb, total_dims, block_dim=None, max_block_dim=None):
     """Workspace bytes of encode_blocks: CSR blocks (nb, total_dims, none
     longer than ``max_block_dim``, default total_dims), or uniform blocks of
-    ``block_dim`` (cwq_greedy_encode[_uniform]_workspace_size)."""
+    ``block_dim`` (cwq_greedy_encode_workspace_size;
+    cwq_greedy_encode_uniform_defer_bytes: the uniform encoder's layout with the
+    regions that let it defer the pruned kernel's exact work)."""
     lib = _lib.load()
     if block_dim is not None:
-        return int(lib.cwq_greedy_encode_uniform_workspace_size(int(nb), int(block_dim)))
+        return int(lib.cwq_greedy_encode_uniform_defer_bytes(int(nb), int(block_dim)))
     mbd = int(total_dims if max_block_dim is None else max_block_dim)
     return int(lib.cwq_greedy_encode_workspace_size(int(nb), int(total_dims), mbd))
 

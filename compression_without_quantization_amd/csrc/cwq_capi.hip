@@ -335,7 +335,7 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
                 void* workspace, size_t workspace_bytes, const cwq_options* opts, void* stream,
                 const int32_t* block_seeds = nullptr, float* ds_out = nullptr,
                 const float* ds_loc = nullptr, const float* ds_scale = nullptr,
-                bool rows_wave = false, int tau_guess = -1) {
+                bool rows_wave = false, int tau_guess = -1, int defer_mode = -2) {
   int rc = check_common(n_bits, n_steps, nb);
   if (rc) return rc;
   cwq_options o;
@@ -359,6 +359,25 @@ int encode_impl(const float* t_loc, const float* t_scale, const float* p_loc,
   a.ds_scale = ds_scale;
   a.rows_wave = rows_wave;
   a.tau_guess = tau_guess;
+  // Deferral (defer_mode -2: not this call's; -1: the launcher's rule; 0 .. 3:
+  // cwq_selftest_encode_uniform_defer): the regions behind the encoder's layout,
+  // where the caller's workspace has them (cwq_greedy_encode_uniform_defer_bytes)
+  if (defer_mode >= -1 && !block_off) {
+    const cwq::DeferWs dl = cwq::defer_ws(l.total, nb, ud);
+    if (defer_mode >= 0 && (rc = check_ws(workspace, workspace_bytes, dl.total, NullWs::TakenIfEmpty)))
+      return rc;
+    if (dl.surv.bytes && workspace && workspace_bytes >= dl.total) {
+      a.defer_surv = at<uint32_t>(workspace, dl.surv);
+      a.defer_count = at<uint32_t>(workspace, dl.count);
+      a.defer_list = at<uint32_t>(workspace, dl.dlist);
+      a.defer_dcount = at<uint32_t>(workspace, dl.dcount);
+      a.defer_mode = defer_mode;
+    }
+    if (defer_mode >= 0 && dl.surv.bytes) {  // every block one tile, whatever the call's size
+      a.tiles_per_block = 1;
+      a.cand_per_tile = (a.n_cand + 255) / 256 * 256;
+    }
+  }
   hipError_t e = cwq::launch_encode(a, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode");
   return ok();
@@ -484,6 +503,11 @@ size_t cwq_greedy_encode_uniform_workspace_size(int64_t nb, int64_t d) {
   return cwq::enc_ws_uniform(nb, d).total;
 }
 
+size_t cwq_greedy_encode_uniform_defer_bytes(int64_t nb, int64_t d) {
+  if (nb < 0 || d < 0 || (d > 0 && nb > INT64_MAX / d)) return 0;
+  return cwq::defer_ws_uniform(nb, d).total;
+}
+
 int cwq_greedy_encode(const float* t_loc, const float* t_scale, const float* p_loc,
                       const float* p_scale, const int64_t* block_off, int64_t nb,
                       int64_t total_dims, int64_t max_block_dim, int n_bits_per_step,
@@ -507,7 +531,8 @@ int cwq_greedy_encode_uniform(const float* t_loc, const float* t_scale, const fl
   if (nb < 0 || (d > 0 && nb > INT64_MAX / d)) return fail(CWQ_ERR_INVALID, "bad nb");
   return encode_impl(t_loc, t_scale, p_loc, p_scale, nullptr, d, nb, nb * d, d, n_bits_per_step,
                      n_steps, seed, rho, block_id_base, out_idx, out_sample, workspace,
-                     workspace_bytes, opts, stream);
+                     workspace_bytes, opts, stream, nullptr, nullptr, nullptr, nullptr,
+                     /*rows_wave=*/false, /*tau_guess=*/-1, /*defer_mode=*/-1);
 }
 
 int cwq_greedy_decode(const int32_t* idx, const float* p_loc, const float* p_scale,
@@ -2952,6 +2977,22 @@ int cwq_selftest_encode_uniform_tau_guess(const float* t_loc, const float* t_sca
                      n_steps, seed, rho, block_id_base, out_idx, out_sample, workspace,
                      workspace_bytes, opts, stream, nullptr, nullptr, nullptr, nullptr,
                      /*rows_wave=*/false, guess_mode);
+}
+
+int cwq_selftest_encode_uniform_defer(const float* t_loc, const float* t_scale,
+                                      const float* p_loc, const float* p_scale, int64_t nb,
+                                      int64_t d, int n_bits_per_step, int n_steps, int32_t seed,
+                                      float rho, int64_t block_id_base, int32_t* out_idx,
+                                      float* out_sample, void* workspace, size_t workspace_bytes,
+                                      const cwq_options* opts, void* stream, int defer_mode) {
+  if (d < 0) return fail(CWQ_ERR_INVALID, "d must be >= 0");
+  if (nb < 0 || (d > 0 && nb > INT64_MAX / d)) return fail(CWQ_ERR_INVALID, "bad nb");
+  if (defer_mode < 0 || defer_mode > 3)
+    return fail(CWQ_ERR_INVALID, "defer_mode=%d outside [0, 3]", defer_mode);
+  return encode_impl(t_loc, t_scale, p_loc, p_scale, nullptr, d, nb, nb * d, d, n_bits_per_step,
+                     n_steps, seed, rho, block_id_base, out_idx, out_sample, workspace,
+                     workspace_bytes, opts, stream, nullptr, nullptr, nullptr, nullptr,
+                     /*rows_wave=*/false, /*tau_guess=*/-1, defer_mode);
 }
 
 namespace {

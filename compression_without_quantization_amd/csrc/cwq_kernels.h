@@ -46,6 +46,14 @@ struct EncodeArgs {
   // tile queue counters of k_encode_prune (kTileQueueSlots u32, one per fork
   // part; nullptr: static tile loop); zeroed by the launcher before each launch
   uint32_t* tq = nullptr;
+  // deferred exact work of k_encode_prune's one-tile-per-block launches
+  // (defer_ws, cwq_workspace.h); nullptr: the single launch.  defer_mode: -1 the
+  // launcher's rule, 0 off, 1 on, 2 every tile deferred, 3 Q = 0 (tests)
+  uint32_t* defer_surv = nullptr;
+  uint32_t* defer_count = nullptr;
+  uint32_t* defer_list = nullptr;
+  uint32_t* defer_dcount = nullptr;
+  int defer_mode = -1;
   float* loc_s;              // [total_dims]
   float* scale_s;            // [total_dims]
   float* lognorm;            // [total_dims]

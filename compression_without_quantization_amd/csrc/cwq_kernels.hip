@@ -164,8 +164,13 @@ constexpr float kPruneC1 = 0x1p-14f;
 #ifndef CWQ_PRUNE_MIN_WAVES
 #define CWQ_PRUNE_MIN_WAVES 6  // waves/SIMD the register allocator must allow (tools/variants.sh)
 #endif
+#ifndef CWQ_DEFER_MIN_WAVES
+// ... for the screening-only form (FORM 1), which holds no exact arithmetic;
+// its tile queue grid is 256 CUs x this many resident workgroups
+#define CWQ_DEFER_MIN_WAVES 8
+#endif
 #ifndef CWQ_XCD_BALANCE
-#define CWQ_XCD_BALANCE 1  // INTER tiles: each XCD runs every block (see k_encode_prune)
+#define CWQ_XCD_BALANCE 1 // INTER tiles: each XCD runs every block (see k_encode_prune)
 #endif
 #ifndef CWQ_TAU_SHARE_MASK
 // k_encode_prune shares tau across the workgroup every 8 units: a share is one
@@ -286,31 +291,40 @@ static_assert(sizeof(VisitRec) == 48, "VisitRec: 48 bytes");
 // eight accumulators of eval_row_f, whose tail sum stays the +0 it starts from
 // since D % 8 == 0.  Returns to every lane of 8 r .. 8 r + 7 the value of row
 // r < cnt, eval_row<D, STEP0>'s bit for bit.  Full exec mask; cnt is uniform.
+//
+// The two halves are functions of their own, which k_score_survivors shares:
+// there the rows of one pass come from different blocks, so the stream and the
+// constants are the lane's.
+// The four terms of Philox block u of `row` into rowterms[4 u .. 4 u + 3]
+// (rowterms: the row's D terms; the constants: the row's block).
 template <int D, bool STEP0>
-__device__ __forceinline__ float score_rows_wave(
-    const PhiloxStream& st, const uint32_t* rows, uint32_t cnt, const float* __restrict__ loc_s,
+__device__ __forceinline__ void score_block_terms(
+    const PhiloxStream& st, uint32_t row, uint32_t u, const float* __restrict__ loc_s,
     const float* __restrict__ scale_s, const float* __restrict__ mu,
     const float* __restrict__ sg, const float* __restrict__ lognorm,
-    const float* __restrict__ best, const double* logtab, float* buf, uint32_t lane) {
+    const float* __restrict__ best, const double* logtab, float* rowterms) {
   constexpr uint32_t G = D / 4;
-  const uint32_t r = lane / G, u = lane - r * G;
-  if (r < cnt) {
-    const F4 z = normal4_dev(st, (uint64_t)rows[r] * G + u, logtab);
+  const F4 z = normal4_dev(st, (uint64_t)row * G + u, logtab);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint32_t j = 4u * u + (uint32_t)t;
-      const float zz = t == 0 ? z.a : (t == 1 ? z.b : (t == 2 ? z.c : z.d));
-      float v = scale_s[j] * zz;  // misc.py:14
-      v = loc_s[j] + v;           // misc.py:15
-      const float tv = STEP0 ? v : best[j] + v;
-      buf[r * D + j] = log_prob(tv, mu[j], sg[j], lognorm[j]);
-    }
+  for (int t = 0; t < 4; ++t) {
+    const uint32_t j = 4u * u + (uint32_t)t;
+    const float zz = t == 0 ? z.a : (t == 1 ? z.b : (t == 2 ? z.c : z.d));
+    float v = scale_s[j] * zz;  // misc.py:14
+    v = loc_s[j] + v;           // misc.py:15
+    const float tv = STEP0 ? v : best[j] + v;
+    rowterms[j] = log_prob(tv, mu[j], sg[j], lognorm[j]);
   }
+}
+// The Eigen-order sum of the rows' terms in buf (row r's at buf + r D): lanes
+// 8 r .. 8 r + 7 get row r's value where `valid` (the same in those eight
+// lanes).  Waits for the wave's writes of buf first.  Full exec mask.
+template <int D>
+__device__ __forceinline__ float score_fold8(const float* buf, uint32_t lane, bool valid) {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
   float acc = 0.0f;
   const uint32_t fr = lane >> 3;
-  if (fr < cnt)
+  if (valid)
     for (uint32_t e = lane & 7u; e < (uint32_t)D; e += 8u) acc = acc + buf[fr * D + e];
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -319,6 +333,33 @@ __device__ __forceinline__ float score_rows_wave(
   for (int l = 0; l < 8; ++l) p[l] = __shfl(acc, (int)((lane & ~7u) + (uint32_t)l), 64);
   return eigen_fold8(p, 0.0f);
 }
+template <int D, bool STEP0>
+__device__ __forceinline__ float score_rows_wave(
+    const PhiloxStream& st, const uint32_t* rows, uint32_t cnt, const float* __restrict__ loc_s,
+    const float* __restrict__ scale_s, const float* __restrict__ mu,
+    const float* __restrict__ sg, const float* __restrict__ lognorm,
+    const float* __restrict__ best, const double* logtab, float* buf, uint32_t lane) {
+  constexpr uint32_t G = D / 4;
+  const uint32_t r = lane / G, u = lane - r * G;
+  if (r < cnt)
+    score_block_terms<D, STEP0>(st, rows[r], u, loc_s, scale_s, mu, sg, lognorm, best, logtab,
+                                buf + r * D);
+  return score_fold8<D>(buf, lane, (lane >> 3) < cnt);
+}
+
+// What the screening-only form of k_encode_prune (FORM 1) and the launch over
+// the deferred list (FORM 2) take beyond the kernel's own arguments; the
+// single-launch form (FORM 0) takes nothing.
+template <int FORM>
+struct DeferArgs {
+  uint32_t* surv;    // [nb][kDeferSlots]
+  uint32_t* count;   // [nb]
+  uint32_t* list;    // [nb]
+  uint32_t* dcount;  // the list's length
+  int q;             // Q in [0, kDeferSlots]; -1: every tile is deferred (tests)
+};
+template <>
+struct DeferArgs<0> {};
 
 #ifdef CWQ_TILE_TIMES
 // timing builds only (tools/tile_times.py): per tile of k_encode_prune its
@@ -388,16 +429,31 @@ __device__ __forceinline__ void unroll_each(F& f, std::integer_sequence<uint32_t
 
 // PARK: the screening loop without its per-iteration completion test
 // (CWQ_PARK_COMPLETE; chosen per launch from the rows per tile, launch_prune_t)
-template <int D, bool STEP0, bool INTER, bool PARK>
-__global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
+//
+// FORM (one tile per block, INTER = false; DESIGN.md 4 "Deferral"):
+//   0  the whole of the above in one launch.
+//   1  screening only.  The loop, the set-up, the guess and its retry are the
+//      same; at the tile's end the rows of the survivor list that reach
+//      tau_final go to the block's slots in the workspace (DeferArgs::surv,
+//      count) and k_score_survivors scores them.  A tile that fails the
+//      screening gate, whose list overflows or that has more than Q such rows
+//      writes count 0 and its block to the deferred list instead: it runs
+//      again under FORM 2.  Every tile writes its count; keys is not touched.
+//      Nothing here scores a row exactly, so the f64 code and its registers
+//      are not in this form (CWQ_DEFER_MIN_WAVES).
+//   2  FORM 0 over the deferred list: tile t is block list[t], t < *dcount.
+template <int D, bool STEP0, bool INTER, bool PARK, int FORM = 0>
+__global__ void __launch_bounds__(256, FORM == 1 ? CWQ_DEFER_MIN_WAVES : CWQ_PRUNE_MIN_WAVES)
+k_encode_prune(
     const float* __restrict__ t_loc, const float* __restrict__ t_scale,
     const float* __restrict__ loc_s, const float* __restrict__ scale_s,
-    const float* __restrict__ lognorm, const float* __restrict__ best, int64_t ntiles,
+    const float* __restrict__ lognorm, const float* __restrict__ best, int64_t ntiles_arg,
     int64_t tiles_per_block, int64_t cand_per_tile, int64_t n_cand, SeedSpec sd, int32_t step,
     int allow_screen, unsigned long long* __restrict__ keys, int64_t tail_from, int tail_div,
-    uint32_t* __restrict__ tq) {
+    uint32_t* __restrict__ tq, DeferArgs<FORM> df) {
   static_assert(D % 8 == 0 && D >= 8 && D <= 64, "pruned path: D % 8 == 0, D <= 64");
   static_assert(!PARK || CWQ_PARK_COMPLETE, "PARK instances exist in CWQ_PARK_COMPLETE builds only");
+  static_assert(FORM == 0 || !INTER, "deferral: one tile per block");
   constexpr int G = D / 4;
   constexpr int NF = STEP0 ? 6 : 7;  // loc_s, scale_s, mu, sigma, c, 1/sigma[, best]
   // survivor rows one wave scores per pass: a lane per Philox block of a row,
@@ -439,7 +495,14 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
   __shared__ uint32_t s_ps[72];
   for (int i = threadIdx.x; i < 72; i += blockDim.x) s_ps[i] = 0u;
 #endif
-  fill_logtab(logtab);
+  __shared__ uint32_t dq_cnt;  // FORM 1: the list's rows that reach tau_final
+  // (FORM 1 scores nothing: no table, no rowbuf, no wkey)
+  if constexpr (FORM != 1) fill_logtab(logtab);
+  int64_t ntiles = ntiles_arg;
+  if constexpr (FORM == 2) {  // the deferred list's length: uniform, and at most nb < 2^31
+    ntiles = (int64_t)__builtin_amdgcn_readfirstlane((int)*df.dcount);
+    if (ntiles > ntiles_arg) ntiles = ntiles_arg;
+  }
   const uint32_t wv = wave_id();
   const uint32_t lane = threadIdx.x & 63u;
 
@@ -488,8 +551,12 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     if (inter && CWQ_XCD_BALANCE && tq == nullptr && tile < treg && (treg & 7) == 0 &&
         (gridDim.x & 7u) == 0)
       tord = (tile & 7) * (treg >> 3) + (tile >> 3);
-    const int64_t g = inter ? tord % nbt : tile / tiles_per_block;
-    const int64_t tt = inter ? tord / nbt : tile - g * tiles_per_block;
+    int64_t g = inter ? tord % nbt : tile / tiles_per_block;
+    int64_t tt = inter ? tord / nbt : tile - g * tiles_per_block;
+    if constexpr (FORM == 2) {  // the tile of a listed block (tile < *dcount <= nb)
+      g = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)df.list[tile]);
+      tt = 0;
+    }
     const int64_t off = g * D;
     // a block's tiles from tail_from on are tail_div times smaller: the last
     // rounds of the launch drain in short tiles (INTER; tail_div 1: no tail)
@@ -590,7 +657,8 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     const bool scr_all = __syncthreads_and(scr_ok) != 0;
     // (e) drop bounds: thread k computes B_k for the first k visited groups
     //     (exact or screening form); thread G + 1 the screening constants
-    const bool screen = (allow_screen & 1) && scr_all;
+    bool screen = (allow_screen & 1) && scr_all;
+    if constexpr (FORM == 1) screen = screen && df.q >= 0;  // (q < 0: every tile deferred)
     // tau guess (cwq_tau_guess.h): while wave 0 sums the bounds below, wave 1
     // solves for q_m, a dim per lane, from the records (d) has just written
     if (wv == 1u) {
@@ -1052,7 +1120,8 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
             if (slot < CWQ_SURVIVOR_CAP) {
               sq_n[slot] = (uint32_t)n;
               sq_ub[slot] = upper;
-            } else {  // list full (near-ties everywhere): evaluate exactly now
+            } else if constexpr (FORM != 1) {  // list full (near-ties everywhere): evaluate exactly now
+              // (FORM 1: sq_cnt has passed the cap, which defers the tile)
 #ifdef CWQ_PRUNE_STATS
               atomicAdd(&g_prune_stats[69], 1ull);
 #endif
@@ -1255,65 +1324,99 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
         __syncthreads();
         tau = (INTER && CWQ_TAU_FROM_KEYS) ? seed : -__builtin_inff();
       }
+    } else if constexpr (FORM == 1) {  // gate failed: the tile is deferred (below)
+      tau_final = tau;
     } else {  // the exact pass takes no guess (qm_cell: kTauNoGuess)
       pass(std::false_type{});
       tau_share_wave(&tau_cell, tau);
       __syncthreads();
       tau_final = tau_cell;
     }
-    // exact evaluation of the survivors that can still reach the final tau
-    const uint32_t nsurv = sq_cnt < CWQ_SURVIVOR_CAP ? sq_cnt : CWQ_SURVIVOR_CAP;
-    // A wave takes the list 64 entries at a time, packs those that reach
-    // tau_final to the front of its 64 (in place: every lane has read its
-    // entry before any writes) and scores them RW rows per pass, a lane per
-    // Philox block (score_rows_wave).  All of it is wave-uniform.  The lane
-    // comes from the tile's opaque tid, so that the rows' per-lane addresses
-    // are not hoisted out of the tile loop and spilled.
-    const uint32_t nsurv_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)nsurv);
-    const uint32_t sl = tid & 63u;
-    for (uint32_t c0 = wv * 64u; c0 < nsurv_u; c0 += 256u) {
-      const uint32_t i = c0 + sl;
-      const bool q = i < nsurv_u && sq_ub[i] >= tau_final;
-      const uint32_t nn = i < nsurv_u ? sq_n[i] : 0u;
-      const uint64_t qm = __builtin_amdgcn_ballot_w64(q);
-      if (qm == 0ull) continue;
-#ifdef CWQ_PRUNE_STATS
-      if (q) atomicAdd(&g_prune_stats[68], 1ull);
-#endif
-      const uint32_t qr = __builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32),
-                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (q) sq_n[c0 + qr] = nn;
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const uint32_t qn = (uint32_t)__builtin_popcountll(qm);
-      for (uint32_t b = 0; b < qn; b += (uint32_t)RW) {
-        const uint32_t cnt = qn - b < (uint32_t)RW ? qn - b : (uint32_t)RW;
-        const float v = score_rows_wave<D, STEP0>(
-            st, sq_n + c0 + b, cnt, loc_s + off, scale_s + off, t_loc + off, t_scale + off,
-            lognorm + off, STEP0 ? nullptr : best + off, logtab, rowbuf[wv], sl);
-        if ((sl & 7u) == 0u && (sl >> 3) < cnt) {
-          const uint64_t kv = argmax_key(v, sq_n[c0 + b + (sl >> 3)]);
-          bestk = kv > bestk ? kv : bestk;
+    if constexpr (FORM == 1) {
+      // The rows that reach tau_final into the block's slots, their number
+      // into its count word; with more than Q of them, a list past its cap or
+      // no screening pass, count 0 and the block onto the deferred list.  The
+      // slots' order is the order of arrival: k_score_survivors takes a max.
+      // (sq_cnt and screen are the workgroup's: the branches are uniform.)
+      const uint32_t pushed = sq_cnt;
+      const bool listed = screen && pushed <= (uint32_t)CWQ_SURVIVOR_CAP;
+      const uint32_t qmax = df.q > 0 ? (uint32_t)df.q : 0u;  // <= kDeferSlots (launch_prune_t)
+      if (tid == 0) dq_cnt = 0u;
+      __syncthreads();
+      if (listed) {
+        for (uint32_t i = tid; i < pushed; i += 256u) {
+          if (sq_ub[i] >= tau_final) {
+            const uint32_t slot = atomicAdd(&dq_cnt, 1u);
+            if (slot < qmax) df.surv[cwq::defer_slot(g, (int)slot)] = sq_n[i];
+          }
         }
       }
-    }
-
-    bestk = wave_max_u64(bestk);
-    if (lane == 0) wkey[wv] = bestk;
-    __syncthreads();
-    if (tid == 0) {
-      uint64_t mk = wkey[0];
-      for (int i = 1; i < 4; ++i) mk = wkey[i] > mk ? wkey[i] : mk;
-      if (mk) atomicMax(&keys[g], (unsigned long long)mk);
+      __syncthreads();
+      if (tid == 0) {
+        const uint32_t c = dq_cnt;
+        const bool deferred = !listed || c > qmax;
+        df.count[g] = deferred ? 0u : cwq::defer_count_word(c, (int)qmax);
+        if (deferred) {  // (a block is listed once, so the slot is below nb: the test guards the store)
+          const uint32_t at = atomicAdd(df.dcount, 1u);
+          if ((int64_t)at < ntiles_arg) df.list[at] = (uint32_t)g;
+        }
+      }
+      __syncthreads();
+    } else {
+      // exact evaluation of the survivors that can still reach the final tau
+      const uint32_t nsurv = sq_cnt < CWQ_SURVIVOR_CAP ? sq_cnt : CWQ_SURVIVOR_CAP;
+      // A wave takes the list 64 entries at a time, packs those that reach
+      // tau_final to the front of its 64 (in place: every lane has read its
+      // entry before any writes) and scores them RW rows per pass, a lane per
+      // Philox block (score_rows_wave).  All of it is wave-uniform.  The lane
+      // comes from the tile's opaque tid, so that the rows' per-lane addresses
+      // are not hoisted out of the tile loop and spilled.
+      const uint32_t nsurv_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)nsurv);
+      const uint32_t sl = tid & 63u;
+      for (uint32_t c0 = wv * 64u; c0 < nsurv_u; c0 += 256u) {
+        const uint32_t i = c0 + sl;
+        const bool q = i < nsurv_u && sq_ub[i] >= tau_final;
+        const uint32_t nn = i < nsurv_u ? sq_n[i] : 0u;
+        const uint64_t qm = __builtin_amdgcn_ballot_w64(q);
+        if (qm == 0ull) continue;
 #ifdef CWQ_PRUNE_STATS
-      if (!g_seed_tau && g < kDbgBlocks) g_dbg_best[g] = mk;
+        if (q) atomicAdd(&g_prune_stats[68], 1ull);
+#endif
+        const uint32_t qr = __builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32),
+                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (q) sq_n[c0 + qr] = nn;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t qn = (uint32_t)__builtin_popcountll(qm);
+        for (uint32_t b = 0; b < qn; b += (uint32_t)RW) {
+          const uint32_t cnt = qn - b < (uint32_t)RW ? qn - b : (uint32_t)RW;
+          const float v = score_rows_wave<D, STEP0>(
+              st, sq_n + c0 + b, cnt, loc_s + off, scale_s + off, t_loc + off, t_scale + off,
+              lognorm + off, STEP0 ? nullptr : best + off, logtab, rowbuf[wv], sl);
+          if ((sl & 7u) == 0u && (sl >> 3) < cnt) {
+            const uint64_t kv = argmax_key(v, sq_n[c0 + b + (sl >> 3)]);
+            bestk = kv > bestk ? kv : bestk;
+          }
+        }
+      }
+
+      bestk = wave_max_u64(bestk);
+      if (lane == 0) wkey[wv] = bestk;
+      __syncthreads();
+      if (tid == 0) {
+        uint64_t mk = wkey[0];
+        for (int i = 1; i < 4; ++i) mk = wkey[i] > mk ? wkey[i] : mk;
+        if (mk) atomicMax(&keys[g], (unsigned long long)mk);
+#ifdef CWQ_PRUNE_STATS
+        if (!g_seed_tau && g < kDbgBlocks) g_dbg_best[g] = mk;
 #endif
 #ifdef CWQ_TILE_TIMES
-      if (tile < kTileTimes) g_tile_t1[tile] = __builtin_amdgcn_s_memrealtime();
+        if (tile < kTileTimes) g_tile_t1[tile] = __builtin_amdgcn_s_memrealtime();
 #endif
-    }
+      }
+    }  // FORM != 1
 #ifdef CWQ_PRUNE_STATS
     if (tid < 72) {
       if (s_ps[tid]) atomicAdd(&g_prune_stats[tid], (unsigned long long)s_ps[tid]);
@@ -1321,6 +1424,67 @@ __global__ void __launch_bounds__(256, CWQ_PRUNE_MIN_WAVES) k_encode_prune(
     }
 #endif
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The rows k_encode_prune's screening-only form listed (FORM 1), scored
+// exactly: eval_row<D, STEP0>'s value bit for bit (score_block_terms and
+// score_fold8 are score_rows_wave's halves), folded into keys[g] by atomicMax.
+//
+// A wave takes RW = min(64 / G, 8) consecutive blocks, the first row of each in
+// one pass: lane l computes Philox block l % G of block l / G's row, with that
+// block's stream and constants, and lanes 8 r .. 8 r + 7 sum block r's terms
+// (eight lanes per row in the fold, hence at most 8 rows; at d <= 24 the lanes
+// past 8 G idle).  Rows past a block's first go in further passes, over the
+// slot index, as long as any block of the wave has one: the loop is uniform.
+// A count word is at most kDeferSlots (k_encode_prune writes min(c, Q) or 0);
+// it is clamped here all the same, so that the slots read stay the block's.
+// ---------------------------------------------------------------------------
+// The deferred list's length, zeroed before the screening-only launch.  A
+// launch, not a memset as for the tile queue: with a memset here the replay of
+// a captured multi-step call gave wrong indices from step 1 on.
+__global__ void k_defer_reset(uint32_t* __restrict__ dcount) {
+  if (threadIdx.x == 0) *dcount = 0u;
+}
+
+template <int D, bool STEP0>
+__global__ void __launch_bounds__(256) k_score_survivors(
+    const float* __restrict__ t_loc, const float* __restrict__ t_scale,
+    const float* __restrict__ loc_s, const float* __restrict__ scale_s,
+    const float* __restrict__ lognorm, const float* __restrict__ best, int64_t nb, SeedSpec sd,
+    int32_t step, const uint32_t* __restrict__ surv, const uint32_t* __restrict__ count,
+    unsigned long long* __restrict__ keys) {
+  constexpr uint32_t G = D / 4;
+  constexpr uint32_t RW = (64 / G) < 8 ? (64 / G) : 8;
+  __shared__ double logtab[32];
+  __shared__ float rowbuf[4][RW * D];
+  fill_logtab(logtab);
+  const uint32_t wv = wave_id();
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t g0 = ((int64_t)blockIdx.x * 4 + wv) * RW;
+  // the lane's block as a term lane (r, u) and as a fold lane (fr)
+  const uint32_t r = lane / G, u = lane - r * G, fr = lane >> 3;
+  const int64_t g = g0 + r, gf = g0 + fr;
+  const bool term_lane = r < RW && g < nb, fold_lane = fr < RW && gf < nb;
+  uint32_t cnt = term_lane ? count[g] : 0u, cntf = fold_lane ? count[gf] : 0u;
+  cnt = cnt < (uint32_t)cwq::kDeferSlots ? cnt : (uint32_t)cwq::kDeferSlots;
+  cntf = cntf < (uint32_t)cwq::kDeferSlots ? cntf : (uint32_t)cwq::kDeferSlots;
+  if (__builtin_amdgcn_ballot_w64(cnt != 0u) == 0ull) return;  // (uniform)
+  PhiloxStream st{};
+  if (cnt != 0u) st = generate_key(step_seed(sd.of(g), step), 42);
+  const int64_t off = g * D;
+  for (uint32_t q = 0; q < (uint32_t)cwq::kDeferSlots; ++q) {
+    if (__builtin_amdgcn_ballot_w64(q < cnt) == 0ull) break;  // (uniform)
+    if (q < cnt)
+      score_block_terms<D, STEP0>(st, surv[cwq::defer_slot(g, (int)q)], u, loc_s + off,
+                                  scale_s + off, t_loc + off, t_scale + off, lognorm + off,
+                                  STEP0 ? nullptr : best + off, logtab, rowbuf[wv] + r * D);
+    const float v = score_fold8<D>(rowbuf[wv], lane, q < cntf);
+    if ((lane & 7u) == 0u && q < cntf) {
+      const uint64_t kv = argmax_key(v, surv[cwq::defer_slot(gf, (int)q)]);
+      if (kv) atomicMax(&keys[gf], (unsigned long long)kv);
+    }
   }
 }
 
@@ -3891,7 +4055,7 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                        dim3((unsigned)(nt_s < kPruneGrid ? nt_s : kPruneGrid)), dim3(256), 0,
                        stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                        nt_s, seed_n / cpt_s, cpt_s, seed_n, seeds_of(a), step,
-                       prune_screen_arg(a), a.keys, seed_n / cpt_s, 1, nullptr);
+                       prune_screen_arg(a), a.keys, seed_n / cpt_s, 1, nullptr, DeferArgs<0>{});
   }
   // tile queue (k_encode_prune): a persistent grid of CWQ_QUEUE_GRID workgroups
   // draws tiles from a counter in the workspace, zeroed here before the launch
@@ -3907,13 +4071,37 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
 #ifndef CWQ_QUEUE_MIN_CPT
 #define CWQ_QUEUE_MIN_CPT 4096
 #endif
+  // Deferral (k_encode_prune FORM 1 and 2, k_score_survivors): for one tile per
+  // block, where the caller's workspace has the regions (defer_ws) and the
+  // screening pass is on.  Three more launches cost a fixed 0.15 ms or so (the
+  // launch over an empty deferred list alone is 1,536 workgroups that start and
+  // leave), against 1.3% of the screening kernel's time, so only for calls of
+  // at least CWQ_DEFER_MIN_WORK candidate dims (rows x d): 16,384 blocks of
+  // d = 64 at 16 bits, 12 ms, were 1.2% faster, of d = 32, 4.7 ms, 2% slower
+  // (DESIGN.md 4 "Deferral"); C4 has 2^41.  defer_mode >= 1 (tests) takes it
+  // at any size.
+#ifndef CWQ_DEFER
+#define CWQ_DEFER 1
+#endif
+#ifndef CWQ_DEFER_MIN_WORK
+#define CWQ_DEFER_MIN_WORK (1LL << 36)
+#endif
+  const int64_t tile_rows = a.cand_per_tile < a.n_cand ? a.cand_per_tile : a.n_cand;
+  bool defer = CWQ_DEFER && a.defer_surv && a.defer_count && a.defer_list && a.defer_dcount &&
+               a.defer_mode != 0 && (prune_screen_arg(a) & 1) && a.tiles_per_block == 1 &&
+               !seeded && ntiles < (1LL << 31) &&
+               // (the product can pass 2^63: tile_rows D <= 2^36 divides instead)
+               (a.defer_mode >= 1 || ntiles >= (CWQ_DEFER_MIN_WORK + tile_rows * D - 1) / (tile_rows * D));
+  if (defer) hipLaunchKernelGGL(k_defer_reset, dim3(1), dim3(64), 0, stream, a.defer_dcount);
+  // the queue's grid: every resident slot of the form that runs
+  const int64_t queue_grid = defer ? 256 * (int64_t)CWQ_DEFER_MIN_WAVES : (int64_t)CWQ_QUEUE_GRID;
   uint32_t* tq = nullptr;
   if (CWQ_TILE_QUEUE && a.tq != nullptr && ntiles < (1LL << 31) &&
-      a.cand_per_tile >= CWQ_QUEUE_MIN_CPT && ntiles > CWQ_QUEUE_GRID) {
+      a.cand_per_tile >= CWQ_QUEUE_MIN_CPT && ntiles > queue_grid) {
     if (hipMemsetAsync(a.tq, 0, sizeof(uint32_t), stream) == hipSuccess) tq = a.tq;
   }
   auto qgrid = [&](int64_t nt) -> unsigned {
-    const int64_t cap = tq ? (int64_t)CWQ_QUEUE_GRID : kPruneGrid;
+    const int64_t cap = tq ? queue_grid : kPruneGrid;
     return (unsigned)(nt < cap ? nt : cap);
   };
   // The loop variant (CWQ_PARK_COMPLETE): tiles of CWQ_PARK_MIN_ROWS rows or
@@ -3929,7 +4117,6 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
   // a d = 32 tile and scaled by 32 / d.  The rows are those of a full tile; the
   // tail tiles of such a launch are a quarter of it and start from keys[g], the
   // tiles before them having finished.
-  const int64_t tile_rows = a.cand_per_tile < a.n_cand ? a.cand_per_tile : a.n_cand;
   auto with_park = [&](auto launch) {
     if constexpr (CWQ_PARK_COMPLETE && D >= CWQ_PARK_MIN_D) {
       if (tile_rows * D >= (int64_t)CWQ_PARK_MIN_ROWS * 32) return launch(std::true_type{});
@@ -3957,7 +4144,37 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                          dim3(qgrid(nt2)), dim3(256), 0,
                          stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                          nt2, tpb2, a.cand_per_tile, a.n_cand, seeds_of(a), step,
-                         prune_screen_arg(a), a.keys, from, (int)div, tq);
+                         prune_screen_arg(a), a.keys, from, (int)div, tq, DeferArgs<0>{});
+    });
+  } else if (defer) {
+    // Deferral: the screening-only form lists each block's rows
+    // that reach its tau, k_score_survivors scores them, and the full kernel
+    // runs over the blocks the first launch put on the deferred list, whose
+    // length it reads on the device: a fixed grid, which finds the list empty
+    // as a rule, and no wait on the host.
+    const int q = a.defer_mode == 2 ? -1 : (a.defer_mode == 3 ? 0 : (int)kDeferQ);
+    static_assert(kDeferQ >= 0 && kDeferQ <= kDeferSlots, "Q slots per block");
+    with_park([&](auto park) {
+      hipLaunchKernelGGL((k_encode_prune<D, STEP0, false, decltype(park)::value, 1>),
+                         dim3(qgrid(ntiles)), dim3(256), 0,
+                         stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
+                         ntiles, a.tiles_per_block, a.cand_per_tile, a.n_cand, seeds_of(a), step,
+                         prune_screen_arg(a), a.keys, a.tiles_per_block, 1, tq,
+                         DeferArgs<1>{a.defer_surv, a.defer_count, a.defer_list, a.defer_dcount, q});
+    });
+    constexpr int64_t kRowsPerWg = 4 * ((64 / (D / 4)) < 8 ? (64 / (D / 4)) : 8);
+    hipLaunchKernelGGL((k_score_survivors<D, STEP0>),
+                       dim3((unsigned)((a.nb + kRowsPerWg - 1) / kRowsPerWg)), dim3(256), 0, stream,
+                       a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample, a.nb,
+                       seeds_of(a), step, (const uint32_t*)a.defer_surv,
+                       (const uint32_t*)a.defer_count, a.keys);
+    with_park([&](auto park) {
+      hipLaunchKernelGGL((k_encode_prune<D, STEP0, false, decltype(park)::value, 2>),
+                         dim3((unsigned)(ntiles < 1536 ? ntiles : 1536)), dim3(256), 0,
+                         stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
+                         ntiles, a.tiles_per_block, a.cand_per_tile, a.n_cand, seeds_of(a), step,
+                         prune_screen_arg(a), a.keys, a.tiles_per_block, 1, nullptr,
+                         DeferArgs<2>{a.defer_surv, a.defer_count, a.defer_list, a.defer_dcount, q});
     });
   } else {
     with_park([&](auto park) {
@@ -3965,7 +4182,7 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                          dim3(qgrid(ntiles)), dim3(256), 0,
                          stream, a.t_loc, a.t_scale, a.loc_s, a.scale_s, a.lognorm, a.out_sample,
                          ntiles, a.tiles_per_block, a.cand_per_tile, a.n_cand, seeds_of(a), step,
-                         prune_screen_arg(a), a.keys, a.tiles_per_block, 1, tq);
+                         prune_screen_arg(a), a.keys, a.tiles_per_block, 1, tq, DeferArgs<0>{});
     });
   }
 }
@@ -4312,6 +4529,7 @@ hipError_t launch_encode(const EncodeArgs& a_in, hipStream_t stream) {
     if (a.seeds) p.seeds = a.seeds + g0;
     p.keys = a.keys + g0;
     if (a.tq) p.tq = a.tq + i;  // its own tile queue counter
+    p.defer_surv = nullptr;  // (parts are CSR calls: no deferral, and one list counter)
     p.out_idx = a.out_idx + g0 * a.n_steps;
     if (a.sab) p.sab = a.sab + 8 * g0;
     if (a.bpre) p.bpre = a.bpre + 12 * g0;

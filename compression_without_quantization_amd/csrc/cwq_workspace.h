@@ -18,6 +18,13 @@
 #ifndef CWQ_CSR_GTAU_STRIDE
 #define CWQ_CSR_GTAU_STRIDE 1  // words between blocks' shared thresholds (tuning builds)
 #endif
+#ifndef CWQ_DEFER_Q
+// rows per block that k_encode_prune's screening-only form lists for
+// k_score_survivors (at most kDeferSlots); a block with more is deferred.  The
+// smallest that defers under 0.1% of C4's blocks: 0.599% of them have more than
+// one such row, 0.0025% more than two (tools/defer_stats.py)
+#define CWQ_DEFER_Q 2
+#endif
 #define CWQ_SLIST_PER_BLOCK 8  // survivor slots per block of the screened small-candidate path
 
 namespace cwq {
@@ -119,6 +126,46 @@ inline EncWs enc_ws_csr(int64_t nb, int64_t total_dims, int64_t max_block_dim) {
 }
 inline EncWs enc_ws_uniform(int64_t nb, int64_t d) {
   return enc_ws(nb, nb * d, has_screen_arrays(false, d, nb), has_long_block_records(false, d, nb));
+}
+
+// ---- deferred exact work of the pruned uniform encoder (DESIGN.md 4 "Deferral") ----
+// Behind the encoder's layout, for the shapes k_encode_prune runs one tile per
+// block at (defer_shape): the screening-only launch leaves per block
+//   surv   [nb][kDeferSlots] u32: the rows that reach the tile's final tau
+//   count  [nb] u32: how many of its slots are filled, 0 .. Q <= kDeferSlots;
+//          0 also for a block that is on the deferred list
+//   dlist  [nb] u32: the blocks whose tile runs again in the full kernel
+//   dcount one u32: their number (zeroed on the stream before the launch)
+// The encoder's own layout and cwq_greedy_encode_uniform_workspace_size stay
+// what they were: a caller that sizes its workspace with
+// cwq_greedy_encode_uniform_defer_bytes gets these regions behind it and the
+// three-launch form; one that gives the smaller size gets the single launch.
+constexpr int kDeferSlots = 4;  // slots per block: the largest Q
+constexpr int kDeferQ = CWQ_DEFER_Q;  // Q: rows per block that the dense scoring launch takes
+inline bool defer_shape(int64_t nb, int64_t d) {
+  return nb > 0 && nb < (1LL << 31) && d % 8 == 0 && d >= 8 && d <= 64;
+}
+// (constexpr: the kernels index with it too)
+constexpr size_t defer_slot(int64_t g, int q) { return (size_t)g * kDeferSlots + (size_t)q; }
+// the count word of a block with c rows listed (c > Q: deferred, no row listed)
+constexpr uint32_t defer_count_word(uint32_t c, int Q) { return c <= (uint32_t)Q ? c : 0u; }
+struct DeferWs {
+  Region surv, count, dlist, dcount;
+  size_t total;
+};
+inline DeferWs defer_ws(size_t enc_total, int64_t nb, int64_t d) {
+  DeferWs l;
+  Arena a{Arena::up(enc_total)};
+  const size_t n = defer_shape(nb, d) ? (size_t)nb : 0;
+  l.surv = a.take(n * kDeferSlots * 4);
+  l.count = a.take(n * 4);
+  l.dlist = a.take(n * 4);
+  l.dcount = a.take(n ? 4 : 0);
+  l.total = a.o;
+  return l;
+}
+inline DeferWs defer_ws_uniform(int64_t nb, int64_t d) {
+  return defer_ws(enc_ws_uniform(nb, d).total, nb, d);
 }
 
 // ---- blocks sorted by bit budget: the sorted view (cwq_capi.hip sort_blocks) ----

@@ -112,8 +112,13 @@ extern "C" {
  *        starts its threshold from a predicted level; same results);
  *   0.15 beam search under per-block bit budgets: cwq_beam_encode_var and
  *        cwq_selftest_beam_encode_var (no new size function, no decoder
- *        change; cwq_beam_encode's results are unchanged). */
-#define CWQ_ABI_VERSION ((0 << 16) | 15)
+ *        change; cwq_beam_encode's results are unchanged);
+ *   0.16 cwq_greedy_encode_uniform_defer_bytes and
+ *        cwq_selftest_encode_uniform_defer: cwq_greedy_encode_uniform takes a
+ *        larger workspace and, given one, defers the pruned kernel's exact
+ *        work to launches of its own (same results; every existing size
+ *        function answers what it did). */
+#define CWQ_ABI_VERSION ((0 << 16) | 16)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -684,6 +689,29 @@ int cwq_selftest_encode_uniform_tau_guess(const float* t_loc, const float* t_sca
                                           int32_t* out_idx, float* out_sample, void* workspace,
                                           size_t workspace_bytes, const cwq_options* opts,
                                           void* stream, int guess_mode);
+/* The bytes of a cwq_greedy_encode_uniform workspace with which the call may
+ * defer the pruned kernel's exact work: the layout of
+ * cwq_greedy_encode_uniform_workspace_size with, for blocks of d % 8 == 0,
+ * 8 <= d <= 64 dims, per-block survivor slots, counts and a list of deferred
+ * blocks behind it.  With workspace_bytes of at least this, a call whose
+ * blocks run one tile each scores in three launches: the screening-only
+ * kernel, the listed rows' exact values, and the full kernel over the blocks
+ * the first launch could not settle.  With fewer bytes (at least
+ * cwq_greedy_encode_uniform_workspace_size) it runs as before.  Same results
+ * either way.  Equal to cwq_greedy_encode_uniform_workspace_size for every
+ * other d; 0 for invalid arguments. */
+size_t cwq_greedy_encode_uniform_defer_bytes(int64_t nb, int64_t d);
+/* cwq_greedy_encode_uniform (same arguments, validation and results; the
+ * workspace of cwq_greedy_encode_uniform_defer_bytes) with every block one
+ * tile and the deferral set by defer_mode: 0 = off (the single launch), 1 = on
+ * at any size, 2 = on with every tile deferred, 3 = on with no slot per block
+ * (Q = 0: every tile with a row to score is deferred). */
+int cwq_selftest_encode_uniform_defer(const float* t_loc, const float* t_scale,
+                                      const float* p_loc, const float* p_scale, int64_t nb,
+                                      int64_t d, int n_bits_per_step, int n_steps, int32_t seed,
+                                      float rho, int64_t block_id_base, int32_t* out_idx,
+                                      float* out_sample, void* workspace, size_t workspace_bytes,
+                                      const cwq_options* opts, void* stream, int defer_mode);
 
 /* ---- Beam search over the greedy coder's steps (csrc/cwq_beam.hip) --------
  * cwq_greedy_encode keeps the one best partial sum after each step; this
