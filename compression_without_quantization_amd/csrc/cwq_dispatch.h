@@ -72,6 +72,21 @@ inline void choose_tiling(int64_t nb, int64_t n_cand, int64_t* tiles_per_block,
   *tiles_per_block = (n_cand + cpt - 1) / cpt;
 }
 
+// The tile queue of k_encode_prune (launch_prune_t): a persistent grid of
+// queue_grid workgroups draws tiles from a counter in the workspace.  Only for
+// tiles of real work: with tiny tiles (C1: 16 candidates) the counter's reset
+// and a round trip per tile cost more than the slots they keep busy (C1 0.039
+// -> 0.065 ms with the queue), and only with more tiles than the grid holds.
+#ifndef CWQ_QUEUE_GRID
+#define CWQ_QUEUE_GRID 1536
+#endif
+#ifndef CWQ_QUEUE_MIN_CPT
+#define CWQ_QUEUE_MIN_CPT 4096
+#endif
+inline bool takes_tile_queue(int64_t ntiles, int64_t cand_per_tile, int64_t queue_grid) {
+  return ntiles < (1LL << 31) && cand_per_tile >= CWQ_QUEUE_MIN_CPT && ntiles > queue_grid;
+}
+
 struct EncodeShape {
   bool csr;        // ragged blocks (block_off given); false: uniform blocks of ud dims
   int64_t ud;      // uniform block length (csr: unused)

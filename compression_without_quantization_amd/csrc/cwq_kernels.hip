@@ -1441,11 +1441,24 @@ k_encode_prune(
 // A count word is at most kDeferSlots (k_encode_prune writes min(c, Q) or 0);
 // it is clamped here all the same, so that the slots read stay the block's.
 // ---------------------------------------------------------------------------
-// The deferred list's length, zeroed before the screening-only launch.  A
-// launch, not a memset as for the tile queue: with a memset here the replay of
-// a captured multi-step call gave wrong indices from step 1 on.
-__global__ void k_defer_reset(uint32_t* __restrict__ dcount) {
-  if (threadIdx.x == 0) *dcount = 0u;
+// The one-word counters of a scoring launch, zeroed before it: the deferred
+// list's length and the tile queue's next tile (either may be null).  And the
+// argmax keys of a step after the first.  Launches, not memsets: the encode
+// sequence is kernels only, so that a captured call holds no memset node
+// between its kernel nodes: replays of such nodes did not write the zeros
+// that were captured (DESIGN.md 4 "Graph replay").
+__global__ void k_counters_reset(uint32_t* __restrict__ dcount, uint32_t* __restrict__ tq) {
+  if (threadIdx.x == 0) {
+    if (dcount) *dcount = 0u;
+    if (tq) *tq = 0u;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_keys_reset(unsigned long long* __restrict__ keys,
+                                                    int64_t nb) {
+  for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < nb;
+       g += (int64_t)gridDim.x * blockDim.x)
+    keys[g] = 0ull;
 }
 
 template <int D, bool STEP0>
@@ -4058,18 +4071,10 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                        prune_screen_arg(a), a.keys, seed_n / cpt_s, 1, nullptr, DeferArgs<0>{});
   }
   // tile queue (k_encode_prune): a persistent grid of CWQ_QUEUE_GRID workgroups
-  // draws tiles from a counter in the workspace, zeroed here before the launch
+  // draws tiles from a counter in the workspace, zeroed here before the launch;
+  // for which launches: takes_tile_queue (cwq_dispatch.h)
 #ifndef CWQ_TILE_QUEUE
 #define CWQ_TILE_QUEUE 1
-#endif
-#ifndef CWQ_QUEUE_GRID
-#define CWQ_QUEUE_GRID 1536
-#endif
-  // Only for tiles of real work: with tiny tiles (C1: 16 candidates) the memset
-  // and a counter round trip per tile cost more than the slots they keep busy
-  // (C1 0.039 -> 0.065 ms with the queue)
-#ifndef CWQ_QUEUE_MIN_CPT
-#define CWQ_QUEUE_MIN_CPT 4096
 #endif
   // Deferral (k_encode_prune FORM 1 and 2, k_score_survivors): for one tile per
   // block, where the caller's workspace has the regions (defer_ws) and the
@@ -4092,14 +4097,15 @@ static void launch_prune_t(const EncodeArgs& a, int step, hipStream_t stream) {
                !seeded && ntiles < (1LL << 31) &&
                // (the product can pass 2^63: tile_rows D <= 2^36 divides instead)
                (a.defer_mode >= 1 || ntiles >= (CWQ_DEFER_MIN_WORK + tile_rows * D - 1) / (tile_rows * D));
-  if (defer) hipLaunchKernelGGL(k_defer_reset, dim3(1), dim3(64), 0, stream, a.defer_dcount);
   // the queue's grid: every resident slot of the form that runs
   const int64_t queue_grid = defer ? 256 * (int64_t)CWQ_DEFER_MIN_WAVES : (int64_t)CWQ_QUEUE_GRID;
   uint32_t* tq = nullptr;
-  if (CWQ_TILE_QUEUE && a.tq != nullptr && ntiles < (1LL << 31) &&
-      a.cand_per_tile >= CWQ_QUEUE_MIN_CPT && ntiles > queue_grid) {
-    if (hipMemsetAsync(a.tq, 0, sizeof(uint32_t), stream) == hipSuccess) tq = a.tq;
-  }
+  if (CWQ_TILE_QUEUE && a.tq != nullptr && takes_tile_queue(ntiles, a.cand_per_tile, queue_grid))
+    tq = a.tq;
+  // one launch zeroes the deferred list's length and the queue's counter
+  if (defer || tq)
+    hipLaunchKernelGGL(k_counters_reset, dim3(1), dim3(64), 0, stream,
+                       defer ? a.defer_dcount : nullptr, tq);
   auto qgrid = [&](int64_t nt) -> unsigned {
     const int64_t cap = tq ? queue_grid : kPruneGrid;
     return (unsigned)(nt < cap ? nt : cap);
@@ -4376,10 +4382,11 @@ static hipError_t encode_steps(const EncodeArgs& a, hipStream_t stream, bool eve
   for (int s = 0; s < a.n_steps; ++s) {
     // step 0's keys were zeroed by k_prep_dims (launch_encode); the small
     // pipeline keeps its argmax in registers and LDS and never reads keys
-    if (s > 0 && !plan.self_finalizing &&
-        (e = hipMemsetAsync(a.keys, 0, (size_t)a.nb * sizeof(unsigned long long), stream)) !=
-            hipSuccess)
-      return e;
+    if (s > 0 && !plan.self_finalizing) {
+      hipLaunchKernelGGL(k_keys_reset, dim3(grid_for(a.nb, 256, 4096)), dim3(256), 0, stream,
+                         a.keys, a.nb);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     if (events && s == 0 && a.ev_start) {
       e = hipEventRecord((hipEvent_t)a.ev_start, stream);
       if (e != hipSuccess) return e;

@@ -767,14 +767,20 @@ hipError_t launch_vb_scatter(const float* sample_s, const int32_t* idx_s, const 
 }
 
 
+// The out-of-range flag of launch_vb_offsets, zeroed by a launch: pack and
+// unpack can be captured, and a captured sequence holds no memset node
+// (DESIGN.md 4 "Graph replay").
+static __global__ void k_vb_flag_reset(uint32_t* __restrict__ flag) {
+  if (threadIdx.x == 0) *flag = 0u;
+}
+
 hipError_t launch_vb_offsets(const int32_t* bits, int64_t nb, int n_steps, int64_t* off,
                              int64_t* partial, uint32_t* flag, int64_t* total_out,
                              hipStream_t stream) {
   if (nb <= 0) return hipSuccess;
   if (nb > 0x7fffffff) return hipErrorInvalidValue;
   const int64_t nwg = vb_tiles(nb);
-  hipError_t e = hipMemsetAsync(flag, 0, 4, stream);
-  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_vb_flag_reset, dim3(1), dim3(64), 0, stream, flag);
   hipLaunchKernelGGL(k_vb_off_partial, dim3((unsigned)nwg), dim3(kVbThreads), 0, stream, bits, nb,
                      (int64_t)n_steps, partial, flag);
   hipLaunchKernelGGL(k_vb_off_scan, dim3(1), dim3(kVbThreads), 0, stream, partial, nwg,

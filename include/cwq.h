@@ -52,7 +52,9 @@
  *     0; out_sample is a sum over steps that starts from 0, not from the
  *     buffer); only capacity past the returned counts (bits_cap, starts_cap,
  *     out_cap) is left untouched.  tests/test_workspace_state_gpu.py holds
- *     every entry point to this.
+ *     every entry point to this, and tests/test_graph_replay_gpu.py holds the
+ *     capturable ones to it under graph replay: each is captured once and
+ *     replayed on outputs and workspaces overwritten between replays.
  *   - Blocks ("groups" in the reference) are described in CSR form:
  *     block g covers dims [block_off[g], block_off[g+1]) of the flat arrays;
  *     block_off is a device int64 array of nb+1 entries.  The *_uniform
@@ -445,7 +447,8 @@ int64_t cwq_code_grouped_greedy_end(const int32_t* idx_host, int64_t G, int n_st
  * or torch's pinned memory); NULL = library-owned pageable staging (slower
  * copies).  sample_host is best page-locked as well.  Returns the total number
  * of groups, or a negative error code.  Returns only after all of its device
- * work has finished (also on error). */
+ * work has finished (also on error): it SYNCHRONISES the stream and is NOT
+ * graph-capturable. */
 size_t cwq_code_grouped_greedy_batch_workspace_size(int64_t D_total, int64_t n_items,
                                                     int n_steps);
 size_t cwq_code_grouped_greedy_batch_host_workspace_size(int64_t D_total, int64_t n_items,
@@ -504,7 +507,8 @@ int cwq_importance_plan(const float* kl, const int64_t* starts, int64_t ng, int6
  * outlier dims and their unquantised draws (outlier_*_host, capacity D,
  * *n_outliers of them), and optionally (kl_sum_out) the total standardised KL
  * in nats for the reference's log line.  Returns G or a negative error code.
- * Blocks the host until the results are on it. */
+ * Blocks the host until the results are on it: SYNCHRONISES the stream, NOT
+ * graph-capturable. */
 size_t cwq_code_grouped_importance_workspace_size(int64_t D);
 int64_t cwq_code_grouped_importance(const float* q_loc, const float* q_scale,
                                     const float* p_loc, const float* p_scale, int64_t D,
@@ -536,7 +540,7 @@ int64_t cwq_code_grouped_importance(const float* q_loc, const float* q_scale,
  *   kl_sum_out [n_items] (optional): each item's standardised KL in nats.
  * opts->eval_ms_out receives the encode launches' milliseconds.  Returns the
  * total number of groups, or a negative error code.  Blocks the host until
- * the results are on it. */
+ * the results are on it: SYNCHRONISES the stream, NOT graph-capturable. */
 size_t cwq_code_grouped_importance_batch_workspace_size(int64_t D_total, int64_t n_items);
 int64_t cwq_code_grouped_importance_batch(
     int64_t n_items, const int64_t* item_off, const float* q_loc, const float* q_scale,
@@ -570,7 +574,9 @@ int64_t cwq_code_grouped_importance_batch(
  * device; either may be NULL, not both.  With sample_host == NULL the call
  * only enqueues work: host_workspace is the source of an asynchronous copy and
  * must stay valid and unchanged until the stream has reached this point, as
- * starts_host of cwq_code_grouped_greedy_begin must until _end.
+ * starts_host of cwq_code_grouped_greedy_begin must until _end.  Either way
+ * the launch follows a plan made on the host from the codes: NOT
+ * graph-capturable.
  * G_total of the size functions: the total number of starts entries
  * (starts_off[n_items] - starts_off[0]).  host_workspace is best page-locked.
  * opts: only eval_start_event / eval_stop_event are read (recorded around the
@@ -594,7 +600,8 @@ int64_t cwq_decode_grouped_greedy_batch(
  * :294), starts_host[starts_off[i], starts_off[i+1]).  Group g of item i is row
  * index[g] of the stream seeded seeds[i] + g.  One plan copy, one launch, one
  * copy out; workspace, staging, sample_host / sample_dev, opts and the return
- * value as above (G_total: the total number of starts entries). */
+ * value as above (G_total: the total number of starts entries); NOT
+ * graph-capturable, as above. */
 size_t cwq_decode_grouped_importance_batch_workspace_size(int64_t D_total, int64_t G_total);
 size_t cwq_decode_grouped_importance_batch_host_workspace_size(int64_t D_total, int64_t G_total);
 int64_t cwq_decode_grouped_importance_batch(

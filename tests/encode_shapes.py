@@ -136,3 +136,81 @@ NEAR_TIE_CASES = {
     "backfit_var": _case("backfit_var", VAR_SHORT_SIZES, [min(b, 8) for b in VAR_SHORT_BITS], 2,
                          27, path="backfit_wave"),
 }
+
+# ---------------------------------------------------------------------------
+# test_graph_replay_gpu.py: one case per encoder path, each captured into a
+# graph at every step count of GRAPH_STEPS (tests/graph_replay.py).  Each case:
+#   entry   the C entry point: "uniform" (cwq_greedy_encode_uniform), "defer"
+#           (cwq_selftest_encode_uniform_defer, ``defer``: its mode), "csr"
+#           (cwq_greedy_encode), "rows_wave" (cwq_selftest_encode_rows_wave)
+#   d, nb   uniform blocks, or ``sizes``: ragged ones
+#   prune   cwq_options.prune_mode
+#   path    the path of every block range (test_encode_plan.py checks it), and
+#           ``tiles``: "one" tile per block, "many" (the interleaved launch, its
+#           tail tiles split), or "queue" (one tile per block, the tile queue)
+#   oracle_stride  the oracle on every n-th block, the whole table against a
+#           prune_mode 0 run that the oracle has confirmed on those blocks
+# The seed and the base make seed + base + g wrap past 2^31 - 1 in every case.
+# ---------------------------------------------------------------------------
+GRAPH_STEPS = (1, 2, 3, 4)
+GRAPH_RHO, GRAPH_SEED, GRAPH_BASE = 0.8, 2 ** 31 - 4, 5
+GRAPH_FAILURE_SHAPE = (32, 12, 70)  # (d, bits, nb) of the failure DESIGN.md 4 recorded
+
+
+def _guni(d, bits, nb, prune, path, tiles=None, entry="uniform", **how):
+    return dict(entry=entry, d=d, sizes=[d] * nb, bits=bits, prune=prune, path=path, tiles=tiles,
+                **how)
+
+
+def _gcsr(sizes, bits, path, entry="csr", prune=2, **how):
+    return dict(entry=entry, d=None, sizes=list(sizes), bits=bits, prune=prune, path=path,
+                tiles=None, **how)
+
+
+GRAPH_CASES = {
+    "exact_uniform": _guni(*WS_UNIFORM_PRUNED[:3], 0, "eval"),
+    # (the tiling aims at 16,384 tiles a launch: below 16,384 blocks a block of
+    # 4,096 candidates is split into tiles of 256, and the uniform entry runs one
+    # tile per block only where the tile queue is on; the deferral selftest's
+    # mode 0 is the single launch with one tile per block and no queue)
+    "prune_d16_mode1": _guni(*WS_UNIFORM_PRUNED[:3], 1, "uniform_pruned", "many"),
+    "prune_d16_mode2": _guni(*WS_UNIFORM_PRUNED[:3], 2, "uniform_pruned", "many"),
+    **{f"prune_d{d}_nb70_mode{m}": _guni(d, 12, 70, m, "uniform_pruned", "many")
+       for d in (8, 32, 64) for m in (1, 2)},
+    "prune_inter": _guni(32, 16, 4, 2, "uniform_pruned", "many"),
+    "prune_one_tile": _guni(*GRAPH_FAILURE_SHAPE, 2, "uniform_pruned", "one", entry="defer",
+                            defer=0),
+    "prune_one_tile_mode1": _guni(*GRAPH_FAILURE_SHAPE, 1, "uniform_pruned", "one",
+                                  entry="defer", defer=0),
+    "tile_queue": _guni(*WS_TILE_QUEUE[:3], 2, "uniform_pruned", "queue", oracle_stride=16),
+    **{f"defer_mode{m}": _guni(*GRAPH_FAILURE_SHAPE, 2, "uniform_pruned", "one", entry="defer",
+                               defer=m) for m in (1, 2, 3)},
+    "general_d5": _guni(*WS_UNIFORM_GENERAL[0][:3], 2, "csr_pruned"),
+    "general_d100": _guni(*WS_UNIFORM_GENERAL[1][:3], 2, "csr_pruned"),
+    "exact_ragged": _gcsr(*WS_EVAL_RAGGED[:2], "eval"),
+    "csr_lane": _gcsr(*WS_CSR_LANE[:2], "csr_pruned"),
+    "csr_all": _gcsr(*WS_CSR_ALL[:2], "csr_pruned"),
+    "small_pipe": _gcsr(*WS_SMALL["pipeline"][:2], "small_pipe"),
+    "small_three": _gcsr(*WS_SMALL["three_kernel"][:2], "small_three"),
+    "rows_wave": _gcsr(ROWS_WAVE_LENGTHS[:8], 9, "rows_wave", entry="rows_wave"),
+    # The few-block cases above once more with their layout repeated to
+    # GRAPH_MIN_BLOCKS blocks or more.  A key left over from the step before
+    # shows only in a block whose best value falls from that step to the next;
+    # with 2 to 8 blocks a case may hold none ("Teeth").
+    "prune_inter_x4": _guni(32, 16, 16, 2, "uniform_pruned", "many"),
+    "general_d5_x3": _guni(WS_UNIFORM_GENERAL[0][0], WS_UNIFORM_GENERAL[0][1],
+                           3 * WS_UNIFORM_GENERAL[0][2], 2, "csr_pruned"),
+    "general_d100_x8": _guni(WS_UNIFORM_GENERAL[1][0], WS_UNIFORM_GENERAL[1][1],
+                             8 * WS_UNIFORM_GENERAL[1][2], 2, "csr_pruned"),
+    "exact_ragged_x6": _gcsr(WS_EVAL_RAGGED[0] * 6, WS_EVAL_RAGGED[1], "eval"),
+    "small_three_x3": _gcsr(WS_SMALL["three_kernel"][0] * 3, WS_SMALL["three_kernel"][1],
+                            "small_three"),
+}
+GRAPH_MIN_BLOCKS = 16
+# the uniform decoders' cases of test_graph_replay_gpu.py: (encoder case, kernel family)
+GRAPH_DECODE_STEPS = (1, 3)  # the LDS-ring float4 kernel takes one step, the other more
+GRAPH_DECODE_CASES = {
+    "uniform_float4": ("prune_d32_nb70_mode2", "uniform", "q4"),   # d % 4 == 0: the float4 kernels
+    "uniform_general": ("general_d5", "uniform", "general"),       # a d they do not take
+    "ragged": ("csr_lane", "csr", "general"),
+}

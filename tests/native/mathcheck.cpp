@@ -206,6 +206,16 @@ void mc_dispatch_consts(int64_t* out) {
   out[1] = CWQ_CSR_COOP_MIN_D;
   out[2] = CWQ_CSR_LDS_DIMS;
 }
+// The uniform encoder's tiling and k_encode_prune's tile queue.
+// out = (tiles_per_block, cand_per_tile, CWQ_QUEUE_MIN_CPT, CWQ_QUEUE_GRID).
+void mc_choose_tiling(int64_t nb, int64_t n_cand, int64_t* out) {
+  cwq::choose_tiling(nb, n_cand, &out[0], &out[1]);
+  out[2] = CWQ_QUEUE_MIN_CPT;
+  out[3] = CWQ_QUEUE_GRID;
+}
+int mc_takes_tile_queue(int64_t ntiles, int64_t cand_per_tile, int64_t queue_grid) {
+  return cwq::takes_tile_queue(ntiles, cand_per_tile, queue_grid);
+}
 
 // The decode dispatch (csrc/cwq_dispatch.h) of one launch_decode call.
 // out = (kernel, qpb, bpw, groups, workgroups); kernel in DecodeKernel's order.

@@ -305,3 +305,23 @@ def test_bad_index_blocks_spread_over_groups_and_chunks(mc, d, qpb, bpw):
         assert len(set(S.bad_blocks(nb))) == 4
     assert len(set(S.bad_blocks(len(S.BAD_RAGGED_SIZES)))) == 4
     assert all(S.BAD_RAGGED_SIZES[b] > 0 for b in S.bad_blocks(len(S.BAD_RAGGED_SIZES)))
+
+
+# ---------------------------------------------------------------------------
+# test_graph_replay_gpu.py: each captured decoder case takes the kernel it names
+# ---------------------------------------------------------------------------
+def test_graph_replay_decoder_cases(mc):
+    import encode_shapes as E
+    seen = set()
+    for name, (enc, entry, family) in E.GRAPH_DECODE_CASES.items():
+        c = E.GRAPH_CASES[enc]
+        for n_steps in E.GRAPH_DECODE_STEPS:
+            if entry == "uniform":
+                k = plan(mc, d=c["d"], nb=len(c["sizes"]), n_steps=n_steps)[0]
+            else:
+                assert c["d"] is None
+                k = plan(mc, nb=len(c["sizes"]), sizes=c["sizes"], n_steps=n_steps)[0]
+            want = GENERAL if family == "general" else (Q4_GLDS if n_steps == 1 else Q4)
+            assert k == want, (name, n_steps)
+            seen.add(k)
+    assert seen == {GENERAL, Q4, Q4_GLDS}

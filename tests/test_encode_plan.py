@@ -421,3 +421,93 @@ def test_near_tie_case_takes_its_path(mc, search_plans, name):
     if c["group"] in ("backfit", "backfit_var"):
         assert n_steps >= 2  # a code of one step is returned as given
         assert backfit.bf_path(max(sizes), nb) == (1 if c["path"] == "backfit_lane" else 0)
+
+
+# ---------------------------------------------------------------------------
+# test_graph_replay_gpu.py: each captured case takes the path it names, at
+# every step count it runs with
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(S.GRAPH_CASES))
+def test_graph_case_takes_its_path(mc, name):
+    mc.mc_choose_tiling.argtypes = [I64, I64, ctypes.POINTER(I64)]
+    mc.mc_choose_tiling.restype = None
+    mc.mc_takes_tile_queue.argtypes = [I64, I64, I64]
+    c = S.GRAPH_CASES[name]
+    sizes, nb, bits = c["sizes"], len(c["sizes"]), c["bits"]
+    want = ENCODE_PATHS[c["path"]]
+    assert (want == EVAL) == (c["prune"] == 0 or c["path"] == "eval")
+    assert S.GRAPH_STEPS == (1, 2, 3, 4)
+    for n_steps in S.GRAPH_STEPS:
+        if c["d"] is not None:
+            whole = plan(mc, csr=False, ud=c["d"], bits=bits, prune=c["prune"], nb=nb,
+                         n_steps=n_steps)
+            assert whole == (want, c["path"] == "csr_pruned", False, 1), (name, n_steps)
+        else:
+            rw = c["entry"] == "rows_wave"
+            whole = plan(mc, csr=True, bits=bits, prune=c["prune"], nb=nb, max_d=max(sizes),
+                         rows_wave=rw, n_steps=n_steps)
+            # a ragged call of several steps forks, a one-step call does not
+            assert whole[3] == (1 if n_steps == 1 else min(3, nb)), (name, n_steps)
+            for n in part_sizes(nb, whole[3]):
+                part = plan(mc, csr=True, bits=bits, prune=c["prune"], nb=n, max_d=max(sizes),
+                            rows_wave=rw, n_steps=n_steps)
+                assert part[0] == want and part[2] == (want == SMALL_PIPE), (name, n_steps, n)
+    consts = (I64 * 3)()
+    mc.mc_dispatch_consts(consts)
+    coop_min_d, lds = consts[1], consts[2]
+    if name == "csr_lane":
+        assert max(sizes) < coop_min_d and 0 in sizes
+    if name == "csr_all":
+        assert lds in sizes and any(n > lds for n in sizes) and any(n < coop_min_d for n in sizes)
+        assert mc.mc_has_long_block_records(1, max(sizes), nb)
+    if name.startswith("general"):
+        assert mc.mc_has_screen_arrays(0, c["d"], nb)
+    if "_x" in name:  # a few-block case's layout repeated
+        base = S.GRAPH_CASES[name[:name.rindex("_x")]]
+        k = int(name[name.rindex("_x") + 2:])
+        assert sizes == base["sizes"] * k and nb >= S.GRAPH_MIN_BLOCKS > len(base["sizes"])
+        assert {q: c[q] for q in c if q != "sizes"} == {q: base[q] for q in base if q != "sizes"}
+    if c["entry"] == "rows_wave":
+        assert sizes == S.ROWS_WAVE_LENGTHS[:8] and 0 in sizes and bits == 9
+    if c["tiles"] is None:
+        return
+    # k_encode_prune's tiling (choose_tiling) and its queue (takes_tile_queue)
+    assert c["d"] % 8 == 0 and 8 <= c["d"] <= 64 and not mc.mc_has_screen_arrays(0, c["d"], nb)
+    t = (I64 * 4)()
+    mc.mc_choose_tiling(nb, 1 << bits, t)
+    tpb, cpt, min_cpt, grid = t[0], t[1], t[2], t[3]
+    assert (min_cpt, grid) == (4096, 1536)
+    if c["entry"] == "defer":
+        # the selftest runs every block as one tile of its whole row count; the
+        # screening-only form's queue grid is its 8 waves per SIMD: 2,048 slots
+        # (deferral needs the screening pass: prune_mode 2; mode 0 is the single
+        # launch, with the screening pass and, prune_mode 1, without it)
+        assert c["defer"] in (0, 1, 2, 3) and c["prune"] in ((1, 2) if c["defer"] == 0 else (2,))
+        assert (c["defer"] == 0) == name.startswith("prune_one_tile")
+        tpb, cpt = 1, ((1 << bits) + 255) // 256 * 256
+        grid = 256 * 8 if c["defer"] else t[3]
+        assert (c["d"], bits, nb) == S.GRAPH_FAILURE_SHAPE
+    queue = bool(mc.mc_takes_tile_queue(nb * tpb, cpt, grid))
+    if c["tiles"] == "one":
+        assert tpb == 1 and cpt >= 1 << bits and not queue
+    elif c["tiles"] == "many":
+        assert tpb > 1 and tpb * cpt == 1 << bits and not queue
+    else:
+        assert c["tiles"] == "queue"
+        assert tpb == 1 and cpt >= min_cpt and nb * tpb > grid and queue
+        # one tile fewer than the grid holds, or a smaller tile: no queue
+        assert not mc.mc_takes_tile_queue(grid, cpt, grid)
+        assert not mc.mc_takes_tile_queue(nb * tpb, min_cpt - 256, grid)
+        assert c["oracle_stride"] == 16
+
+
+def test_graph_cases_cover_the_recorded_failure():
+    d, bits, nb = S.GRAPH_FAILURE_SHAPE
+    assert (d, bits, nb) == (32, 12, 70)
+    for m in (1, 2):
+        c = S.GRAPH_CASES[f"prune_d32_nb70_mode{m}"]
+        assert (c["d"], c["bits"], len(c["sizes"]), c["prune"]) == (d, bits, nb, m)
+    assert 3 in S.GRAPH_STEPS and 4 in S.GRAPH_STEPS
+    # one tile per block without the queue, in both pruning modes
+    one = {c["prune"] for c in S.GRAPH_CASES.values() if c["tiles"] == "one" and not c.get("defer")}
+    assert one == {1, 2}

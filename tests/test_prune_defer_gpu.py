@@ -224,8 +224,9 @@ def test_poisoned_workspace_and_outputs(cwq, cwqlib, pattern):
 def test_graph_capture_and_replay(cwq, cwqlib):
     """The launches of a deferred call are stream work alone, the deferred
     list's length is read on the device: one capture, replayed on poisoned
-    outputs and workspace.  Two steps, so that STEP0 = false is captured too."""
-    d, bits, nb, n_steps = 32, 12, 70, 2
+    outputs and workspace.  Three steps: STEP0 = false is captured too, and two
+    key resets with the same arguments lie between the scoring launches."""
+    d, bits, nb, n_steps = 32, 12, 70, 3
     want = _reference(cwq, d, bits, nb, n_steps)
     call = Call(cwqlib, d, bits, nb, n_steps, _inputs(d, bits, nb))
     call.run(1)  # (first call outside the capture: module loading)
