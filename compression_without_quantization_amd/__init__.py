@@ -30,6 +30,7 @@ from .coded_importance_sampler import (code_grouped_importance_sample,
 from .misc import stateless_normal_sample
 from .pln import ProbabilisticLadderNetwork, build_empirical_dists
 from .parallel import gather_indices, shard_range
+from .ratetable import choose_bits, choose_bits_total, encode_blocks_rate, rate_table
 from .streaming import encode_blocks_host
 from .varbits import (block_bits, code_grouped_greedy_sample_var, decode_blocks_var,
                       decode_grouped_greedy_sample_var, encode_blocks_var, pack_indices,
@@ -55,4 +56,5 @@ __all__ = [
     "encode_blocks_var_beam", "code_grouped_greedy_sample_var_beam",
     "backfit_blocks", "encode_blocks_backfit", "code_grouped_greedy_sample_backfit",
     "backfit_blocks_var", "encode_blocks_var_backfit", "code_grouped_greedy_sample_var_backfit",
+    "rate_table", "choose_bits", "choose_bits_total", "encode_blocks_rate",
 ]

@@ -167,6 +167,10 @@ SIGNATURES = {
     "cwq_greedy_backfit_var": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp,
                                        c_int, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_size, c_opts, c_vp]),
+    "cwq_rate_table_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_int]),
+    "cwq_rate_table": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i32,
+                               c_f32, c_i64, c_vp, c_vp, c_vp, c_size, c_opts, c_vp]),
+    "cwq_choose_bits": (c_int, [c_vp, c_i64, c_int, c_f64, c_int, c_int, c_vp, c_vp, c_vp]),
     "cwq_pln_posterior": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "cwq_permute_gather": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "cwq_permute_scatter": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
@@ -184,7 +188,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 16
+ABI_VERSION = (0 << 16) | 17
 
 _lib = None
 

@@ -7,10 +7,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcwq.so")
 SOURCES = ["cwq_kernels.hip", "cwq_importance.hip", "cwq_pln.hip", "cwq_partition.hip",
-           "cwq_varbits.hip", "cwq_beam.hip", "cwq_backfit.hip", "cwq_capi.hip", "cwq_ac.cpp"]
+           "cwq_varbits.hip", "cwq_beam.hip", "cwq_backfit.hip", "cwq_ratetable.hip",
+           "cwq_capi.hip", "cwq_ac.cpp"]
 HEADERS = ["cwq_math.h", "cwq_screen.h", "cwq_dispatch.h", "cwq_workspace.h", "cwq_kernels.h",
            "cwq_device.h", "cwq_debug.h", "cwq_refill.h", "cwq_imp_plan.h", "cwq_tau_guess.h",
-           "cwq_beam_plan.h", "cwq_budget_plan.h", "cwq_philox_lo.h", "cwq_imp_screen.h"]
+           "cwq_beam_plan.h", "cwq_budget_plan.h", "cwq_philox_lo.h", "cwq_imp_screen.h",
+           "cwq_rate_plan.h"]
 
 # -ffp-contract=off: every FMA in the arithmetic is explicit (bit-exactness).
 # Division and sqrt stay IEEE correctly rounded (hipcc's default

@@ -3240,6 +3240,106 @@ int cwq_greedy_backfit_var(const float* t_loc, const float* t_scale, const float
   return ok();
 }
 
+// ---- rate tables -------------------------------------------------
+size_t cwq_rate_table_workspace_bytes(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                      int max_bits) {
+  if (nb < 0 || total_dims < 0 || max_block_dim < 0 || max_bits < 0 ||
+      max_bits > CWQ_MAX_BITS_PER_STEP)
+    return 0;
+  // sized for either layout of the blocks: ragged needs the most
+  return cwq::rate_ws(true, nb, total_dims, max_block_dim, max_bits).total;
+}
+
+// Launches only, all on `stream`: k_prep_dims (which also zeroes lkeys), the
+// levels launch, one launch_encode per budget above kRateMaxLevel with its
+// keys in a column of hkeys, then the fold and the columns.
+int cwq_rate_table(const float* t_loc, const float* t_scale, const float* p_loc,
+                   const float* p_scale, const int64_t* block_off, int64_t nb,
+                   int64_t total_dims, int64_t max_block_dim, int max_bits, int32_t seed,
+                   float rho, int64_t block_id_base, int32_t* out_idx, float* out_value,
+                   void* workspace, size_t workspace_bytes, const cwq_options* opts,
+                   void* stream) {
+  if (max_bits < 0 || max_bits > CWQ_MAX_BITS_PER_STEP)
+    return fail(CWQ_ERR_INVALID, "max_bits=%d outside [0, %d]", max_bits, CWQ_MAX_BITS_PER_STEP);
+  if (nb < 0) return fail(CWQ_ERR_INVALID, "nb=%lld must be >= 0", (long long)nb);
+  cwq_options o;
+  int rc = read_options(opts, &o);
+  if (rc) return rc;
+  o = without_events(o);
+  if (total_dims < 0 || max_block_dim < 0)
+    return fail(CWQ_ERR_INVALID, "total_dims and max_block_dim must be >= 0");
+  if (!block_off && nb > 0 && (max_block_dim > INT64_MAX / nb || nb * max_block_dim != total_dims))
+    return fail(CWQ_ERR_INVALID, "uniform blocks: total_dims must be nb * max_block_dim");
+  if (nb > 0 && (!out_idx || !out_value)) return fail(CWQ_ERR_INVALID, "out_idx / out_value is null");
+  if (total_dims > 0 && (!t_loc || !t_scale || !p_loc || !p_scale))
+    return fail(CWQ_ERR_INVALID, "null input pointer");
+  if (nb == 0) return ok();  // no block: nothing is launched
+  const bool csr = block_off != nullptr;
+  const int64_t ud = csr ? 0 : max_block_dim;
+  const cwq::RateWs l = cwq::rate_ws(csr, nb, total_dims, max_block_dim, max_bits);
+  // the size asked for is the ragged layout's, which no uniform layout exceeds
+  const size_t need = cwq_rate_table_workspace_bytes(nb, total_dims, max_block_dim, max_bits);
+  if ((rc = check_ws(workspace, workspace_bytes, need, NullWs::Refused))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  void* enc = (char*)workspace + l.enc.off;
+  unsigned long long* lkeys = at<unsigned long long>(workspace, l.lkeys);
+  unsigned long long* hkeys = at<unsigned long long>(workspace, l.hkeys);
+  float* scratch_sample = at<float>(workspace, l.sample);
+  const cwq::RatePlan p = cwq::rate_plan(cwq::RateShape{csr, ud, max_block_dim, nb, max_bits});
+
+  cwq::EncodeArgs a;
+  fill_encode_args(a, t_loc, t_scale, p_loc, p_scale, block_off, ud, nb, total_dims,
+                   max_block_dim, p.levels, 1, seed, rho, block_id_base,
+                   at<int32_t>(workspace, l.idx), scratch_sample, o, l.encl, enc);
+  hipError_t e = cwq::launch_prep_dims(t_scale, p_loc, p_scale, total_dims, 1, rho, a.loc_s,
+                                       a.scale_s, a.lognorm, scratch_sample, lkeys,
+                                       nb * cwq::kRateLevels, st);
+  if (e == hipSuccess)
+    e = cwq::launch_rate_levels(p, t_loc, t_scale, a.loc_s, a.scale_s, a.lognorm, block_off, ud,
+                                seed, block_id_base, lkeys, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_rate_table (levels)");
+  if (!csr) {  // deferral, as cwq_greedy_encode_uniform runs it given the room
+    const cwq::DeferWs dl = cwq::defer_ws(l.encl.total, nb, ud);
+    if (dl.surv.bytes) {
+      a.defer_surv = at<uint32_t>(enc, dl.surv);
+      a.defer_count = at<uint32_t>(enc, dl.count);
+      a.defer_list = at<uint32_t>(enc, dl.dlist);
+      a.defer_dcount = at<uint32_t>(enc, dl.dcount);
+      a.defer_mode = -1;
+    }
+  }
+  for (int b = max_bits; b >= p.high_first; --b) {
+    a.n_cand = (int64_t)1 << b;
+    cwq::choose_tiling(nb, a.n_cand, &a.tiles_per_block, &a.cand_per_tile);
+    a.keys = hkeys + (size_t)(b - p.high_first) * (size_t)nb;
+    if ((e = cwq::launch_encode(a, st)) != hipSuccess)
+      return fail(CWQ_ERR_HIP, "cwq_rate_table (budget %d): %s", b, hipGetErrorString(e));
+  }
+  e = cwq::launch_rate_fold(p, lkeys, hkeys, block_off, ud, nb, max_bits, out_idx, out_value, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_rate_table (fold)");
+  return ok();
+}
+
+int cwq_choose_bits(const float* value, int64_t nb, int max_bits_table, double lam, int min_bits,
+                    int max_bits, int32_t* out_bits, int64_t* out_total, void* stream) {
+  if (max_bits_table < 0 || max_bits_table > CWQ_MAX_BITS_PER_STEP)
+    return fail(CWQ_ERR_INVALID, "max_bits_table=%d outside [0, %d]", max_bits_table,
+                CWQ_MAX_BITS_PER_STEP);
+  if (nb < 0) return fail(CWQ_ERR_INVALID, "nb=%lld must be >= 0", (long long)nb);
+  if (!(lam >= 0.0 && lam < INFINITY))
+    return fail(CWQ_ERR_INVALID, "lam=%g must be finite and >= 0", lam);
+  const int hi = max_bits < max_bits_table ? max_bits : max_bits_table;
+  if (min_bits < 0 || min_bits > hi)
+    return fail(CWQ_ERR_INVALID, "min_bits=%d outside [0, min(max_bits=%d, %d)]", min_bits,
+                max_bits, max_bits_table);
+  if (nb > 0 && (!value || !out_bits)) return fail(CWQ_ERR_INVALID, "value / out_bits is null");
+  if (nb == 0 && !out_total) return ok();  // nothing to write: nothing is launched
+  hipError_t e = cwq::launch_choose_bits(value, nb, max_bits_table + 1, lam, min_bits, hi, out_bits,
+                                         out_total, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_choose_bits");
+  return ok();
+}
+
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream) {
   if (n_waves < 0 || n_waves > (1LL << 31) || (n_waves > 0 && (!x || !out)))
     return fail(CWQ_ERR_INVALID, "cwq_selftest_wave_max: bad arguments");

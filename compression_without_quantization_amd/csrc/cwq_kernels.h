@@ -339,6 +339,29 @@ struct BackfitArgs {
 };
 hipError_t launch_backfit(const BackfitArgs& a, hipStream_t stream);
 
+// ---- rate tables (cwq_ratetable.hip) ---------------------------
+// The levels launch of plan p (rate_plan, cwq_rate_plan.h): the best key of
+// every level of rows [0, 2^p.levels) of every block into lkeys [nb][kRateLevels],
+// which the caller zeroed on the stream.  loc_s, scale_s, lognorm: k_prep_dims'
+// arrays for n_steps = 1.
+hipError_t launch_rate_levels(const RatePlan& p, const float* t_loc, const float* t_scale,
+                              const float* loc_s, const float* scale_s, const float* lognorm,
+                              const int64_t* block_off, int64_t ud, int32_t seed,
+                              int64_t block_id_base, unsigned long long* lkeys,
+                              hipStream_t stream);
+// Columns 0 .. p.levels of out_idx / out_value [nb][max_bits + 1] from lkeys and
+// columns p.high_first .. max_bits from hkeys [p.high_count][nb], the key
+// columns the budgets' launch_encode calls left.
+hipError_t launch_rate_fold(const RatePlan& p, const unsigned long long* lkeys,
+                            const unsigned long long* hkeys, const int64_t* block_off, int64_t ud,
+                            int64_t nb, int max_bits, int32_t* out_idx, float* out_value,
+                            hipStream_t stream);
+// out_bits[g] = the lowest b in [lo, hi] that maximises (double)value[g][b] -
+// lam * (double)b over the table value [nb][n_cols]; *out_total (device, or
+// nullptr) = their sum.
+hipError_t launch_choose_bits(const float* value, int64_t nb, int n_cols, double lam, int lo,
+                              int hi, int32_t* out_bits, int64_t* out_total, hipStream_t stream);
+
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);
 hipError_t launch_selftest_screen(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "cwq_dispatch.h"
+#include "cwq_rate_plan.h"
 
 // Tuning switches of the sizes (tools/variants.sh builds with -D...).
 #ifndef CWQ_CSR_GTAU_STRIDE
@@ -603,6 +604,39 @@ inline BackfitVarWs backfit_var_ws(bool csr, int64_t nb, int64_t total_dims, int
   l.rows = a.take((size_t)n_steps * total_dims * 4);
   l.value = a.take(n * 4);
   l.count = a.take(n * 4);
+  l.total = a.o;
+  return l;
+}
+
+// ---- rate tables (cwq_rate_table, cwq_ratetable.hip) --------------
+//   enc     the encoder's layout for the shape (uniform blocks: with the deferral
+//           regions behind it); its loc_s, scale_s and lognorm serve the levels
+//           launch too, and every budget above kRateMaxLevel runs its
+//           launch_encode in it
+//   lkeys   [nb][kRateLevels] u64: the best key of every level of rows
+//   hkeys   [B - kRateMaxLevel][nb] u64: the argmax keys of budgets 12 .. B, a
+//           column per budget (none for B <= kRateMaxLevel)
+//   sample  [total_dims] f32, idx [nb] i32: what launch_encode writes besides
+//           its keys; nobody reads them
+// cwq_rate_table_workspace_bytes does not know the blocks' form and answers
+// for ragged ones, which no uniform layout of the same blocks exceeds.
+struct RateWs {
+  Region enc, lkeys, hkeys, sample, idx;
+  size_t total;
+  EncWs encl;  // the arrays inside `enc`
+};
+inline RateWs rate_ws(bool csr, int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                      int max_bits) {
+  RateWs l{};
+  Arena a;
+  const size_t n = (size_t)nb;
+  const int high = max_bits > kRateMaxLevel ? max_bits - kRateMaxLevel : 0;
+  l.encl = csr ? enc_ws_csr(nb, total_dims, max_block_dim) : enc_ws_uniform(nb, max_block_dim);
+  l.enc = a.take(csr ? l.encl.total : defer_ws(l.encl.total, nb, max_block_dim).total);
+  l.lkeys = a.take(n * kRateLevels * 8);
+  l.hkeys = a.take(n * (size_t)high * 8);
+  l.sample = a.take((size_t)total_dims * 4);
+  l.idx = a.take(high ? n * 4 : 0);
   l.total = a.o;
   return l;
 }

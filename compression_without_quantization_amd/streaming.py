@@ -91,6 +91,10 @@ def encode_blocks_host(t_loc, t_scale, p_loc, p_scale, n_bits_per_step, n_steps,
                           dtype=torch.uint8, device=dev) for _ in range(nslot)]
         in_done = [torch.cuda.Event() for _ in range(nslot)]  # the slot's inputs are in HBM
         coded = [torch.cuda.Event() for _ in range(nslot)]    # the slot's chunk is coded
+        # The slots come from the compute stream's allocator pool and may be memory
+        # that work still queued on that stream uses (a workspace freed by the call
+        # before this one): the copy stream's first writes wait for that work.
+        copy.wait_stream(compute)
 
         def fetch(c):  # chunk c's results into the caller's arrays (blocks until coded)
             s = c % nslot

@@ -119,8 +119,12 @@ extern "C" {
  *        cwq_selftest_encode_uniform_defer: cwq_greedy_encode_uniform takes a
  *        larger workspace and, given one, defers the pruned kernel's exact
  *        work to launches of its own (same results; every existing size
- *        function answers what it did). */
-#define CWQ_ABI_VERSION ((0 << 16) | 16)
+ *        function answers what it did);
+ *   0.17 rate tables for single-step codes: cwq_rate_table,
+ *        cwq_rate_table_workspace_bytes and cwq_choose_bits (no decoder
+ *        change; every existing call's results and size functions are
+ *        unchanged). */
+#define CWQ_ABI_VERSION ((0 << 16) | 17)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -936,6 +940,59 @@ int cwq_greedy_backfit_var(const float* t_loc, const float* t_scale, const float
                            float* out_value, int32_t* out_accepted, void* workspace,
                            size_t workspace_bytes, const cwq_options* opts, void* stream);
 
+
+/* ---- rate tables: the winning index at every budget ----
+ * Single-step codes only.  Candidate row n of a block is drawn from the flat
+ * indices n d + j of the block's one stream whatever the budget, so the 2^b
+ * rows of a b-bit code are the first 2^b rows of a B-bit code, and one call can
+ * answer for every budget b = 0 .. max_bits:
+ *   out_idx[g * (max_bits + 1) + b]    the index cwq_greedy_encode /
+ *                 cwq_greedy_encode_uniform writes for block g with
+ *                 n_bits_per_step = b, n_steps = 1 and the same seed, rho and
+ *                 block_id_base;
+ *   out_value[g * (max_bits + 1) + b]  the value that row's argmax key holds:
+ *                 the float32 log-density of the row in the coder's summation
+ *                 order, NaN and anything <= -FLT_MAX as -FLT_MAX, -0 as +0.
+ * A block none of whose rows scores above -FLT_MAX gets index 0 at -FLT_MAX, an
+ * empty block index 0 at +0, in every column.
+ *   block_off     device [nb + 1], or NULL for uniform blocks of max_block_dim
+ *                 dims (total_dims = nb * max_block_dim)
+ *   max_bits      B in [0, CWQ_MAX_BITS_PER_STEP]
+ *   out_idx       device [nb, B + 1] int32; out_value device [nb, B + 1] float
+ *   opts          prune_mode selects the scoring kernels of the budgets from 12
+ *                 bits on, as in cwq_greedy_encode; results never depend on it.
+ *                 The eval events are not recorded.
+ * Budgets 0 .. min(B, 11) come from one launch that scores rows [0, 2^11) of
+ * every block once; each budget from 12 on takes the launches of one
+ * cwq_greedy_encode at that budget, so the call costs about two encodes at B
+ * bits.  Everything is enqueued on `stream`: no host wait, no allocation, no
+ * memset or copy; the call can be captured into a graph.
+ * Workspace: cwq_rate_table_workspace_bytes(nb, total_dims, max_block_dim,
+ * max_bits) (for uniform blocks total_dims = nb * max_block_dim), which is the
+ * encoder's layout plus 8 * 12 * nb + 8 * max(B - 11, 0) * nb bytes of keys, a
+ * scratch sample (4 * total_dims) and, from 12 bits on, scratch indices (4 * nb);
+ * less returns CWQ_ERR_WORKSPACE.  Its contents before the call do not matter. */
+size_t cwq_rate_table_workspace_bytes(int64_t nb, int64_t total_dims, int64_t max_block_dim,
+                                      int max_bits);
+int cwq_rate_table(const float* t_loc, const float* t_scale, const float* p_loc,
+                   const float* p_scale, const int64_t* block_off /* NULL: uniform */,
+                   int64_t nb, int64_t total_dims, int64_t max_block_dim, int max_bits,
+                   int32_t seed, float rho, int64_t block_id_base, int32_t* out_idx,
+                   float* out_value, void* workspace, size_t workspace_bytes,
+                   const cwq_options* opts, void* stream);
+
+/* Budgets from a rate table.  out_bits[g] = the lowest b in [min_bits,
+ * min(max_bits, max_bits_table)] that maximises
+ *     (double)value[g * (max_bits_table + 1) + b] - lam * (double)b,
+ * a float64 multiply, then a float64 subtract (no fused multiply-add), compared
+ * with >: lam is the price of a bit in nats.
+ *   value         device [nb, max_bits_table + 1], cwq_rate_table's out_value
+ *   lam           finite and >= 0 (anything else, a NaN included, is refused)
+ *   out_bits      device [nb] int32: cwq_greedy_encode_var's n_bits
+ *   out_total     device, one int64: the sum of out_bits; or NULL
+ * Two launches on `stream` (one without out_total); no host wait. */
+int cwq_choose_bits(const float* value, int64_t nb, int max_bits_table, double lam, int min_bits,
+                    int max_bits, int32_t* out_bits, int64_t* out_total, void* stream);
 
 /* ---- PLN image codec plumbing (csrc/cwq_pln.hip) ----
  * The ladder network's transforms are library convolutions; these three
