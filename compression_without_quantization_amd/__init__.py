@@ -30,7 +30,9 @@ from .coded_importance_sampler import (code_grouped_importance_sample,
 from .misc import stateless_normal_sample
 from .pln import ProbabilisticLadderNetwork, build_empirical_dists
 from .parallel import gather_indices, shard_range
-from .ratetable import choose_bits, choose_bits_total, encode_blocks_rate, rate_table
+from .ratetable import (choose_bits, choose_bits_total, choose_bits_total_device,
+                        code_grouped_greedy_sample_rate, encode_blocks_rate,
+                        encode_blocks_rate_total, rate_table)
 from .streaming import encode_blocks_host
 from .varbits import (block_bits, code_grouped_greedy_sample_var, decode_blocks_var,
                       decode_grouped_greedy_sample_var, encode_blocks_var, pack_indices,
@@ -57,4 +59,5 @@ __all__ = [
     "backfit_blocks", "encode_blocks_backfit", "code_grouped_greedy_sample_backfit",
     "backfit_blocks_var", "encode_blocks_var_backfit", "code_grouped_greedy_sample_var_backfit",
     "rate_table", "choose_bits", "choose_bits_total", "encode_blocks_rate",
+    "choose_bits_total_device", "encode_blocks_rate_total", "code_grouped_greedy_sample_rate",
 ]

@@ -171,6 +171,13 @@ SIGNATURES = {
     "cwq_rate_table": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_i32,
                                c_f32, c_i64, c_vp, c_vp, c_vp, c_size, c_opts, c_vp]),
     "cwq_choose_bits": (c_int, [c_vp, c_i64, c_int, c_f64, c_int, c_int, c_vp, c_vp, c_vp]),
+    "cwq_choose_bits_total_workspace_bytes": (c_size, [c_int]),
+    "cwq_choose_bits_total": (c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp,
+                                      c_vp, c_size, c_vp]),
+    "cwq_greedy_encode_rate_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_int]),
+    "cwq_greedy_encode_rate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
+                                       c_i64, c_int, c_i32, c_f32, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_size, c_opts, c_vp]),
     "cwq_pln_posterior": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "cwq_permute_gather": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "cwq_permute_scatter": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
@@ -188,7 +195,7 @@ TOOL_SIGNATURES = {
 
 # CWQ_ABI_VERSION of the include/cwq.h these signatures mirror: a library
 # reporting another version has other argument lists and is refused.
-ABI_VERSION = (0 << 16) | 17
+ABI_VERSION = (0 << 16) | 18
 
 _lib = None
 

@@ -12,7 +12,7 @@ SOURCES = ["cwq_kernels.hip", "cwq_importance.hip", "cwq_pln.hip", "cwq_partitio
 HEADERS = ["cwq_math.h", "cwq_screen.h", "cwq_dispatch.h", "cwq_workspace.h", "cwq_kernels.h",
            "cwq_device.h", "cwq_debug.h", "cwq_refill.h", "cwq_imp_plan.h", "cwq_tau_guess.h",
            "cwq_beam_plan.h", "cwq_budget_plan.h", "cwq_philox_lo.h", "cwq_imp_screen.h",
-           "cwq_rate_plan.h"]
+           "cwq_rate_plan.h", "cwq_rate_solve.h"]
 
 # -ffp-contract=off: every FMA in the arithmetic is explicit (bit-exactness).
 # Division and sqrt stay IEEE correctly rounded (hipcc's default

@@ -3340,6 +3340,108 @@ int cwq_choose_bits(const float* value, int64_t nb, int max_bits_table, double l
   return ok();
 }
 
+// ---- budgets under a total -----------------------------------------
+size_t cwq_choose_bits_total_workspace_bytes(int max_bits_table) {
+  if (max_bits_table < 0 || max_bits_table > CWQ_MAX_BITS_PER_STEP) return 0;
+  return cwq::solve_ws(0, max_bits_table).total;
+}
+
+namespace {
+// The refusals cwq_choose_bits_total and cwq_greedy_encode_rate share; *hi: the
+// top of the budgets' range.
+int check_total_ranges(int64_t nb, int max_bits_table, int64_t total_bits, int min_bits,
+                       int max_bits, int* hi) {
+  if (max_bits_table < 0 || max_bits_table > CWQ_MAX_BITS_PER_STEP)
+    return fail(CWQ_ERR_INVALID, "max_bits_table=%d outside [0, %d]", max_bits_table,
+                CWQ_MAX_BITS_PER_STEP);
+  if (nb < 0) return fail(CWQ_ERR_INVALID, "nb=%lld must be >= 0", (long long)nb);
+  *hi = max_bits < max_bits_table ? max_bits : max_bits_table;
+  if (min_bits < 0 || min_bits > *hi)
+    return fail(CWQ_ERR_INVALID, "min_bits=%d outside [0, min(max_bits=%d, %d)]", min_bits,
+                max_bits, max_bits_table);
+  if ((__int128)nb * min_bits > (__int128)total_bits)
+    return fail(CWQ_ERR_INVALID, "%lld blocks at min_bits=%d exceed total_bits=%lld",
+                (long long)nb, min_bits, (long long)total_bits);
+  return CWQ_OK;
+}
+}  // namespace
+
+// Launches only (launch_choose_bits_total): a reset, the sweep at lam = 0,
+// kSolveRounds rounds of a one-wave step and a sweep of the tree it laid out,
+// the last step, and the pass that writes the bits at the final lam_hi.
+int cwq_choose_bits_total(const float* value, int64_t nb, int max_bits_table, int64_t total_bits,
+                          int min_bits, int max_bits, int32_t* out_bits, double* out_lam,
+                          int64_t* out_total, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  int hi = 0;
+  int rc = check_total_ranges(nb, max_bits_table, total_bits, min_bits, max_bits, &hi);
+  if (rc) return rc;
+  if (nb == 0) return ok();  // no block: nothing is launched
+  if (!value || !out_bits || !out_lam || !out_total)
+    return fail(CWQ_ERR_INVALID, "value / out_bits / out_lam / out_total is null");
+  const cwq::SolveWs l = cwq::solve_ws(0, max_bits_table);
+  if ((rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
+  hipError_t e = cwq::launch_choose_bits_total(
+      value, nb, max_bits_table + 1, total_bits, min_bits, hi, out_bits, out_lam, out_total,
+      at<cwq::SolveState>(workspace, l.state), at<double>(workspace, l.prod),
+      at<int64_t>(workspace, l.totals), (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "cwq_choose_bits_total");
+  return ok();
+}
+
+size_t cwq_greedy_encode_rate_workspace_bytes(int64_t nb, int64_t total_dims,
+                                              int64_t max_block_dim, int max_bits) {
+  if (nb < 0 || total_dims < 0 || max_block_dim < 0 || max_bits < 0 ||
+      max_bits > CWQ_MAX_BITS_PER_STEP)
+    return 0;
+  return cwq::enc_rate_ws(nb, total_dims, max_block_dim, max_bits).total;
+}
+
+// Launches only: cwq_rate_table's into the table inside the workspace (or the
+// caller's out_value), the solver's, the gather and the decoder's.
+int cwq_greedy_encode_rate(const float* t_loc, const float* t_scale, const float* p_loc,
+                           const float* p_scale, const int64_t* block_off, int64_t nb,
+                           int64_t total_dims, int64_t max_block_dim, int max_bits,
+                           int64_t total_bits, int min_bits, int32_t seed, float rho,
+                           int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                           int32_t* out_bits, double* out_lam, int64_t* out_total,
+                           float* out_value, void* workspace, size_t workspace_bytes,
+                           const cwq_options* opts, void* stream) {
+  if (max_bits < 0 || max_bits > CWQ_MAX_BITS_PER_STEP)
+    return fail(CWQ_ERR_INVALID, "max_bits=%d outside [0, %d]", max_bits, CWQ_MAX_BITS_PER_STEP);
+  int hi = 0;
+  int rc = check_total_ranges(nb, max_bits, total_bits, min_bits, max_bits, &hi);
+  if (rc) return rc;
+  if (total_dims < 0 || max_block_dim < 0)
+    return fail(CWQ_ERR_INVALID, "total_dims and max_block_dim must be >= 0");
+  if (nb > 0 && (!out_idx || !out_bits || !out_lam || !out_total))
+    return fail(CWQ_ERR_INVALID, "out_idx / out_bits / out_lam / out_total is null");
+  if (total_dims > 0 && !out_sample) return fail(CWQ_ERR_INVALID, "out_sample is null");
+  const cwq::EncRateWs l = cwq::enc_rate_ws(nb, total_dims, max_block_dim, max_bits);
+  if (nb > 0 && (rc = check_ws(workspace, workspace_bytes, l.total, NullWs::Refused))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* tidx = nb > 0 ? at<int32_t>(workspace, l.tidx) : nullptr;
+  float* tvalue = out_value ? out_value : (nb > 0 ? at<float>(workspace, l.tvalue) : nullptr);
+  // (the table call checks the inputs, the blocks' form and the options)
+  if ((rc = cwq_rate_table(t_loc, t_scale, p_loc, p_scale, block_off, nb, total_dims,
+                           max_block_dim, max_bits, seed, rho, block_id_base, tidx, tvalue,
+                           workspace, l.rate.bytes, opts, stream)))
+    return rc;
+  if (nb == 0) return ok();  // no block: nothing is launched
+  hipError_t e = cwq::launch_choose_bits_total(
+      tvalue, nb, max_bits + 1, total_bits, min_bits, hi, out_bits, out_lam, out_total,
+      at<cwq::SolveState>(workspace, l.solve.state), at<double>(workspace, l.solve.prod),
+      at<int64_t>(workspace, l.solve.totals), st);
+  if (e == hipSuccess) e = cwq::launch_rate_gather(tidx, out_bits, nb, max_bits + 1, out_idx, st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_rate (budgets)");
+  // the decoders take the bit count only as the indices' range
+  e = cwq::launch_decode(out_idx, p_loc, p_scale, block_off, block_off ? 0 : max_block_dim, nb,
+                         total_dims, CWQ_MAX_BITS_PER_STEP, 1, seed, rho, block_id_base, out_sample,
+                         st);
+  if (e != hipSuccess) return hip_fail(e, "cwq_greedy_encode_rate (decode)");
+  return ok();
+}
+
 int cwq_selftest_wave_max(const float* x, int64_t n_waves, float* out, void* stream) {
   if (n_waves < 0 || n_waves > (1LL << 31) || (n_waves > 0 && (!x || !out)))
     return fail(CWQ_ERR_INVALID, "cwq_selftest_wave_max: bad arguments");

@@ -361,6 +361,17 @@ hipError_t launch_rate_fold(const RatePlan& p, const unsigned long long* lkeys,
 // nullptr) = their sum.
 hipError_t launch_choose_bits(const float* value, int64_t nb, int n_cols, double lam, int lo,
                               int hi, int32_t* out_bits, int64_t* out_total, hipStream_t stream);
+// launch_choose_bits at the price 60 halvings of [0, span] find for a total of at
+// most `target` (ratetable.choose_bits_total's result; nb > 0):
+// kSolveLaunches launches, *out_lam and *out_total are device words; state,
+// prod and totals are solve_ws' regions, whatever they hold.
+hipError_t launch_choose_bits_total(const float* value, int64_t nb, int n_cols, int64_t target,
+                                    int lo, int hi, int32_t* out_bits, double* out_lam,
+                                    int64_t* out_total, SolveState* state, double* prod,
+                                    int64_t* totals, hipStream_t stream);
+// out_idx[g] = tidx[g][bits[g]] over the table tidx [nb][n_cols]
+hipError_t launch_rate_gather(const int32_t* tidx, const int32_t* bits, int64_t nb, int n_cols,
+                              int32_t* out_idx, hipStream_t stream);
 
 hipError_t launch_selftest_bm(uint32_t m0, int64_t count, float* rad, float* sn, float* cs,
                               hipStream_t stream);

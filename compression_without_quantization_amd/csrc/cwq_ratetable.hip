@@ -240,7 +240,235 @@ __global__ void __launch_bounds__(256) k_choose_bits(const float* __restrict__ v
   if ((threadIdx.x & 63) == 0 && sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
 }
 
+// ---- budgets under a total (cwq_rate_solve.h) ---------------------
+// The sweeps read the table a tile of 64 rows per wave at a time: the tile is
+// 64 n_cols contiguous floats, loaded coalesced into LDS at a row stride of
+// n_cols | 1 words, from which lane l reads row l.  ds_read_b32 banks are the
+// word address mod 32 within each half of the wave, and an odd stride sends 32
+// consecutive rows to 32 different banks.  Per-lane totals are 32-bit: a
+// workgroup's share of the rows of a table that fits the device's memory sums
+// far below 2^32 (4 (B + 1) nb bytes of table bound nb B).
+constexpr int kSolveWaves = 4;               // per workgroup
+// The grid: 256 CUs x the workgroups of k_solve_sweep a CU holds at once, so
+// that no workgroup waits for another to end; the tiles beyond are strided
+// over.  A CU holds what its registers and its LDS both allow: by registers a
+// wave of each workgroup per SIMD (r = 3, 4, 5, 6: 67, 77, 109, 167 VGPRs as
+// hipcc of ROCm 7 allots them, i.e. 7, 6, 4, 3 waves of the 512 a SIMD lane
+// has), by LDS 160 KiB over the workgroup's tiles (solve_grid below).
+constexpr unsigned kSolveWgPerCuRegs = kSolveLevels == 6 ? 3 : kSolveLevels == 5 ? 4
+                                       : kSolveLevels == 4 ? 6 : 7;
+constexpr size_t kSolveLdsPerCu = 160 * 1024;
+constexpr size_t kSolveStaticLds = 8 * kSolveSlots;  // k_solve_sweep's wg_tot
+
+__global__ void k_solve_reset(SolveState* __restrict__ st) {
+  st->span_key = 0;
+  st->total0 = 0;
+  st->done = 0;
+}
+
+// This wave's next tile into `mine`; returns the row of this lane, or nullptr
+// past the table's end.  Full exec mask.
+__device__ __forceinline__ const float* solve_stage(const float* __restrict__ value, int64_t tile,
+                                                    int64_t nb, int n_cols, int stride, float* mine,
+                                                    uint32_t lane) {
+  const int64_t row0 = tile * 64;
+  const int rows = nb - row0 < 64 ? (int)(nb - row0) : 64;
+  const int cnt = rows * n_cols;
+  const float* src = value + row0 * n_cols;
+  // the reads of the tile before are done before this one's stores
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (int i = (int)lane; i < cnt; i += 64) {
+    const int r = i / n_cols;
+    mine[r * stride + (i - r * n_cols)] = src[i];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return (int)lane < rows ? mine + lane * stride : nullptr;
+}
+
+// One price.  FIRST: lam = 0; total(0) and the span's key go to the state, no
+// bits are written.  Else lam = *lam_p (the last step's), and the bits and
+// their sum are the call's results.  k_choose_bits' arithmetic, term for term.
+template <bool FIRST>
+__global__ void __launch_bounds__(64 * kSolveWaves) k_solve_single(
+    const float* __restrict__ value, int64_t nb, int n_cols, int lo, int hi, int stride,
+    int64_t tiles, const double* __restrict__ lam_p, SolveState* __restrict__ st,
+    int32_t* __restrict__ out_bits, long long* __restrict__ out_total) {
+  extern __shared__ float solve_rows[];
+  const uint32_t lane = threadIdx.x & 63u, wv = wave_id();
+  float* mine = solve_rows + (size_t)wv * 64 * stride;
+  const double lam = FIRST ? 0.0 : *lam_p;
+  long long sum = 0;
+  uint64_t span = 0;
+  for (int64_t t = (int64_t)blockIdx.x * kSolveWaves + wv; t < tiles;
+       t += (int64_t)gridDim.x * kSolveWaves) {
+    const float* row = solve_stage(value, t, nb, n_cols, stride, mine, lane);
+    if (row) {
+      const double v_lo = (double)row[lo];
+      int best_b = lo;
+      double best = v_lo - solve_product(lam, lo);
+      for (int b = lo + 1; b <= hi; ++b) {
+        const double v = (double)row[b];
+        const double s = v - solve_product(lam, b);
+        if (s > best) best = s, best_b = b;
+        if (FIRST) {
+          const uint64_t k = solve_span_key(v - v_lo);
+          span = k > span ? k : span;
+        }
+      }
+      if (!FIRST) out_bits[t * 64 + lane] = best_b;
+      sum += best_b;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  long long* total = FIRST ? (long long*)&st->total0 : out_total;
+  if (lane == 0 && sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
+  if (FIRST) {
+    span = wave_max_u64(span);
+    if (lane == 0 && span) atomicMax((unsigned long long*)&st->span_key, (unsigned long long)span);
+  }
+}
+
+// One wave between two sweeps.  Round 0 starts the interval from the first
+// sweep's facts; round i > 0 walks the tree of round i - 1 by its totals.  Before
+// the last round's end it lays out the next tree (lane k: node k's products)
+// and zeroes its totals; at the end it writes lam_hi and zeroes the sum the
+// last pass adds to.
+__global__ void __launch_bounds__(64) k_solve_step(SolveState* __restrict__ st,
+                                                   double* __restrict__ prod,
+                                                   long long* __restrict__ totals, int64_t target,
+                                                   int n_budgets, int round,
+                                                   double* __restrict__ out_lam,
+                                                   long long* __restrict__ out_total) {
+  const int k = (int)threadIdx.x;
+  SolveInterval iv;
+  int done;
+  if (round == 0) {
+    iv = solve_start(st->total0, target, solve_span_of(st->span_key));
+    done = st->total0 <= target;
+  } else {
+    iv = SolveInterval{st->lo, st->hi};
+    done = st->done;
+    if (!done) iv = solve_walk(iv, (const int64_t*)totals, target);
+  }
+  // Every lane has read the state and walked the totals before any lane zeroes
+  // them: this barrier is the only thing that orders the two, so the kernel
+  // must stay at one workgroup (it is launched as one wave).  All lanes walk,
+  // redundantly: each needs the interval for its node.
+  __syncthreads();
+  if (round < kSolveRounds) {
+    if (k < kSolveSlots) {
+      solve_fill_node(iv, k, n_budgets, prod);
+      totals[k] = 0;
+    }
+    if (k == 0) st->lo = iv.lo, st->hi = iv.hi, st->done = done;
+  } else if (k == 0) {
+    *out_lam = iv.hi;
+    *out_total = 0;
+  }
+}
+
+// total(mid_k) of every node of the tree in `prod`, eight nodes at a time: a
+// lane holds its row's value at b once per eight nodes, subtracts the nodes'
+// products (wave-uniform) and keeps eight running maxima, k_choose_bits' rule
+// with the multiply taken out.  Slot 0 is no node; it is evaluated (at lam 0)
+// for the loop's regularity and nobody reads its total.
+__global__ void __launch_bounds__(64 * kSolveWaves) k_solve_sweep(
+    const float* __restrict__ value, int64_t nb, int n_cols, int lo, int hi, int stride,
+    int64_t tiles, const SolveState* __restrict__ st, const double* __restrict__ prod,
+    long long* __restrict__ totals) {
+  extern __shared__ float solve_rows[];
+  __shared__ unsigned long long wg_tot[kSolveSlots];
+  if (st->done) return;  // uniform over the grid
+  const uint32_t lane = threadIdx.x & 63u, wv = wave_id();
+  float* mine = solve_rows + (size_t)wv * 64 * stride;
+  if (threadIdx.x < kSolveSlots) wg_tot[threadIdx.x] = 0ull;
+  uint32_t tot[kSolveSlots];
+#pragma unroll
+  for (int k = 0; k < kSolveSlots; ++k) tot[k] = 0;
+  for (int64_t t = (int64_t)blockIdx.x * kSolveWaves + wv; t < tiles;
+       t += (int64_t)gridDim.x * kSolveWaves) {
+    const float* row = solve_stage(value, t, nb, n_cols, stride, mine, lane);
+    const double v_lo = row ? (double)row[lo] : 0.0;
+#pragma unroll
+    for (int c = 0; row && c < kSolveSlots; c += 8) {
+      double best[8];
+      int best_b[8];
+      const double* p = prod + solve_prod_at(lo, c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) best[j] = v_lo - p[j], best_b[j] = lo;
+      for (int b = lo + 1; b <= hi; ++b) {
+        const double v = (double)row[b];
+        p = prod + solve_prod_at(b, c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const double s = v - p[j];
+          if (s > best[j]) best[j] = s, best_b[j] = b;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tot[c + j] += (uint32_t)best_b[j];
+    }
+  }
+  __syncthreads();  // wg_tot is zero
+#pragma unroll
+  for (int k = 0; k < kSolveSlots; ++k) {
+    uint32_t s = tot[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0 && s) atomicAdd(&wg_tot[k], (unsigned long long)s);
+  }
+  __syncthreads();
+  if (threadIdx.x < kSolveSlots && wg_tot[threadIdx.x])
+    atomicAdd((unsigned long long*)&totals[threadIdx.x], wg_tot[threadIdx.x]);
+}
+
+// out_idx[g] = the table's index at the budget chosen for block g
+__global__ void __launch_bounds__(256) k_rate_gather(const int32_t* __restrict__ tidx,
+                                                     const int32_t* __restrict__ bits, int64_t nb,
+                                                     int n_cols, int32_t* __restrict__ out_idx) {
+  for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < nb;
+       g += (int64_t)gridDim.x * blockDim.x)
+    out_idx[g] = tidx[g * n_cols + bits[g]];
+}
+
 }  // namespace
+
+hipError_t launch_choose_bits_total(const float* value, int64_t nb, int n_cols, int64_t target,
+                                    int lo, int hi, int32_t* out_bits, double* out_lam,
+                                    int64_t* out_total, SolveState* state, double* prod,
+                                    int64_t* totals, hipStream_t stream) {
+  const int stride = n_cols | 1;
+  const size_t lds = (size_t)kSolveWaves * 64 * stride * sizeof(float);
+  const int64_t tiles = (nb + 63) / 64;
+  const unsigned by_lds = (unsigned)(kSolveLdsPerCu / (lds + kSolveStaticLds));  // >= 5: lds <= 31 KiB
+  const unsigned per_cu = by_lds < kSolveWgPerCuRegs ? by_lds : kSolveWgPerCuRegs;
+  const dim3 grid(grid_for(tiles, kSolveWaves, 256 * per_cu)), wg(64 * kSolveWaves);
+  long long* tot = (long long*)totals;
+  hipLaunchKernelGGL(k_solve_reset, dim3(1), dim3(1), 0, stream, state);
+  hipLaunchKernelGGL(k_solve_single<true>, grid, wg, lds, stream, value, nb, n_cols, lo, hi, stride,
+                     tiles, (const double*)nullptr, state, (int32_t*)nullptr, (long long*)nullptr);
+  for (int round = 0; round <= kSolveRounds; ++round) {
+    hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(64), 0, stream, state, prod, tot, target, n_cols,
+                       round, out_lam, (long long*)out_total);
+    if (round < kSolveRounds)
+      hipLaunchKernelGGL(k_solve_sweep, grid, wg, lds, stream, value, nb, n_cols, lo, hi, stride,
+                         tiles, (const SolveState*)state, (const double*)prod, tot);
+  }
+  hipLaunchKernelGGL(k_solve_single<false>, grid, wg, lds, stream, value, nb, n_cols, lo, hi, stride,
+                     tiles, (const double*)out_lam, state, out_bits, (long long*)out_total);
+  return hipGetLastError();
+}
+
+hipError_t launch_rate_gather(const int32_t* tidx, const int32_t* bits, int64_t nb, int n_cols,
+                              int32_t* out_idx, hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rate_gather, dim3(grid_for(nb, 256, 4096)), dim3(256), 0, stream, tidx, bits,
+                     nb, n_cols, out_idx);
+  return hipGetLastError();
+}
 
 hipError_t launch_rate_levels(const RatePlan& p, const float* t_loc, const float* t_scale,
                               const float* loc_s, const float* scale_s, const float* lognorm,

@@ -14,6 +14,7 @@
 
 #include "cwq_dispatch.h"
 #include "cwq_rate_plan.h"
+#include "cwq_rate_solve.h"
 
 // Tuning switches of the sizes (tools/variants.sh builds with -D...).
 #ifndef CWQ_CSR_GTAU_STRIDE
@@ -638,6 +639,49 @@ inline RateWs rate_ws(bool csr, int64_t nb, int64_t total_dims, int64_t max_bloc
   l.sample = a.take((size_t)total_dims * 4);
   l.idx = a.take(high ? n * 4 : 0);
   l.total = a.o;
+  return l;
+}
+
+// ---- budgets under a total (cwq_choose_bits_total) ------------------
+//   state   one SolveState (cwq_rate_solve.h)
+//   prod    [B + 1][kSolveSlots] f64: mid_k * b of the current tree's nodes
+//   totals  [kSolveSlots] i64: total(mid_k) of the current tree's nodes
+// The size depends on the table's B alone.
+struct SolveWs {
+  Region state, prod, totals;
+  size_t total;
+};
+inline SolveWs solve_ws(size_t base, int max_bits_table) {
+  SolveWs l;
+  Arena a{Arena::up(base)};
+  l.state = a.take(sizeof(SolveState));
+  l.prod = a.take((size_t)(max_bits_table + 1) * kSolveSlots * 8);
+  l.totals = a.take((size_t)kSolveSlots * 8);
+  l.total = a.o;
+  return l;
+}
+
+// ---- a code under a total from the distributions (cwq_greedy_encode_rate, 4k) ------
+// The rate table's layout for the shape, then the table itself and the solver's:
+//   rate    cwq_rate_table's workspace (rate_ws; sized for ragged blocks, as
+//           cwq_rate_table_workspace_bytes is)
+//   tidx    [nb][B + 1] i32: the table's indices, which the gather reads
+//   tvalue  [nb][B + 1] f32: its values, when the caller does not ask for them
+//   solve   cwq_choose_bits_total's workspace (offsets from the call's base)
+struct EncRateWs {
+  Region rate, tidx, tvalue;
+  SolveWs solve;
+  size_t total;
+};
+inline EncRateWs enc_rate_ws(int64_t nb, int64_t total_dims, int64_t max_block_dim, int max_bits) {
+  EncRateWs l;
+  Arena a;
+  const size_t cells = (size_t)nb * (size_t)(max_bits + 1);
+  l.rate = a.take(rate_ws(true, nb, total_dims, max_block_dim, max_bits).total);
+  l.tidx = a.take(cells * 4);
+  l.tvalue = a.take(cells * 4);
+  l.solve = solve_ws(a.o, max_bits);
+  l.total = l.solve.total;
   return l;
 }
 

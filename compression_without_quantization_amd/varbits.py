@@ -321,11 +321,13 @@ def decode_blocks_var(code_or_idx, n_bits, p_loc, p_scale, n_steps, seed, rho=1.
 # the grouped coder with a budget per group (composed from the calls above)
 # ---------------------------------------------------------------------------
 def _code_grouped_var_with(encode, target, proposal, n_steps, n_bits_per_step, seed,
-                           max_group_size_bits, extra_bits, min_bits):
+                           max_group_size_bits, extra_bits, min_bits, encoder_chooses_bits=False):
     """code_grouped_greedy_sample_var's pipeline around a block encoder:
     standardise, per-dim KL, partition, budgets, ``encode(t_loc, t_scale, zeros,
     ones, bits, starts)`` -> (idx, sample) on the standard proposal,
-    destandardise, pack_indices."""
+    destandardise, pack_indices.  With ``encoder_chooses_bits`` the encoder
+    returns (idx, sample, the budgets it coded at) and those are packed and
+    returned in place of block_bits' budgets."""
     lib = _lib.load()
     dev = _device_of(target.loc, target.scale, proposal.loc, proposal.scale)
     q_loc, q_scale = _dist_parts(target, dev, "Target")
@@ -349,7 +351,10 @@ def _code_grouped_var_with(encode, target, proposal, n_steps, n_bits_per_step, s
                       n_steps=n_steps, min_bits=min_bits, max_bits=n_bits_per_step)
     zeros = torch.zeros(D, dtype=torch.float32, device=dev)
     ones = torch.ones(D, dtype=torch.float32, device=dev)
-    idx, sample = encode(t_loc, t_scale, zeros, ones, bits, starts)
+    if encoder_chooses_bits:
+        idx, sample, bits = encode(t_loc, t_scale, zeros, ones, bits, starts)
+    else:
+        idx, sample = encode(t_loc, t_scale, zeros, ones, bits, starts)
     out = torch.empty(D, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.cwq_destandardise(_ptr(sample), _ptr(p_loc), _ptr(p_scale), D, _ptr(out),

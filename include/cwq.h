@@ -123,8 +123,11 @@ extern "C" {
  *   0.17 rate tables for single-step codes: cwq_rate_table,
  *        cwq_rate_table_workspace_bytes and cwq_choose_bits (no decoder
  *        change; every existing call's results and size functions are
- *        unchanged). */
-#define CWQ_ABI_VERSION ((0 << 16) | 17)
+ *        unchanged);
+ *   0.18 budgets under a bit total, solved on the device: cwq_choose_bits_total,
+ *        cwq_greedy_encode_rate and their workspace sizes (no decoder change;
+ *        every existing call's results and size functions are unchanged). */
+#define CWQ_ABI_VERSION ((0 << 16) | 18)
 int cwq_version(void);
 
 /* Thread-local description of the last error ("" if none). */
@@ -993,6 +996,61 @@ int cwq_rate_table(const float* t_loc, const float* t_scale, const float* p_loc,
  * Two launches on `stream` (one without out_total); no host wait. */
 int cwq_choose_bits(const float* value, int64_t nb, int max_bits_table, double lam, int min_bits,
                     int max_bits, int32_t* out_bits, int64_t* out_total, void* stream);
+
+/* Budgets from a rate table whose sum is at most total_bits:
+ * cwq_choose_bits at the price lam that 60 halvings of an interval find.  With
+ * lo = min_bits, hi = min(max_bits, max_bits_table) and total(lam) the sum of
+ * cwq_choose_bits(value, ..., lam, lo, hi):
+ *   total(0) <= total_bits: lam = 0.  Else the interval starts as (0, the largest
+ *   (double)value[g, b] - (double)value[g, lo] over g and b in [lo, hi]); 60
+ *   times mid = 0.5 * (low end + high end) in float64 and the high end moves to
+ *   mid when total(mid) <= total_bits, the low end otherwise; lam = the high end.
+ * The totals are taken three halvings at a time, for the 7 mids those halvings
+ * can reach, in one pass over the table; the result is bit for bit the one of
+ * the 60 single steps.
+ *   out_bits      device [nb] int32: cwq_choose_bits at lam
+ *   out_lam       device, one double: lam
+ *   out_total     device, one int64: the sum of out_bits; at most total_bits for
+ *                 every finite table
+ * Refused with CWQ_ERR_INVALID before any launch: the ranges cwq_choose_bits
+ * refuses, and nb * min_bits > total_bits (no budgets fit).
+ * Enqueues 44 launches on `stream`: no host wait, no allocation, no memset or
+ * copy; the call can be captured into a graph.  nb = 0: nothing is launched.
+ * Workspace: cwq_choose_bits_total_workspace_bytes(max_bits_table); less returns
+ * CWQ_ERR_WORKSPACE.  Its contents before the call do not matter. */
+size_t cwq_choose_bits_total_workspace_bytes(int max_bits_table);
+int cwq_choose_bits_total(const float* value, int64_t nb, int max_bits_table, int64_t total_bits,
+                          int min_bits, int max_bits, int32_t* out_bits, double* out_lam,
+                          int64_t* out_total, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
+/* A single-step code under a bit total from the distributions, in one call:
+ * cwq_rate_table's launches into a table inside the workspace,
+ * cwq_choose_bits_total on it with budgets in [min_bits, max_bits], the table's
+ * index at each block's budget, and the decoder for the sample.  The first nine
+ * arguments, seed, rho, block_id_base and opts are cwq_rate_table's.
+ *   out_idx       device [nb] int32: block g's index at out_bits[g] bits, what
+ *                 cwq_greedy_encode_var writes for these budgets at n_steps = 1
+ *   out_sample    device [total_dims]: cwq_greedy_decode(_uniform) of out_idx
+ *   out_bits, out_lam, out_total   as cwq_choose_bits_total writes them
+ *   out_value     device [nb, max_bits + 1], or NULL: the table's values
+ * Refusals: cwq_rate_table's and cwq_choose_bits_total's.  Everything is
+ * enqueued on `stream`: no host wait, no allocation, no memset or copy; the
+ * call can be captured into a graph.  nb = 0: nothing is launched.
+ * Workspace: cwq_greedy_encode_rate_workspace_bytes(nb, total_dims,
+ * max_block_dim, max_bits): cwq_rate_table's, the table (8 * nb * (max_bits + 1)
+ * bytes) and the solver's; less returns CWQ_ERR_WORKSPACE.  Its contents before
+ * the call do not matter. */
+size_t cwq_greedy_encode_rate_workspace_bytes(int64_t nb, int64_t total_dims,
+                                              int64_t max_block_dim, int max_bits);
+int cwq_greedy_encode_rate(const float* t_loc, const float* t_scale, const float* p_loc,
+                           const float* p_scale, const int64_t* block_off /* NULL: uniform */,
+                           int64_t nb, int64_t total_dims, int64_t max_block_dim, int max_bits,
+                           int64_t total_bits, int min_bits, int32_t seed, float rho,
+                           int64_t block_id_base, int32_t* out_idx, float* out_sample,
+                           int32_t* out_bits, double* out_lam, int64_t* out_total,
+                           float* out_value /* or NULL */, void* workspace,
+                           size_t workspace_bytes, const cwq_options* opts, void* stream);
 
 /* ---- PLN image codec plumbing (csrc/cwq_pln.hip) ----
  * The ladder network's transforms are library convolutions; these three
